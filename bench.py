@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: rays/sec rendering full synthetic 512x512 frames of a 2-person scene on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (Multiply.forward, eval mode, all persons, with background) over one batch of
 synthetic input = one full 512x512 frame = 262,144 rays (BASELINE.json configs[1]: 2 persons, 128 importance
@@ -15,9 +15,17 @@ background rays), every rank renders its share and ONE RCCL all_gather per outpu
 the timed region; time = max over ranks between barriers.  The frame-per-rank weak-scaling throughput (no data-path
 collective at all) is reported beside it under "weak".  Training: 512 / N rays per rank + one flat gradient all-reduce.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step = wall
+milliseconds of one timed step, dtype, config).  `--dump-outputs DIR` then also writes what the last timed step returned
+(rgb_values, normal_values, ... as DIR/<name>.npy, float32; rays with a non-finite output are listed in the line instead of
+written; a fixed seeded sample of the rays if the frame's outputs exceed 64 MB); the inputs are the same on every run with the
+same arguments.
+
+`--full` adds everything beyond the headline (and the line then also carries):
   roofline     : the dominant kernel's algorithmic FLOP/s (HIP events inside the timed region) vs the dense 16-bit MFMA peak
+  train_iter   : ms per training iteration (--train-steps), with its own roofline
   cpu_baseline : the CPU oracle (fp32 torch restatement of the reference path) timed on this host on a bounded sample
+  weak         : N > 1, the frame-per-rank weak-scaling leg
 """
 import argparse
 import contextlib
@@ -418,14 +426,51 @@ def relaunch_under_torchrun(n):
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.run(cmd).returncode               # a fresh child process: this one only waits for it
+    sys.exit(rc if rc >= 0 else 128 - rc)
+
+
+def dump_outputs(outs, path, limit_bytes=64 << 20, seed=0):
+    """Writes the floating-point outputs of one step as path/<name>.npy (float32; float64 stays float64), every file holding the
+    same rays (rows, in the order of the batch).  Rays with a non-finite output anywhere are left out of every file and listed in
+    the returned record instead: a ray through the centre of the bounding sphere is NaN by the reference's own arithmetic
+    (depth2pts_outside divides 0/0, multiply.py:712-713; its loss filters such rays).  Above `limit_bytes` in all, the same fixed
+    seeded sample of the remaining rays is taken from every output.  Returns what was written."""
+    arrs = {}
+    for k, v in outs.items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            v = v.detach()
+            arrs[k] = (v if v.dtype == torch.float64 else v.float()).cpu().numpy()
+    rows = {a.shape[0] for a in arrs.values()}
+    assert len(rows) == 1, f"outputs differ in their number of rays: {sorted(rows)}"
+    n = rows.pop()
+    finite = np.ones(n, dtype=bool)
+    for a in arrs.values():
+        finite &= np.isfinite(a.reshape(n, -1)).all(axis=1)
+    keep = np.flatnonzero(finite)
+    total = sum(a.nbytes for a in arrs.values()) * len(keep) // max(n, 1)
+    sample = None
+    if total > limit_bytes:
+        k = max(1, (len(keep) * limit_bytes) // total)
+        sample = np.sort(np.random.default_rng(seed).choice(len(keep), size=k, replace=False))
+        keep = keep[sample]
+    arrs = {name: np.ascontiguousarray(a[keep]) for name, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    bad = np.flatnonzero(~finite)
+    return {"dir": path, "arrays": {name: list(a.shape) for name, a in arrs.items()}, "rays": n,
+            "nonfinite_rays": [int(i) for i in bad[:64]], "nonfinite_ray_count": int(len(bad)),
+            "sampled_rays": None if sample is None else int(len(sample)), "sample_seed": None if sample is None else seed}
 
 
 def timed_frames(model, gin, steps, barrier, after=None, frame_fn=None):
     """EXACTLY `steps` forward passes between two barriers; after(out) runs inside the timed region (the all_gather of the
     strong-scaling mode).  frame_fn(gin) replaces model(gin) (person / hybrid modes: a frame is several calls; it returns the
-    frame's (n_shaded, n_sdf_evals) lists itself).  Returns elapsed seconds and the per-step statistics."""
+    frame's (n_shaded, n_sdf_evals) lists itself).  Returns elapsed seconds, the per-step statistics and the last step's outputs."""
     shaded, sdf_evals = [], []
+    out = None
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -440,7 +485,7 @@ def timed_frames(model, gin, steps, barrier, after=None, frame_fn=None):
         if after is not None:
             after(out)
     barrier()
-    return time.perf_counter() - t0, shaded, sdf_evals
+    return time.perf_counter() - t0, shaded, sdf_evals, out
 
 
 def main():
@@ -472,7 +517,16 @@ def main():
                          "the round 1-5 default: ~5 ms per frame less)")
     ap.add_argument("--no-weak", action="store_true", help="N > 1: skip the frame-per-rank weak-scaling leg")
     ap.add_argument("--breakdown", action="store_true", help="print per-phase GPU times to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, finite rays only, at most 64 MB: "
+                         "a fixed seeded sample of the rays beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: roofline and per-phase times, the training leg (--train-steps), "
+                         "the CPU baselines and their parity (--cpu-*), N > 1: the weak-scaling leg.  Off: set up, warm up, time "
+                         "the steps, print the headline line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         relaunch_under_torchrun(args.gpus)            # does not return
@@ -558,7 +612,9 @@ def main():
     else:
         gin, assemble = to_dev(inp), None
 
-    model.profile = True                     # the warm-up also creates the pool of timing events the phases use
+    # HIP-event brackets around the phases of a frame: what the roofline and --breakdown read (--full); a plain run times without them
+    profiled = args.full or args.breakdown
+    model.profile = profiled
     # the frame's inputs are resident before the loop: the setup (SMPL, culls) and its one host sync run on a side stream, so that
     # the host keeps enqueuing ahead of the GPU from frame to frame (Multiply._setup, async_setup)
     model.async_setup = os.environ.get("MP_BENCH_ASYNC_EVAL", "1") == "1"
@@ -572,7 +628,7 @@ def main():
         gather_evs.clear()
     if exchange_evs is not None:
         exchange_evs.clear()
-    elapsed, shaded, sdf_evals = timed_frames(model, gin, args.steps, barrier, assemble, frame_fn)
+    elapsed, shaded, sdf_evals, last = timed_frames(model, gin, args.steps, barrier, assemble, frame_fn)
     model.profile = False
     model.async_setup = False
     per_rank = None
@@ -594,23 +650,27 @@ def main():
             per_rank["exchanges_per_step"] = [float(t[1]) for t in allx]
     elapsed = max_over_ranks(elapsed)
     render_stats = model.last_stats
-    phases = model.phase_times_ms()
+    phases = model.phase_times_ms() if profiled else {}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the caller's view of the last timed step: N > 1 ray mode, the all-gathered image (the outputs every rank keeps)
+        dumped = dump_outputs(image if dist and frame_fn is None else last, args.dump_outputs)
 
     weak = None
-    if dist and not args.no_weak and args.mode == "ray":            # frame-per-rank: rank r renders frame r of the synthetic sequence, no collective
+    if args.full and dist and not args.no_weak and args.mode == "ray":            # frame-per-rank: rank r renders frame r of the synthetic sequence, no collective
         wmodel, winp, _, _ = build_model(args.samples, seed=rank, H=args.res, W=args.res, P=args.persons, tile=args.tile)
         wmodel.convergence_group = GROUP
         wgin = to_dev(winp)
         for _ in range(args.warmup):
             wmodel(wgin)
-        wel, _, _ = timed_frames(wmodel, wgin, args.steps, barrier)
+        wel = timed_frames(wmodel, wgin, args.steps, barrier)[0]
         wel = max_over_ranks(wel)
         weak = {"value": R * args.steps * world / wel, "unit": "rays/s", "ms_per_step": 1e3 * wel / args.steps, "scaling": "weak",
                 "parallelism": f"frame-sharded dp{world}: every rank renders its own frame, no data-path collective"}
         del wmodel, wgin
 
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         from multiply_amd import train as _T
         if _T.TRAIN_PRECISION == "f32":
             train_dtype, train_peak = "f32", 157.3
@@ -651,59 +711,66 @@ def main():
                                       "matrix-bound: its three dominant kernels (k_tf_sdf_fwd / _bwd, k_gemm_tn_b3w: 5.1 of 9.4 ms) move "
                                       "the SDF net's per-point stash at 2.8-4.3 TB/s (profiles/r05_train_pmc_traffic.txt, r06_train_kernels.txt)"}}
 
-    n_shaded = float(sum(int(w.sum()) for s_ in shaded for w in s_)) / args.steps          # per frame (this rank's share)
-    n_sdf = float(sum(int(w[:-1].sum()) for s_ in sdf_evals for w in s_)) / args.steps
-    R_rank = gin["uv"].shape[1] if frame_fn is None else (R + world - 1) // world     # person / hybrid: background is ray-partitioned
-    flops = {"mlp_shade": n_shaded * 4 * M_IMP, "sampler_mlp_sdf": n_sdf * 2 * M_IMP, "mlp_color": n_shaded * 2 * M_REN,
-             "background": R_rank * 32 * 2 * (M_BGIMP + M_BGREN)}
-    dom = max(flops, key=lambda k: phases.get(k, (0, 0.0))[1])
-    n_launch, ms = phases[dom]
-    per_launch_s = ms / 1e3 / max(n_launch, 1)
-    launches_per_frame = n_launch / args.steps
-    achieved = flops[dom] / launches_per_frame / per_launch_s / 1e12
-    if args.breakdown and rank == 0:
-        tot = sum(v[1] for v in phases.values())
-        for k, (n, m) in sorted(phases.items(), key=lambda kv: -kv[1][1]):
-            print(f"  {k:18s} {n:5d} launches {m / args.steps:9.2f} ms/frame {100 * m / tot:5.1f}%", file=sys.stderr)
-        print(f"  shaded points/frame {n_shaded:.0f}  sdf evals/frame {n_sdf:.0f}  hit rays {render_stats['n_hit']}",
-              file=sys.stderr)
+    roofline = None
+    if profiled:
+        n_shaded = float(sum(int(w.sum()) for s_ in shaded for w in s_)) / args.steps          # per frame (this rank's share)
+        n_sdf = float(sum(int(w[:-1].sum()) for s_ in sdf_evals for w in s_)) / args.steps
+        R_rank = gin["uv"].shape[1] if frame_fn is None else (R + world - 1) // world     # person / hybrid: background is ray-partitioned
+        flops = {"mlp_shade": n_shaded * 4 * M_IMP, "sampler_mlp_sdf": n_sdf * 2 * M_IMP, "mlp_color": n_shaded * 2 * M_REN,
+                 "background": R_rank * 32 * 2 * (M_BGIMP + M_BGREN)}
+        dom = max(flops, key=lambda k: phases.get(k, (0, 0.0))[1])
+        n_launch, ms = phases[dom]
+        per_launch_s = ms / 1e3 / max(n_launch, 1)
+        launches_per_frame = n_launch / args.steps
+        achieved = flops[dom] / launches_per_frame / per_launch_s / 1e12
+        if args.breakdown and rank == 0:
+            tot = sum(v[1] for v in phases.values())
+            for k, (n, m) in sorted(phases.items(), key=lambda kv: -kv[1][1]):
+                print(f"  {k:18s} {n:5d} launches {m / args.steps:9.2f} ms/frame {100 * m / tot:5.1f}%", file=sys.stderr)
+            print(f"  shaded points/frame {n_shaded:.0f}  sdf evals/frame {n_sdf:.0f}  hit rays {render_stats['n_hit']}",
+                  file=sys.stderr)
 
-    # HBM traffic of the dominant kernel: rocprofv3 PMC passes of this same command (FETCH_SIZE and WRITE_SIZE in
-    # separate runs, gfx950 half-count correction on reads) are kept under profiles/; the counters cannot be read from
-    # inside the process, so the committed measurement is attached when it was taken on this workload.
-    traffic = None
-    kernels = {"mlp_shade": ["k_mlp_fwdsave", "k_mlp_grad"] if model.shade_mode == "reverse" else ["k_mlp_shade"],
-               "mlp_color": ["k_mlp_color"], "background": ["k_background"], "sampler_mlp_sdf": ["k_mlp_sdf"]}[dom]
-    pmc_file = next((os.path.join(REPO, "profiles", f) for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json")
-                     if os.path.exists(os.path.join(REPO, "profiles", f))), None)
-    traffic_note = None
-    if pmc_file and args.res == 512 and args.samples == 128 and args.persons == 2 and world == 1:
-        with open(pmc_file) as f:
-            pmc = json.load(f)                      # per-dispatch averages of ONE frame (bench.py --steps 1 --warmup 0)
-        # a committed measurement is attached only when it is a measurement of THIS tree on THIS workload (tools/write_profiles.py
-        # records both): the hash of the kernels' sources and the algorithmic work per launch of the profiled run
-        meta = pmc.pop("_meta", None)
-        want_hash = kernel_source_hash()
-        if meta is None:
-            traffic_note, pmc = f"{os.path.basename(pmc_file)} carries no _meta record (tree / workload of the profiled run unknown): not attached", {}
-        elif meta.get("kernel_source_sha16") != want_hash:
-            traffic_note, pmc = (f"{os.path.basename(pmc_file)} was measured on kernel sources {meta.get('kernel_source_sha16')}, this tree "
-                                 f"is {want_hash}: not attached"), {}
-        elif abs(meta.get("algorithmic_flop_per_launch", 0.0) / (flops[dom] / launches_per_frame) - 1.0) > 0.01 or \
-                meta.get("dominant") != dom:
-            traffic_note, pmc = (f"{os.path.basename(pmc_file)}: the profiled run's work per launch ({meta.get('dominant')}, "
-                                 f"{meta.get('algorithmic_flop_per_launch', 0.0):.4g} FLOP) differs from this run's: not attached"), {}
-        rd = wr = 0.0
-        for name, e in pmc.items():
-            if any(k in name for k in kernels):
-                rd += e["hbm_read_bytes_corrected"] * e["dispatches"]
-                wr += e["hbm_write_bytes_uncalibrated"] * e["dispatches"]
-        if rd + wr > 0:
-            traffic = {"bytes_per_launch": (rd + wr) / launches_per_frame, "read": rd / launches_per_frame,
-                       "write": wr / launches_per_frame,
-                       "source": os.path.relpath(pmc_file, REPO).replace(".json", ".txt") +
-                                 " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; Infinity-Cache hits are "
-                                 "counted: an upper bound on HBM bytes)"}
+        # HBM traffic of the dominant kernel: rocprofv3 PMC passes of this same command (FETCH_SIZE and WRITE_SIZE in
+        # separate runs, gfx950 half-count correction on reads) are kept under profiles/; the counters cannot be read from
+        # inside the process, so the committed measurement is attached when it was taken on this workload.
+        traffic = None
+        kernels = {"mlp_shade": ["k_mlp_fwdsave", "k_mlp_grad"] if model.shade_mode == "reverse" else ["k_mlp_shade"],
+                   "mlp_color": ["k_mlp_color"], "background": ["k_background"], "sampler_mlp_sdf": ["k_mlp_sdf"]}[dom]
+        pmc_file = next((os.path.join(REPO, "profiles", f) for f in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json")
+                         if os.path.exists(os.path.join(REPO, "profiles", f))), None)
+        traffic_note = None
+        if pmc_file and args.res == 512 and args.samples == 128 and args.persons == 2 and world == 1:
+            with open(pmc_file) as f:
+                pmc = json.load(f)                      # per-dispatch averages of ONE frame (bench.py --steps 1 --warmup 0)
+            # a committed measurement is attached only when it is a measurement of THIS tree on THIS workload (tools/write_profiles.py
+            # records both): the hash of the kernels' sources and the algorithmic work per launch of the profiled run
+            meta = pmc.pop("_meta", None)
+            want_hash = kernel_source_hash()
+            if meta is None:
+                traffic_note, pmc = f"{os.path.basename(pmc_file)} carries no _meta record (tree / workload of the profiled run unknown): not attached", {}
+            elif meta.get("kernel_source_sha16") != want_hash:
+                traffic_note, pmc = (f"{os.path.basename(pmc_file)} was measured on kernel sources {meta.get('kernel_source_sha16')}, this tree "
+                                     f"is {want_hash}: not attached"), {}
+            elif abs(meta.get("algorithmic_flop_per_launch", 0.0) / (flops[dom] / launches_per_frame) - 1.0) > 0.01 or \
+                    meta.get("dominant") != dom:
+                traffic_note, pmc = (f"{os.path.basename(pmc_file)}: the profiled run's work per launch ({meta.get('dominant')}, "
+                                     f"{meta.get('algorithmic_flop_per_launch', 0.0):.4g} FLOP) differs from this run's: not attached"), {}
+            rd = wr = 0.0
+            for name, e in pmc.items():
+                if any(k in name for k in kernels):
+                    rd += e["hbm_read_bytes_corrected"] * e["dispatches"]
+                    wr += e["hbm_write_bytes_uncalibrated"] * e["dispatches"]
+            if rd + wr > 0:
+                traffic = {"bytes_per_launch": (rd + wr) / launches_per_frame, "read": rd / launches_per_frame,
+                           "write": wr / launches_per_frame,
+                           "source": os.path.relpath(pmc_file, REPO).replace(".json", ".txt") +
+                                     " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; Infinity-Cache hits are "
+                                     "counted: an upper bound on HBM bytes)"}
+        roofline = {"bound": "mfma", "kernel": dom + " = " + " + ".join(kernels), "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_note": traffic_note,
+                    "avg_launch_ms": 1e3 * per_launch_s, "launches_per_step": launches_per_frame,
+                    "algorithmic_flop_per_launch": flops[dom] / launches_per_frame,
+                    "note": "rank 0's share of the frame" if dist else None}
 
     if rank == 0:
         out = {
@@ -730,21 +797,20 @@ def main():
                                        f"hybrid: {world // (args.person_slots or min(args.persons, world))} ray shards x "
                                        f"{args.person_slots or min(args.persons, world)} person slots (teams exchange inside, one all_gather "
                                        f"of the image over the world)")},
-            "roofline": {"bound": "mfma", "kernel": dom + " = " + " + ".join(kernels), "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_note": traffic_note,
-                         "avg_launch_ms": 1e3 * per_launch_s, "launches_per_step": launches_per_frame,
-                         "algorithmic_flop_per_launch": flops[dom] / launches_per_frame,
-                         "note": "rank 0's share of the frame" if dist else None},
-            "phases_ms_per_step": {k: v[1] / args.steps for k, v in phases.items()},
             "lib_source_sha16": __import__("multiply_amd.hip", fromlist=["x"]).lib_source_sha16(),     # content hash of csrc/* + headers + flags the loaded library was built from
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["phases_ms_per_step"] = {k: v[1] / args.steps for k, v in phases.items()}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if per_rank is not None:
             out["per_rank"] = per_rank
         if weak is not None:
             out["weak"] = weak
         if train is not None:
             out["train_iter"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, inp, tables, sc, args.samples, n_rays=args.cpu_rays, budget_s=args.cpu_budget_s)
             if train is not None:
                 train["cpu_baseline"] = train_cpu_baseline(model, to_dev(inp), inp, tables, sc, args.samples,

@@ -1,11 +1,13 @@
-"""bench.py's contract (the driver depends on it): one JSON line with the headline metric, `roofline` and `cpu_baseline`
-at N = 1; `--gpus N` starts N ranks itself (or asserts the launcher's WORLD_SIZE) and reports n_gpus = N with the
-strong-scaling leg of one frame.  Small frames so that the whole file runs in about a minute."""
+"""bench.py's contract (the driver depends on it): one JSON line with the headline metric; a plain run times the steps and
+nothing else, `--dump-outputs` writes the last step's outputs, `--full` adds `roofline`, `train_iter` and `cpu_baseline` at
+N = 1; `--gpus N` starts N ranks itself (or asserts the launcher's WORLD_SIZE) and reports n_gpus = N with the strong-scaling
+leg of one frame.  Small frames so that the whole file runs in about a minute."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests import tolerances as TOL
@@ -25,11 +27,36 @@ def _run(args, env=None):
     return json.loads(lines[0])
 
 
+def test_plain_line_times_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """`bench.py --steps K --warmup W` does only the headline: the line carries the timed steps and nothing of --full; with
+    --dump-outputs it writes the last step's outputs as float32 .npy, the same bits from a second process (same inputs)"""
+    runs = []
+    for n in range(2):
+        out = tmp_path / f"run{n}"
+        d = _run(["--res", "64", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+        runs.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "rays/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 64 * 64 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+    for k in ("roofline", "phases_ms_per_step", "train_iter", "cpu_baseline"):
+        assert k not in d, k
+    a, b = runs
+    assert set(a) == {"rgb_values", "normal_values", "fg_rgb_values", "acc_map", "acc_person_list"}, sorted(a)
+    dm = d["dump_outputs"]
+    n = 64 * 64 - dm["nonfinite_ray_count"]          # rays with a NaN output (0/0 of the reference's background) are listed, not written
+    assert dm["rays"] == 64 * 64 and dm["sampled_rays"] is None and dm["nonfinite_ray_count"] <= 4
+    assert a["rgb_values"].shape == (n, 3) and a["acc_person_list"].shape == (n, 2) and a["acc_map"].shape == (n,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_single_gpu_line_has_roofline_and_cpu_baseline():
     # --cpu-budget-s 0: the wall-time guard of the CPU oracle's render leg at its tightest (a slower host must not turn the headline run
     # into a driver timeout): the sample stops after the minimum number of rays -- here the whole small sample is below the 4 096-ray
     # floor, so it completes and says how many rays it did (round 6: checked in THIS run instead of a second 70 s bench run)
-    d = _run(["--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1", "--cpu-rays", "128",
+    d = _run(["--full", "--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1", "--cpu-rays", "128",
               "--cpu-train-iters", "1", "--cpu-train-rays", "128", "--cpu-budget-s", "0"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -54,7 +81,7 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline():
 def test_gpus_flag_starts_the_ranks_and_reports_strong_scaling():
     """`python bench.py --gpus 2` with no launcher: two ranks (sharing this box's GPU over gloo), n_gpus = 2, the frame's
     convergence groups split between them, the weak-scaling leg beside it"""
-    d = _run(["--gpus", "2", "--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1"],
+    d = _run(["--full", "--gpus", "2", "--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1"],
              env={"MP_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0 and "cpu_baseline" not in d
     assert d["collective_backend"] == "gloo" and d["rccl_ranks_seen"] == 2      # an all_reduce of ones over the data-path backend
@@ -71,7 +98,7 @@ def test_person_and_hybrid_modes_render_the_single_process_frame(mode, ranks, pe
     """BASELINE.json configs[3]'s measurement path: `--mode person` (persons sharded, one all_to_all per person slot and chunk) and
     `--mode hybrid` (person teams x ray shards) render ONE frame per step over the ranks (sharing this box's GPU over gloo); the
     line carries the per-rank frame time, the exchanges' own time and the image all_gather's"""
-    d = _run(["--gpus", str(ranks), "--mode", mode, "--persons", str(persons), "--res", "64", "--steps", "2", "--warmup", "1",
+    d = _run(["--full", "--gpus", str(ranks), "--mode", mode, "--persons", str(persons), "--res", "64", "--steps", "2", "--warmup", "1",
               "--train-steps", "0", "--chunk-rays", "2048"] + (["--person-slots", str(slots)] if slots else []),
              env={"MP_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == ranks and d["value"] > 0 and d["rccl_ranks_seen"] == ranks and d["config"]["persons"] == persons
@@ -83,7 +110,7 @@ def test_person_and_hybrid_modes_render_the_single_process_frame(mode, ranks, pe
 
 def test_single_gpu_line_of_the_four_person_256_sample_workload():
     """BASELINE.json configs[3] on one GPU: `--persons 4 --samples 256` (small frame here), same fields as the headline line"""
-    d = _run(["--persons", "4", "--samples", "256", "--res", "48", "--steps", "1", "--warmup", "1", "--train-steps", "0", "--cpu-rays", "96"])
+    d = _run(["--full", "--persons", "4", "--samples", "256", "--res", "48", "--steps", "1", "--warmup", "1", "--train-steps", "0", "--cpu-rays", "96"])
     assert d["config"]["persons"] == 4 and "4-person" in d["config"]["workload"] and "N_samples=256" in d["config"]["workload"]
     assert 0 < d["roofline"]["frac"] < 1 and d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["parity_rgb_max_abs"] < 5e-4
 
@@ -98,7 +125,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_gpus():
                f"needs one GPU per rank (the gloo variant of the same code path ran in the test above)")
         print("\n[WARNING] " + msg, file=sys.stderr)
         pytest.skip(msg)
-    d = _run(["--gpus", "2", "--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1"])
+    d = _run(["--full", "--gpus", "2", "--res", "64", "--steps", "2", "--warmup", "1", "--train-steps", "2", "--train-warmup", "1"])
     assert d["n_gpus"] == 2 and d["collective_backend"] == "nccl" and d["value"] > 0
     # the gradient buckets are reduced while the backward runs: the "allreduce" phase is only what is left after it returned
     assert d["train_iter"]["rays_per_iter_per_gpu"] == 256 and d["train_iter"]["gpu_ms"]["allreduce"] >= 0

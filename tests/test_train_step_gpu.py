@@ -40,9 +40,59 @@ def _train_setup(H=11, W=11, epoch=301):      # odd size: no ray through the sph
     return model, oracle, inp, gin, gt, loss_fn, train
 
 
-def test_training_sampler_matches_oracle_with_same_draws():
+def _sdf_fn_correctly_rounded(oracle, p, so, cond):
+    """The oracle's no-grad SDF query of the sampler (multiply.py:137-151), evaluated in float64 and rounded to float32: the
+    fp32 value every host agrees on.  The fp32 evaluation itself moves with the host's matrix-product blocking, and an inverse-CDF
+    depth on a flat stretch of a CDF follows the last bit of an sdf (measured on this scene with other draws: the fp32 oracle 3e-2
+    away from the correctly rounded one on single rays) -- the device's depths would be judged against the host, not the oracle."""
+    pp = oracle.persons[p]
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in pp.sd.items()}
+    tfs, verts, skin_w = so["smpl_tfs"].double(), so["smpl_verts"].double(), pp.server.weights.double()
+
+    def fn(pts):
+        x_c, _ = O.deform_inverse(pts.double(), tfs, verts, skin_w)
+        return O.implicit_forward(sd64, pp.imp, x_c, cond.double(), multires=6)[:, 0:1].float()
+    return fn
+
+
+def _sample_with_branch_ties(cfg, dirs, cam, fn, beta, d, monkeypatch):
+    """The oracle's error_bound_sample, and the same depths with the other branch of the reference's `denom < 1e-5` rule
+    (ray_sampler.py:181-182) taken wherever the final inverse CDF's denominator lies within two fp32 ulps of 1.0 from 1e-5.
+    There the branch is decided by the rounding of an fp32 running sum whose values are close to 1 (pdf = weights + 1e-5,
+    normalised: an empty bin of an opaque ray has a denominator of ~0.9987e-5), i.e. by the summation order, and the two branches
+    lie up to a bin apart (interpolate across the bin, or stay at its start).  Returns (z, z_other_branch, iterations, ties)."""
+    calls, inverse_cdf = [], O.inverse_cdf
+
+    def recording(bins, cdf, u):
+        calls.append((bins, cdf, u))
+        return inverse_cdf(bins, cdf, u)
+    monkeypatch.setattr(O, "inverse_cdf", recording)
+    with torch.no_grad():
+        z, it = O.error_bound_sample(cfg, dirs, cam, fn, beta, d)
+    monkeypatch.setattr(O, "inverse_cdf", inverse_cdf)
+    bins, cdf, u = calls[-1]                         # the final draw: u_final over the last grid
+    inds = torch.searchsorted(cdf, u, right=True)
+    below, above = (inds - 1).clamp(min=0), inds.clamp(max=cdf.shape[-1] - 1)
+    cdf_b, cdf_a, bin_b, bin_a = cdf.gather(1, below), cdf.gather(1, above), bins.gather(1, below), bins.gather(1, above)
+    denom = cdf_a - cdf_b
+    one = torch.ones_like(denom)
+    taken = bin_b + (u - cdf_b) / torch.where(denom < 1e-5, one, denom) * (bin_a - bin_b)      # = inverse_cdf
+    other = bin_b + (u - cdf_b) / torch.where(denom < 1e-5, denom, one) * (bin_a - bin_b)
+    tie = (denom - 1e-5).abs() <= 2 * torch.finfo(torch.float32).eps
+    z_other = z.clone()
+    for r, j in tie.nonzero().tolist():
+        k = int((z_other[r] - taken[r, j]).abs().argmin())
+        z_other[r, k] = other[r, j]
+        z_other[r] = z_other[r].sort().values
+    return z, z_other, it, int(tie.sum())
+
+
+def test_training_sampler_matches_oracle_with_same_draws(monkeypatch):
     """ErrorBoundSampler in training mode (stratified t_rand, random u, randperm extras): same draws -> same depths
-    up to the half-precision SDF of the sampler's network queries."""
+    up to the half-precision SDF of the sampler's network queries.  The oracle's sampler runs on correctly rounded fp32 SDF
+    values (_sdf_fn_correctly_rounded); its plain fp32 depths are printed beside them.  Where the reference's inverse CDF sits
+    on its own `denom < 1e-5` branch point (to the rounding of its running sum, _sample_with_branch_ties), a depth is compared
+    with the branch the device took; every other depth, and the mean, against the oracle's single answer."""
     model, oracle, inp, gin, gt, loss_fn, train = _train_setup()
     R = inp["uv"].shape[1]
     hit = [torch.arange(R), torch.arange(R)]
@@ -56,13 +106,20 @@ def test_training_sampler_matches_oracle_with_same_draws():
         cond = inp["smpl_pose"][0, p, 3:] / np.pi
         dirs, cam1 = O.get_camera_rays(inp["uv"][0], inp["pose"][0], inp["intrinsics"][0])
         cam = cam1[None].expand(R, -1)
-        fn = lambda pts: oracle.persons[p].sdf_func(pts, cond, so["smpl_tfs"], so["smpl_verts"], eval_mode=False)[0]
+        fn32 = lambda pts: oracle.persons[p].sdf_func(pts, cond, so["smpl_tfs"], so["smpl_verts"], eval_mode=False)[0]
         d = _cpu(draws["person"][p])
-        z, it_o = O.error_bound_sample(oracle.cfg, dirs, cam, fn, oracle.beta().detach(),
-                                       dict(t_rand=d["t_rand"], u_final=d["u_final"], extra_idx=d["extra_idx"].long()))
-        print("[info] iterations oracle", it_o, "gpu", iters.tolist())
+        d = dict(t_rand=d["t_rand"], u_final=d["u_final"], extra_idx=d["extra_idx"].long())
+        z, z_other, it_o, ties = _sample_with_branch_ties(oracle.cfg, dirs, cam, _sdf_fn_correctly_rounded(oracle, p, so, cond),
+                                                          oracle.beta().detach(), d, monkeypatch)
+        with torch.no_grad():
+            z32, _ = O.error_bound_sample(oracle.cfg, dirs, cam, fn32, oracle.beta().detach(), d)
+        print("[info] iterations oracle", it_o, "gpu", iters.tolist(), f"| inverse-CDF branch ties {ties} of {d['u_final'].numel()} draws")
+        report(f"train z_vals person {p} vs the oracle's plain fp32 sampler (this host; not asserted)", zfinal, z32)
+        assert ties <= max(2, 0.001 * d["u_final"].numel())          # a branch point is a rounding-level coincidence
+        g = zfinal.detach().cpu()
+        want = torch.where((g - z).abs() <= (g - z_other).abs(), z, z_other)       # z itself wherever there is no tie
         assert model.resolved_sampler_sdf_mode(p) == "bf16x3"          # the default: near-fp32 queries (mp_tf_sdf_val)
-        assert TOL.within(report(f"train z_vals person {p}", zfinal, z), TOL.TRAIN_Z_VALS)
+        assert TOL.within(report(f"train z_vals person {p}", zfinal, want), TOL.TRAIN_Z_VALS)
         # the opt-out, the half-precision sampler kernel, same draws: an order of magnitude farther
         model.sampler_sdf_mode = "f16"
         zp, it_p, _ = model._sample_person(cx, n, p, draws["person"][p])

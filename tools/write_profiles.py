@@ -14,7 +14,7 @@ src, dst = os.path.join(root, "gpurun_out", "prof_" + tag), os.path.join(root, "
 kt = open(os.path.join(src, "kernel_trace.txt")).read()
 bench = json.loads([l for l in open(os.path.join(src, "bench_under_trace.json")) if l.startswith("{")][0])
 with open(os.path.join(dst, tag + "_kernel_trace.txt"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace -- python bench.py --no-cpu-baseline   (MI355X, round {tag[1:]}; tools/profile_round.sh + "
+    f.write(f"# rocprofv3 --kernel-trace -- python bench.py --full --no-cpu-baseline   (MI355X, round {tag[1:]}; tools/profile_round.sh + "
             f"tools/rocpd_summary.py)\n# 2 warm-up + 5 timed frames of the 512x512 2-person scene (N_samples 128), then 2 + 10 training "
             f"iterations of 512 rays.\n# the same run printed: {bench['value'] / 1e6:.3f} M rays/s, {bench['ms_per_step']:.1f} ms/frame, "
             f"roofline.frac {bench['roofline']['frac']:.3f} ({bench['roofline']['kernel']}, avg launch "
@@ -33,11 +33,11 @@ one = [l for l in open(os.path.join(src, "bench_one_frame.json")) if l.startswit
 one = json.loads(one[0]) if one else bench
 pmc["_meta"] = {"kernel_source_sha16": _bench.kernel_source_hash(), "dominant": one["roofline"]["kernel"].split(" = ")[0],
                 "algorithmic_flop_per_launch": one["roofline"]["algorithmic_flop_per_launch"],
-                "launches_per_step": one["roofline"]["launches_per_step"], "command": "bench.py --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline"}
+                "launches_per_step": one["roofline"]["launches_per_step"], "command": "bench.py --full --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline"}
 json.dump(pmc, open(os.path.join(dst, tag + "_pmc_traffic.json"), "w"))
 with open(os.path.join(dst, tag + "_pmc_traffic.txt"), "w") as f:
     f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, each with --kernel-trace only) of\n"
-            "#   python bench.py --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline      (MI355X: ONE frame)\n"
+            "#   python bench.py --full --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline      (MI355X: ONE frame)\n"
             "# read = 2 x 1024 x FETCH_SIZE (gfx950 half-count correction, MI355X_MICROARCH.md HBM section); write = 1024 x WRITE_SIZE "
             "(uncalibrated)\n# per-dispatch averages; k_mlp_fwdsave / k_mlp_grad run once per 2M-point worklist segment (n includes the "
             "empty ones).\n# Infinity-Cache hits are counted by these counters: every figure is an UPPER bound on HBM bytes.\n")
@@ -48,7 +48,7 @@ txt = open(os.path.join(src, "pmc_sq.txt")).read()
 blocks = re.split(r"^== ", txt, flags=re.M)[1:]
 with open(os.path.join(dst, tag + "_pmc_sq.txt"), "w") as f:
     f.write("# rocprofv3 --pmc <SQ counters> (two passes of 8 counters, --kernel-trace only) of ONE frame:\n"
-            "#   python bench.py --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline        (MI355X; tools/profile_round.sh)\n"
+            "#   python bench.py --full --steps 1 --warmup 0 --train-steps 0 --no-cpu-baseline        (MI355X; tools/profile_round.sh)\n"
             "# per-dispatch averages (fwdsave / grad: over all segment dispatches incl. the empty ones -- ratios are unaffected).\n"
             "# derived:  MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs)   [matrix-pipe utilisation; GRBM_GUI_ACTIVE is\n"
             "#           summed over the 8 XCDs: /8 x clock = the dispatch time of the kernel trace; BUSY = 16 cycles x MFMA count]\n"
