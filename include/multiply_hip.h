@@ -138,6 +138,19 @@ int mp_background(const MpNet* net_imp, const void* wpack_imp, const float* bias
 int mp_smpl_pose(const float* v_template, const float* shapedirs, const float* posedirs, const float* j_regressor,
                  const float* lbs_weights, const int* parents, const float* params, const float* tfs_c_inv,
                  float* verts, float* tfs, float* joints, float* work, void* stream);
+/* Adjoint of the posed vertices verts = s (sum_j w_j A_j [v_posed; 1] + transl), v_posed = v_shaped + posedirs^T pf
+ * (lbs.py:196-221, smpl.py:77-78) for the parameters `params` of an mp_smpl_pose call whose work buffer is `work`
+ * (v_shaped, A and pf are read from it; v_posed is recomputed, posedirs is read once).  dverts [V][3].
+ * Two launches, no atomics: per-workgroup partials of 32 vertices each into scratch [MP_SMPL_VBWD_SCRATCH], then a
+ * finishing pass that sums them in a fixed order (bit-identical results on every call).  Output dlbs [MP_SMPL_DLBS]:
+ *   [0, 384)   dA [24][16]: adjoint of the rest-relative transforms A (work layout, unscaled; row 3 = 0)
+ *   [384, 591) dpf [207]:   adjoint of the pose feature (R_j - I, j >= 1)
+ *   [591, 677) dparams [86]: the direct terms -- d scale, d transl, 0 for thetas, d betas through the shape blend shapes
+ * mp_smpl_pose_bwd_lbs turns dA / dpf / dparams into the gradient of the 86 parameters. */
+#define MP_SMPL_VBWD_SCRATCH (216 * 512)
+#define MP_SMPL_DLBS (24 * 16 + 207 + 86)
+int mp_smpl_verts_bwd(const float* posedirs, const float* shapedirs, const float* lbs_weights, const float* params,
+                      const float* work, const float* dverts, float* scratch, float* dlbs, void* stream);
 
 /* Nearest-neighbour acceleration structure over one vertex set (exact K=1 search, replaces
  * pytorch3d.ops.knn_points, deformer.py:39): vertices gathered in cluster order + bounding spheres.
@@ -398,6 +411,17 @@ int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const f
                    const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, void* stream);
 int mp_smpl_pose_bwd(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
                      const float* j_shapedirs, const float* dtfs, float* dparams, void* stream);
+/*   mp_smpl_pose_bwd_lbs: the same chain adjoint with every upstream of SMPLServer.forward: dtfs [24][16] (smpl_tfs),
+ *                     dA [24][16] (the rest-relative transforms, mp_smpl_verts_bwd), djoints [24][3] (smpl_jnts),
+ *                     dpf [207] (the pose feature, mp_smpl_verts_bwd), dparams_in [86] (added to the result; must not alias
+ *                     dparams); any of them NULL = zero.  mp_smpl_pose_bwd is the case dA = djoints = dpf = dparams_in = NULL. */
+int mp_smpl_pose_bwd_lbs(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
+                         const float* j_shapedirs, const float* dtfs, const float* dA, const float* djoints,
+                         const float* dpf, const float* dparams_in, float* dparams, void* stream);
+/* adjoint of x_c = I_nn (x - c_nn) w.r.t. the explicit points x of mp_warp_inverse, gathered onto the vertices they were
+ * drawn from: dverts [n_verts][3] += sum over {s : idx[s] == v} of jinv_s^T dxc_s (jinv [n][9] = I_nn row-major, as
+ * mp_warp_jacobian writes it).  One thread per vertex, samples in ascending order: deterministic, no atomics. */
+int mp_tr_gather_bwd(const int* idx, int n, const float* jinv, const float* dxc, int n_verts, float* dverts, void* stream);
 /* reverse-over-reverse SDF net (train.py ImplicitTrainRev): V = sigma'(Z) (.) U (U NULL: the row vector wrow) ;
  * its adjoint (dU, d sigma') ; dZ = sigma' dX scale + sigma'' dS ; Fourier-feature Jacobian products (3-D points). */
 int mp_tr_sigmul(const float* Z, int ldz, long long rows, int C, const float* U, int ldu, const float* wrow, float scale,

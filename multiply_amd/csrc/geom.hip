@@ -192,6 +192,115 @@ __global__ __launch_bounds__(256) void k_smpl_verts(const float* __restrict__ po
     }
 }
 
+// ---- adjoint of the posed vertices (mp_smpl_verts_bwd).  g_i = dverts_i, T_i = sum_j w_ij A_j, q_i = [p_i; 1]:
+//   d scale = sum_i g_i . (T_i q_i + t) ; d transl = s sum_i g_i ; dA_j = s sum_i w_ij g_i (x) q_i ;
+//   dp_i = s T_i[:3,:3]^T g_i -> dpf = posedirs dp, d betas = shapedirs^T dp.
+// dp does not depend on p, so one pass over a tile of posedirs (207 rows x the 96 columns of 32 vertices, staged in LDS)
+// gives both p (column sums) and the tile's share of dpf (row sums).  Each workgroup writes its 509 partial sums to its own
+// scratch row; k_smpl_verts_bwd_finish adds the rows in a fixed order.
+constexpr int VB = 32, VB_BLOCKS = (V + VB - 1) / VB, VB_COLS = 3 * VB, VB_LD = VB_COLS + 1, VB_ROW = 512;
+constexpr int VB_PF = NJ * 12, VB_DS = VB_PF + 207, VB_DT = VB_DS + 1, VB_DB = VB_DT + 3, VB_OUT = VB_DB + 10;
+static_assert(VB_BLOCKS * VB_ROW == MP_SMPL_VBWD_SCRATCH && VB_OUT <= VB_ROW && VB_COLS % 2 == 0 && (3 * V) % 2 == 0,
+              "scratch layout of mp_smpl_verts_bwd");
+
+__global__ __launch_bounds__(256) void k_smpl_verts_bwd(const float* __restrict__ posedirs,
+                                                        const float* __restrict__ shapedirs,
+                                                        const float* __restrict__ lbs_weights,
+                                                        const float* __restrict__ params, const float* __restrict__ work,
+                                                        const float* __restrict__ dverts, float* __restrict__ partial) {
+    __shared__ float P[207 * VB_LD];
+    __shared__ float A[NJ * 12], pf[207], W[VB * NJ], gs[VB_COLS], dp[VB_COLS], pv[VB_COLS], dsv[VB];
+    const int t = threadIdx.x, v0 = blockIdx.x * VB, nv = min(VB, V - v0);
+    float* out = partial + (size_t)blockIdx.x * VB_ROW;
+    for (int i = t; i < NJ * 12; i += 256) A[i] = work[W_A + 16 * (i / 12) + i % 12];
+    for (int i = t; i < 207; i += 256) pf[i] = work[W_PF + i];
+    for (int i = t; i < VB * NJ; i += 256) W[i] = i < nv * NJ ? lbs_weights[(size_t)v0 * NJ + i] : 0.f;
+    for (int e = t; e < 207 * (VB_COLS / 2); e += 256) {       // the tile, 8-byte loads (3V and the tile's first column are even)
+        const int r = e / (VB_COLS / 2), c = 2 * (e % (VB_COLS / 2)), gc = 3 * v0 + c;
+        float2 x = make_float2(0.f, 0.f);
+        if (gc < 3 * V) x = *reinterpret_cast<const float2*>(posedirs + (size_t)r * (3 * V) + gc);
+        P[r * VB_LD + c] = x.x;
+        P[r * VB_LD + c + 1] = x.y;
+    }
+    __syncthreads();
+    const float scale = params[0];
+    float T[12], g[3] = {0.f, 0.f, 0.f};
+    if (t < VB) {
+        for (int i = 0; i < 12; ++i) T[i] = 0.f;
+        for (int j = 0; j < NJ; ++j) {                          // the forward's blend, same order (k_smpl_verts)
+            const float w = W[t * NJ + j];
+            for (int i = 0; i < 12; ++i) T[i] += w * A[12 * j + i];
+        }
+        if (t < nv && dverts)
+            for (int a = 0; a < 3; ++a) g[a] = dverts[3 * (size_t)(v0 + t) + a];
+        for (int k = 0; k < 3; ++k) {
+            dp[3 * t + k] = scale * (T[k] * g[0] + T[4 + k] * g[1] + T[8 + k] * g[2]);
+            gs[3 * t + k] = scale * g[k];
+        }
+    }
+    __syncthreads();
+    if (t < VB_COLS) {                                          // p = v_shaped + posedirs^T pf  (lbs.py:201-202)
+        float acc = 0.f;
+        for (int r = 0; r < 207; ++r) acc += pf[r] * P[r * VB_LD + t];
+        pv[t] = acc + (t < 3 * nv ? work[W_VS + 3 * v0 + t] : 0.f);
+    } else if (t >= 128) {                                      // the tile's share of dpf = posedirs dp
+        for (int r = t - 128; r < 207; r += 128) {
+            float acc = 0.f;
+            for (int c = 0; c < VB_COLS; ++c) acc += P[r * VB_LD + c] * dp[c];
+            out[VB_PF + r] = acc;
+        }
+    }
+    __syncthreads();
+    if (t < VB) {
+        float s = 0.f;
+        for (int a = 0; a < 3; ++a)
+            s += g[a] * (T[4 * a] * pv[3 * t] + T[4 * a + 1] * pv[3 * t + 1] + T[4 * a + 2] * pv[3 * t + 2] + T[4 * a + 3] +
+                         params[1 + a]);
+        dsv[t] = s;
+    }
+    __syncthreads();
+    for (int e = t; e < NJ * 12 + 14; e += 256) {
+        float acc = 0.f;
+        if (e < NJ * 12) {                                      // dA_j[a][b] over the tile's vertices
+            const int j = e / 12, a = (e % 12) / 4, b = e % 4;
+            for (int i = 0; i < VB; ++i) acc += W[i * NJ + j] * gs[3 * i + a] * (b < 3 ? pv[3 * i + b] : 1.f);
+            out[e] = acc;
+        } else if (e == NJ * 12) {
+            for (int i = 0; i < VB; ++i) acc += dsv[i];
+            out[VB_DS] = acc;
+        } else if (e < NJ * 12 + 4) {
+            const int a = e - NJ * 12 - 1;
+            for (int i = 0; i < VB; ++i) acc += gs[3 * i + a];
+            out[VB_DT + a] = acc;
+        } else {                                                // d betas through v_shaped (lbs.py:252-273)
+            const int l = e - NJ * 12 - 4;
+            for (int c = 0; c < 3 * nv; ++c) acc += shapedirs[(size_t)(3 * v0 + c) * 10 + l] * dp[c];
+            out[VB_DB + l] = acc;
+        }
+    }
+}
+
+// sums the VB_BLOCKS partial rows (wave w: rows w, w + 4, ...; then the four waves in order) -> dlbs (MP_SMPL_DLBS layout)
+__global__ __launch_bounds__(256) void k_smpl_verts_bwd_finish(const float* __restrict__ partial, float* __restrict__ dlbs) {
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, o = blockIdx.x * 64 + lane;
+    float acc = 0.f;
+    if (o < VB_OUT)
+        for (int r = wave; r < VB_BLOCKS; r += 4) acc += partial[(size_t)r * VB_ROW + o];
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave != 0) return;
+    const float s = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+    if (o < NJ * 12) {
+        const int j = o / 12, r = o % 12;
+        dlbs[16 * j + r] = s;
+        if (r < 4) dlbs[16 * j + 12 + r] = 0.f;
+    } else if (o < VB_DS) dlbs[NJ * 16 + o - VB_PF] = s;
+    else if (o < VB_DB) dlbs[NJ * 16 + 207 + o - VB_DS] = s;           // d scale, d transl
+    else if (o < VB_OUT) dlbs[NJ * 16 + 207 + 76 + o - VB_DB] = s;     // d betas
+    if (o < 72) dlbs[NJ * 16 + 207 + 4 + o] = 0.f;                       // thetas: through dA / dpf only
+}
+
 // ------------------------------------------------------------------------------------------------ KNN structure
 // Blocks NC .. NC + NCC - 1 (round 6): the bounding sphere of the PAIR of clusters (2 cc, 2 cc + 1) -- consecutive kd leaves, siblings --
 // as cbound[NC + cc].  The training searches (every sample of a ray needs its exact neighbour however far away it is, so many
@@ -1157,6 +1266,15 @@ extern "C" int mp_smpl_pose(const float* v_template, const float* shapedirs, con
     hipLaunchKernelGGL(k_smpl_joints, dim3(NJ), dim3(256), 0, st, j_regressor, work);
     hipLaunchKernelGGL(k_smpl_chain, dim3(1), dim3(64), 0, st, parents, params, tfs_c_inv, work, tfs, joints);
     hipLaunchKernelGGL(k_smpl_verts, dim3((V + 255) / 256), dim3(256), 0, st, posedirs, lbs_weights, params, work, verts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_smpl_verts_bwd(const float* posedirs, const float* shapedirs, const float* lbs_weights, const float* params,
+                                 const float* work, const float* dverts, float* scratch, float* dlbs, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_smpl_verts_bwd, dim3(VB_BLOCKS), dim3(256), 0, st, posedirs, shapedirs, lbs_weights, params, work,
+                       dverts, scratch);
+    hipLaunchKernelGGL(k_smpl_verts_bwd_finish, dim3((VB_OUT + 63) / 64), dim3(256), 0, st, scratch, dlbs);
     return (int)hipGetLastError();
 }
 

@@ -678,10 +678,14 @@ __global__ __launch_bounds__(256) void k_warp_bwd(const float* __restrict__ xc, 
 
 // ---- adjoint of SMPLServer.forward's bone transforms (smpl.py:50-94, lbs.py:276-377) w.r.t. the 86 SMPL parameters
 //   [scale, transl(3), thetas(72), betas(10)];  one thread: 24 joints, a few hundred flops each.
-//   Only the transforms are differentiated: the posed vertices enter the hot path through a nearest-vertex index.
+//   Upstreams (each optional): dtfs (smpl_tfs), dA_ext (the rest-relative transforms A, from the posed vertices'
+//   adjoint), djoints (smpl_jnts), dpf (the pose feature R_j - I, j >= 1), dparams_in (added at the end).
+//   With only dtfs this is mp_smpl_pose_bwd: the hot path's samples reach the pose through the transforms alone.
 __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __restrict__ params,
                                 const float* __restrict__ tfs_c_inv, const float* __restrict__ rest_joints,
                                 const float* __restrict__ j_shapedirs, const float* __restrict__ dtfs,
+                                const float* __restrict__ dA_ext, const float* __restrict__ djoints,
+                                const float* __restrict__ dpf, const float* __restrict__ dparams_in,
                                 float* __restrict__ dparams) {
     constexpr int NJ = 24;
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -729,8 +733,8 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 4; ++b) {
                 float v = 0.f;
-                if (tfs_c_inv) for (int k = 0; k < 4; ++k) v += dtfs[16 * j + 4 * a + k] * tfs_c_inv[16 * j + 4 * b + k];
-                else v = dtfs[16 * j + 4 * a + b];
+                if (dtfs && tfs_c_inv) for (int k = 0; k < 4; ++k) v += dtfs[16 * j + 4 * a + k] * tfs_c_inv[16 * j + 4 * b + k];
+                else if (dtfs) v = dtfs[16 * j + 4 * a + b];
                 dtf[4 * a + b] = v;
             }
         // A = G with translation column  A[a][3] = G[a][3] - sum_k G[a][k] J_j[k];  tf = scale A, tf[a][3] += scale transl[a]
@@ -742,6 +746,8 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
             dscale += dtf[4 * a + 3] * (A3 + transl[a]);
             dtr[a] += scale * dtf[4 * a + 3];
             for (int b = 0; b < 4; ++b) dA[4 * a + b] = scale * dtf[4 * a + b];
+            if (dA_ext)
+                for (int b = 0; b < 4; ++b) dA[4 * a + b] += dA_ext[16 * j + 4 * a + b];
         }
         for (int a = 0; a < 3; ++a) {
             for (int k = 0; k < 3; ++k) {
@@ -750,6 +756,13 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
             }
             dG[j][4 * a + 3] = dA[4 * a + 3];
         }
+        if (djoints)      // joints_j = scale G_j[:3,3] + scale transl  (smpl.py:79-84)
+            for (int a = 0; a < 3; ++a) {
+                const float dj = djoints[3 * j + a];
+                dscale += dj * (G[j][4 * a + 3] + transl[a]);
+                dtr[a] += scale * dj;
+                dG[j][4 * a + 3] += scale * dj;
+            }
     }
     for (int j = NJ - 1; j >= 1; --j) {   // G_j = G_p [R_j | rel_j]
         const int p = parents[j];
@@ -778,6 +791,9 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
         for (int b = 0; b < 3; ++b) dR[0][3 * a + b] = dG[0][4 * a + b];
         dJ[0][a] += dG[0][4 * a + 3];
     }
+    if (dpf)              // pose_feature = (R_j - I).flatten, j >= 1 (lbs.py:199)
+        for (int j = 1; j < NJ; ++j)
+            for (int e = 0; e < 9; ++e) dR[j][e] += dpf[9 * (j - 1) + e];
     for (int i = 0; i < 86; ++i) dparams[i] = 0.f;
     dparams[0] = dscale;
     for (int a = 0; a < 3; ++a) dparams[1 + a] = dtr[a];
@@ -819,6 +835,29 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
                 for (int k = 0; k < 3; ++k) v += dJ[j][k] * j_shapedirs[(3 * j + k) * 10 + l];
             dparams[76 + l] = v;
         }
+    if (dparams_in)
+        for (int i = 0; i < 86; ++i) dparams[i] += dparams_in[i];
+}
+
+
+// ---- adjoint of x_c = I_nn (x - c_nn) w.r.t. explicit points x = verts[idx[s]] (the smpl_surface regulariser under pose
+// optimisation): dverts[v] += sum_{s : idx[s] == v} I_s^T dxc_s, samples in ascending order (idx is drawn with replacement)
+__global__ void k_gather_bwd(const int* __restrict__ idx, int n, const float* __restrict__ jinv, const float* __restrict__ dxc,
+                             int n_verts, float* __restrict__ dverts) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_verts) return;
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+    for (int s = 0; s < n; ++s) {
+        if (idx[s] != v) continue;
+        const float* I = jinv + 9 * (size_t)s;
+        const float g0 = dxc[3 * (size_t)s], g1 = dxc[3 * (size_t)s + 1], g2 = dxc[3 * (size_t)s + 2];
+        d0 += I[0] * g0 + I[3] * g1 + I[6] * g2;
+        d1 += I[1] * g0 + I[4] * g1 + I[7] * g2;
+        d2 += I[2] * g0 + I[5] * g1 + I[8] * g2;
+    }
+    dverts[3 * (size_t)v] += d0;
+    dverts[3 * (size_t)v + 1] += d1;
+    dverts[3 * (size_t)v + 2] += d2;
 }
 
 
@@ -1121,7 +1160,19 @@ int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const f
 int mp_smpl_pose_bwd(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
                      const float* j_shapedirs, const float* dtfs, float* dparams, void* stream) {
     hipLaunchKernelGGL(k_smpl_pose_bwd, dim3(1), dim3(64), 0, ST, parents, params, tfs_c_inv, rest_joints, j_shapedirs, dtfs,
-                       dparams);
+                       nullptr, nullptr, nullptr, nullptr, dparams);
+    return (int)hipGetLastError();
+}
+int mp_smpl_pose_bwd_lbs(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
+                         const float* j_shapedirs, const float* dtfs, const float* dA, const float* djoints,
+                         const float* dpf, const float* dparams_in, float* dparams, void* stream) {
+    hipLaunchKernelGGL(k_smpl_pose_bwd, dim3(1), dim3(64), 0, ST, parents, params, tfs_c_inv, rest_joints, j_shapedirs, dtfs,
+                       dA, djoints, dpf, dparams_in, dparams);
+    return (int)hipGetLastError();
+}
+int mp_tr_gather_bwd(const int* idx, int n, const float* jinv, const float* dxc, int n_verts, float* dverts, void* stream) {
+    if (n_verts <= 0) return 0;
+    hipLaunchKernelGGL(k_gather_bwd, grid1(n_verts), dim3(TB), 0, ST, idx, n, jinv, dxc, n_verts, dverts);
     return (int)hipGetLastError();
 }
 int mp_tr_sigmul(const float* Z, int ldz, long long rows, int C, const float* U, int ldu, const float* wrow, float scale,

@@ -6,7 +6,7 @@ dumps, tqdm loops and trainer state left to the caller.
 Device work: canonical mesh extraction (mesh.py / csrc/mise.hip), skinning weights of the mesh vertices (mp_query_weights),
 the z-buffers (csrc/raster.hip), the inside test of the interpenetration term (mp_mesh_signed_distance: the sign of the
 signed distance stands in for kaolin.ops.mesh.check_sign).  Everything after those is small torch arithmetic on (H, W)
-maps that autograd differentiates: depth -> vertices -> blended bone transforms -> SMPLServer (_PoseTfs) -> pose.
+maps that autograd differentiates: depth -> vertices -> blended bone transforms -> SMPLServer (_PoseLBS) -> pose.
 """
 import numpy as np
 import torch

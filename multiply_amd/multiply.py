@@ -44,6 +44,9 @@ class Multiply(nn.Module):
         self.smpl_surface_weight = opt.loss.get("smpl_surface_weight", 0)
         self.zero_pose_weight = opt.loss.get("zero_pose_weight", 0)
         self.smpl_vertex_part = None
+        # opt-in: the smpl_surface term back-propagates into smpl_pose / smpl_trans / smpl_shape when they are optimised (the
+        # posed vertices' adjoint, train.TrainGraph._regularisers_*); off, that combination still raises
+        self.smpl_surface_pose_grad = os.environ.get("MP_SMPL_SURFACE_POSE_GRAD", "0") == "1"
         if self.smpl_surface_weight > 0:      # multiply.py:112-113 (the reference's asset ./outputs/smpl_vert_segmentation.json)
             import json
             seg = os.path.abspath(opt.get("smpl_vert_segmentation_path", "./outputs/smpl_vert_segmentation.json"))

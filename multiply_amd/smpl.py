@@ -5,7 +5,8 @@ of the SMPL class it wraps (code/lib/smpl/body_models.py:60-365) for what the ho
 `verts_c`, `joints_c`, `tfs_c_inv`, `faces`, `smpl.faces`, `bone_parents`, `param_canonical`, and
 forward(scale, transl, thetas, betas, absolute=False) -> {'smpl_verts','smpl_tfs','smpl_jnts','smpl_all_jnts',
 'smpl_weights'}; the SMPL sub-module's parameters / buffers keep the reference's state-dict names.
-The arithmetic (blend shapes, Rodrigues, kinematic chain, LBS) runs in csrc/geom.hip (mp_smpl_pose).
+The arithmetic (blend shapes, Rodrigues, kinematic chain, LBS) runs in csrc/geom.hip (mp_smpl_pose), its adjoint in
+csrc/geom.hip (mp_smpl_verts_bwd) and csrc/train.hip (mp_smpl_pose_bwd_lbs).
 """
 import os
 import pickle
@@ -150,25 +151,29 @@ class _SMPLModule(nn.Module):
                                   f"(gender / betas_path / smpl_tables); construct the model with the checkpoint's body model")
 
 
-class _PoseTfs(torch.autograd.Function):
-    """smpl_tfs (24,4,4) of the 86 parameters with the hand-written adjoint of csrc/geom.hip (mp_smpl_pose_bwd)"""
+class _PoseLBS(torch.autograd.Function):
+    """smpl_verts (V,3), smpl_jnts (24,3), smpl_all_jnts (29,3) and smpl_tfs (24,4,4) of the 86 parameters: ONE node over the
+    forward launches of mp_smpl_pose, whose backward takes any subset of the four upstream gradients (SMPLServer.pose_backward:
+    csrc/geom.hip mp_smpl_verts_bwd, csrc/train.hip mp_smpl_pose_bwd_lbs).  smpl_all_jnts = the joints + the face-keypoint
+    vertices, so its gradient folds into d joints and d verts."""
 
     @staticmethod
-    def forward(ctx, server, p, verts, jnts):
+    def forward(ctx, server, p):
         prm = p.detach().contiguous()
-        tfs = torch.empty(NUM_JOINTS, 4, 4, dtype=torch.float32, device=prm.device)
+        dev = prm.device
+        verts = torch.empty(NUM_VERTS, 3, dtype=torch.float32, device=dev)
+        jnts = torch.empty(NUM_JOINTS, 3, dtype=torch.float32, device=dev)
+        tfs = torch.empty(NUM_JOINTS, 4, 4, dtype=torch.float32, device=dev)
         server.pose_into(prm, verts, tfs, jnts)
-        ctx.server, ctx.prm, ctx.rest = server, prm, server.rest_joints().contiguous()
-        return tfs
+        all_jnts = torch.cat([jnts, verts[server.smpl.vertex_joint_selector.extra_joints_idxs]], 0)
+        # v_shaped / J / A / pose feature of THIS call (the server's work buffer is reused by the next pose_into)
+        ctx.server, ctx.prm, ctx.work = server, prm, server._work.clone()
+        ctx.set_materialize_grads(False)
+        return verts, jnts, all_jnts, tfs
 
     @staticmethod
-    def backward(ctx, dtfs):
-        sv, t = ctx.server, ctx.server.tables
-        dprm = torch.empty(86, dtype=torch.float32, device=ctx.prm.device)
-        hip.check(hip.lib().mp_smpl_pose_bwd(hip.ptr(t.parents), hip.ptr(ctx.prm), hip.ptr(sv.tfs_c_inv), hip.ptr(ctx.rest),
-                                             hip.ptr(t.j_shapedirs), hip.ptr(dtfs.reshape(24, 16).float().contiguous()),
-                                             hip.ptr(dprm), hip.stream()), "mp_smpl_pose_bwd")
-        return None, dprm, None, None
+    def backward(ctx, dverts, djnts, dall, dtfs):
+        return None, ctx.server.pose_backward(ctx.prm, ctx.work, dverts=dverts, djoints=djnts, dall_joints=dall, dtfs=dtfs)
 
 
 class SMPLServer(nn.Module):
@@ -200,35 +205,71 @@ class SMPLServer(nn.Module):
         self.joints_c = out["smpl_jnts"]
         self.tfs_c_inv = torch.linalg.inv(out["smpl_tfs"].squeeze(0)).contiguous()   # init-time only (smpl.py:47)
 
-    def pose_into(self, params86, verts, tfs, joints, absolute=False):
-        """raw launch: params86 (86,) device -> preallocated verts (V,3), tfs (24,4,4), joints (24,3)"""
+    def pose_into(self, params86, verts, tfs, joints, absolute=False, work=None):
+        """raw launch: params86 (86,) device -> preallocated verts (V,3), tfs (24,4,4), joints (24,3); `work` (3V + 1024
+        floats) defaults to the server's own buffer"""
         t = self.tables
         hip.check(hip.lib().mp_smpl_pose(hip.ptr(t.v_template), hip.ptr(t.shapedirs), hip.ptr(t.posedirs),
                                          hip.ptr(t.j_regressor), hip.ptr(t.lbs_weights), hip.ptr(t.parents),
                                          hip.ptr(params86), None if absolute else hip.ptr(self.tfs_c_inv), hip.ptr(verts),
-                                         hip.ptr(tfs), hip.ptr(joints), hip.ptr(self._work), hip.stream()),
-                  "mp_smpl_pose")
+                                         hip.ptr(tfs), hip.ptr(joints), hip.ptr(self._work if work is None else work),
+                                         hip.stream()), "mp_smpl_pose")
+
+    def pose_backward(self, params86, work=None, dverts=None, djoints=None, dall_joints=None, dtfs=None):
+        """Adjoint of forward(absolute=False) -> d params (86,) = [scale, transl 3, thetas 72, betas 10].  Upstreams (any may
+        be None): dverts (V,3), djoints (24,3), dall_joints (29,3), dtfs (24,4,4).  `work`: the work buffer of the pose_into
+        call that produced the outputs; None = pose again into a private buffer (same launches, same values).  Deterministic:
+        the same inputs give bit-identical gradients."""
+        t, dev = self.tables, params86.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        prm = params86.detach().float().contiguous()
+        if work is None:
+            work = torch.empty_like(self._work)
+            self.pose_into(prm, torch.empty(NUM_VERTS, 3, **f32), torch.empty(NUM_JOINTS, 4, 4, **f32),
+                           torch.empty(NUM_JOINTS, 3, **f32), work=work)
+        flat = lambda g, n: None if g is None else g.detach().reshape(n, -1).float().contiguous()
+        dverts, djoints, dall_joints, dtfs = flat(dverts, NUM_VERTS), flat(djoints, NUM_JOINTS), flat(dall_joints, NUM_JOINTS + len(FACE_KEYPOINT_VERTS)), flat(dtfs, NUM_JOINTS)
+        if dall_joints is not None:         # smpl_all_jnts = [joints; verts[face keypoints]] (five distinct vertices)
+            djoints = dall_joints[:NUM_JOINTS] if djoints is None else djoints + dall_joints[:NUM_JOINTS]
+            dverts = torch.zeros(NUM_VERTS, 3, **f32) if dverts is None else dverts.clone()
+            dverts[self.smpl.vertex_joint_selector.extra_joints_idxs] += dall_joints[NUM_JOINTS:]
+        dA = dpf = din = None
+        if dverts is not None:
+            dlbs = torch.empty(hip.SMPL_DLBS, **f32)
+            scratch = torch.empty(hip.SMPL_VBWD_SCRATCH, **f32)
+            hip.check(hip.lib().mp_smpl_verts_bwd(hip.ptr(t.posedirs), hip.ptr(t.shapedirs), hip.ptr(t.lbs_weights),
+                                                  hip.ptr(prm), hip.ptr(work), hip.ptr(dverts), hip.ptr(scratch),
+                                                  hip.ptr(dlbs), hip.stream()), "mp_smpl_verts_bwd")
+            dA, dpf, din = dlbs[:NUM_JOINTS * 16], dlbs[NUM_JOINTS * 16:NUM_JOINTS * 16 + 207], dlbs[NUM_JOINTS * 16 + 207:]
+        dprm = torch.empty(86, **f32)
+        rest = work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS]          # csrc/geom.hip W_J
+        hip.check(hip.lib().mp_smpl_pose_bwd_lbs(hip.ptr(t.parents), hip.ptr(prm), hip.ptr(self.tfs_c_inv), hip.ptr(rest),
+                                                 hip.ptr(t.j_shapedirs), hip.ptr(dtfs), hip.ptr(dA), hip.ptr(djoints),
+                                                 hip.ptr(dpf), hip.ptr(din), hip.ptr(dprm), hip.stream()),
+                  "mp_smpl_pose_bwd_lbs")
+        return dprm
 
     def rest_joints(self):
         """J (24,3) of the most recent pose_into() call (kernel work buffer, csrc/geom.hip W_J)"""
         return self._work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS].clone()
 
     def forward(self, scale, transl, thetas, betas, absolute=False):
-        """smpl.py:50-94.  `smpl_tfs` carries gradients to scale / transl / thetas / betas when any of them requires grad
-        (the mesh-space losses back-propagate into BodyModelParams through it, multiply_model.py:586-620, 969-974; betas
-        through the rest joints, as in the training step); vertices and joints are returned detached."""
+        """smpl.py:50-94.  When any of scale / transl / thetas / betas requires grad (and absolute=False), smpl_verts,
+        smpl_jnts, smpl_all_jnts and smpl_tfs all carry gradients to them, as in the reference (the mesh-space losses and
+        keypoint terms back-propagate into BodyModelParams, multiply_model.py:586-620, 969-974): one autograd node
+        (_PoseLBS) over the same forward launches, so the values are those of the no-grad call."""
         dev = self.param_canonical.device
         p = torch.cat([scale.reshape(1, 1), transl.reshape(1, 3), thetas.reshape(1, 72), betas.reshape(1, 10)], 1)
         p = p.float().reshape(86)
-        verts = torch.empty(NUM_VERTS, 3, dtype=torch.float32, device=dev)
-        jnts = torch.empty(NUM_JOINTS, 3, dtype=torch.float32, device=dev)
         if torch.is_grad_enabled() and p.requires_grad and not absolute:
-            tfs = _PoseTfs.apply(self, p, verts, jnts)
+            verts, jnts, all_jnts, tfs = _PoseLBS.apply(self, p)
         else:
+            verts = torch.empty(NUM_VERTS, 3, dtype=torch.float32, device=dev)
+            jnts = torch.empty(NUM_JOINTS, 3, dtype=torch.float32, device=dev)
             tfs = torch.empty(NUM_JOINTS, 4, 4, dtype=torch.float32, device=dev)
             self.pose_into(p.detach().contiguous(), verts, tfs, jnts, absolute=absolute)
-        # smpl_all_jnts: the 24 kinematic joints + the face keypoint vertices (body_models.py:345; smpl.py:83-84) -- the
-        # vertices are already scaled / translated exactly like the joints (smpl.py:77-84)
-        all_jnts = torch.cat([jnts, verts[self.smpl.vertex_joint_selector.extra_joints_idxs]], 0)
+            # smpl_all_jnts: the 24 kinematic joints + the face keypoint vertices (body_models.py:345; smpl.py:83-84) -- the
+            # vertices are already scaled / translated exactly like the joints (smpl.py:77-84)
+            all_jnts = torch.cat([jnts, verts[self.smpl.vertex_joint_selector.extra_joints_idxs]], 0)
         return {"smpl_verts": verts[None], "smpl_jnts": jnts[None], "smpl_all_jnts": all_jnts[None], "smpl_tfs": tfs[None],
                 "smpl_weights": self.tables.lbs_weights[None]}

@@ -1372,10 +1372,11 @@ class TrainGraph:
         head of the backward sweep, before any person's weight-norm adjoint retires its accumulators."""
         m, cx, L, st = self.model, self.cx, hip.lib(), hip.stream()
         dev = cx["dev"]
-        if self.pose_grad and m.smpl_surface_weight > 0:
-            # (the zero-pose term's pose adjoint -- it reaches the pose through the conditioning only -- is built, round 6; the surface
-            # term's needs the adjoint of the posed VERTICES through blend shapes and skinning, which mp_smpl_pose_bwd does not carry)
-            raise NotImplementedError("smpl_surface with body-model inputs under optimisation: the adjoint of the posed vertices is not built")
+        if self.pose_grad and m.smpl_surface_weight > 0 and not getattr(m, "smpl_surface_pose_grad", False):
+            # (the surface term reaches the pose through the sampled posed VERTICES, their warp and the conditioning; that adjoint is
+            # built -- SMPLServer.pose_backward -- but opt-in: model.smpl_surface_pose_grad = True or MP_SMPL_SURFACE_POSE_GRAD=1)
+            raise NotImplementedError("smpl_surface with body-model inputs under optimisation is opt-in: set model.smpl_surface_pose_grad "
+                                      "= True (or MP_SMPL_SURFACE_POSE_GRAD=1)")
         ssl = torch.zeros(1, dtype=F32, device=dev)
         zpl = torch.zeros(1, dtype=F32, device=dev)
         for q in cx["persons"]:
@@ -1389,12 +1390,21 @@ class TrainGraph:
                 xc = torch.empty(n, 3, dtype=F32, device=dev)
                 _chk(L.mp_warp_inverse(_p(pts), None, None, None, None, None, 0, 1, n, _p(pp["vsorted"]), _p(pp["cbound"]),
                                        _p(pp["btab"]), 0, None, None, _p(xc), None, None, None, None, None, st), "mp_warp_inverse")
+                warp = None
+                if self.pose_grad:
+                    # the backward needs the nearest posed vertex of every sample (ties: lowest id) and its inverse blended
+                    # transform I_nn: the same exact search over the posed vertex structure (the weights are constants, deformer.py:47)
+                    jv = torch.empty(n, 9, dtype=F32, device=dev)
+                    nn = torch.empty(n, dtype=torch.int32, device=dev)
+                    _chk(L.mp_warp_jacobian(_p(pts), None, None, 0, 0, n, _p(pp["vsorted"]), _p(pp["cbound"]), _p(pp["btab"]),
+                                            _p(jv), _p(nn), None, None, st), "mp_warp_jacobian")
+                    warp = (xc, jv, nn, idx.to(torch.int32).contiguous())
                 it = ImplicitTrain(imp, xc, cond, fwd=False, lins=self.ts.lins[id(imp)])
                 sdf = it.out[:, 0]
                 mask = sdf > SMPL_SURFACE_THRESHOLD
                 cnt = mask.sum().clamp(min=1).to(F32)
                 ssl = ssl + torch.where(mask, sdf - SMPL_SURFACE_THRESHOLD, torch.zeros_like(sdf)).sum() / cnt      # 0 when none offends
-                self.reg_items.append(("surf", it, mask, cnt))
+                self.reg_items.append(("surf", it, mask, cnt, q, warp))
             if m.zero_pose_weight > 0:
                 for p, vcano in enumerate(m.mesh_v_cano_list):
                     net = m.foreground_implicit_network_list[p]
@@ -1409,15 +1419,33 @@ class TrainGraph:
 
     def _regularisers_backward(self, d_ssl, d_zpl):
         dev = self.cx["dev"]
-        self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the zero-pose term (pose optimisation)
+        self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the regularisers (pose optimisation)
+        self.reg_surf = {}              # person -> (d tfs [24][16], d posed vertices [V][3]) of the surface term (pose optimisation)
+        L, st = hip.lib(), hip.stream()
         for item in self.reg_items:
             if item[0] == "surf":
-                _, it, mask, cnt = item
+                _, it, mask, cnt, q, warp = item
                 if d_ssl is None:
                     continue
                 dZ = torch.zeros(it.P, 257, dtype=F32, device=dev)
                 dZ[:, 0] = d_ssl.reshape(()) * mask.to(F32) / cnt
-                it.backward(dZ)
+                dcond = it.backward(dZ, want_dx=warp is not None)
+                if warp is not None:
+                    # x_c = I_nn (x - c_nn), x = verts[surf_idx]: d tfs through the blended transform (mp_tr_warp_bwd), d x = I_nn^T d x_c
+                    # gathered onto the drawn vertices in sample order (mp_tr_gather_bwd; the draw repeats vertices)
+                    xc, jv, nn, idx = warp
+                    n = xc.shape[0]
+                    pp, server = self.cx["per"][q], self.model.smpl_server_list[q]
+                    dxc = it.dx.contiguous()
+                    dtfs = torch.zeros(24, 16, dtype=F32, device=dev)
+                    _chk(L.mp_tr_warp_bwd(_p(xc), _p(dxc), None, None, _p(nn), None, n, _p(server.tables.lbs_weights), _p(pp["tfs"]),
+                                          _p(dtfs), st), "mp_tr_warp_bwd")
+                    dverts = torch.zeros(server.verts_c.reshape(-1, 3).shape[0], 3, dtype=F32, device=dev)
+                    _chk(L.mp_tr_gather_bwd(_p(idx), n, _p(jv), _p(dxc), dverts.shape[0], _p(dverts), st), "mp_tr_gather_bwd")
+                    prev = self.reg_surf.get(q)
+                    self.reg_surf[q] = (dtfs, dverts) if prev is None else (prev[0] + dtfs, prev[1] + dverts)
+                    if not self.cond_zero:
+                        self.reg_dcond[q] = dcond if q not in self.reg_dcond else self.reg_dcond[q] + dcond
             else:
                 _, it1, it0, sg, q = item
                 if d_zpl is None:
@@ -1522,13 +1550,17 @@ class TrainGraph:
                 dtfs = torch.zeros(24, 16, **f32)
                 _chk(L.mp_tr_warp_bwd(_p(f["X"]), _p(dxc), _p(f["jinv"]), _p(djinv), _p(f["nn_posed"]), _p(f["nn_cano"]),
                                       npts, _p(server.tables.lbs_weights), _p(pp["tfs"]), _p(dtfs), st), "mp_tr_warp_bwd")
-                dprm = torch.empty(86, **f32)
-                _chk(L.mp_smpl_pose_bwd(_p(server.tables.parents), _p(pp["prm"]), _p(server.tfs_c_inv),
-                                        _p(pp["rest_joints"]), _p(server.tables.j_shapedirs), _p(dtfs), _p(dprm), st),
-                     "mp_smpl_pose_bwd")
+                surf = getattr(self, "reg_surf", {}).get(p)
+                if surf is None:
+                    dprm = torch.empty(86, **f32)
+                    _chk(L.mp_smpl_pose_bwd(_p(server.tables.parents), _p(pp["prm"]), _p(server.tfs_c_inv),
+                                            _p(pp["rest_joints"]), _p(server.tables.j_shapedirs), _p(dtfs), _p(dprm), st),
+                         "mp_smpl_pose_bwd")
+                else:                                                    # + the surface term's posed vertices and transforms
+                    dprm = server.pose_backward(pp["prm"], dverts=surf[1], dtfs=dtfs + surf[0])
                 if not self.cond_zero:                                   # cond = smpl_pose[3:] / pi  (multiply.py:270)
                     dc = dcond + torch.mv(rt.lp_w.t(), rt.extra_grads[1])
-                    if p in getattr(self, "reg_dcond", {}):             # + the zero-pose regulariser's share (round 6)
+                    if p in getattr(self, "reg_dcond", {}):             # + the regularisers' share (zero pose; surface, opt-in)
                         dc = dc + self.reg_dcond[p]
                     dprm[7:76] += dc / math.pi
                 self.pose_grads[p] = dprm
