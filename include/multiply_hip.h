@@ -79,7 +79,9 @@ int mp_pack_layers(const MpPackLayer* table, int n_layers, int ks_in, void* stre
  * mp_mlp_sdf: ImplicitNet.forward restricted to the sdf column (networks.py:126-181; caller:
  * multiply.py:140-141 inside the sampler, ray_sampler.py:85-88).
  *   xc [*][3] canonical points, worklist[i] = point id (NULL: id = i), *count work items
- *   sdf_out[point id] <- sdf.  multires = 6 Fourier encoding of 3-D input. */
+ *   sdf_out[point id] <- sdf.  multires = 6 Fourier encoding of 3-D input.
+ * Range: hidden pre-activations are carried as halves in scaled units (x 100 log2 e), so |z| < 65504 / 144.27 = 454.  Beyond
+ * that the sdf comes out +-inf or NaN, never finite and wrong (a unit that overflows towards -inf is exact: softplus 0). */
 int mp_mlp_sdf(const MpNet* net, const void* wpack, const float* bias, const float* xc, const int* worklist,
                const int* count, int max_count, float* sdf_out, void* stream);
 
@@ -110,7 +112,11 @@ int mp_mlp_shade(const MpNet* net, const void* wpack, const float* bias, const f
  * index) into `sig` (seg_points * mp_sig_bytes_per_point() B, seg_points a multiple of 256, ZERO-INITIALISED once by the
  * caller), then a reverse sweep through
  * the TRANSPOSED layers (gnet / gpack: the 'grad' plan of multiply_amd/hip.py; w8_slots: the sdf row of the last layer,
- * 256 halves in K-slot order).  Two network columns per point instead of the four of the forward-mode kernel. */
+ * 256 halves in K-slot order).  Two network columns per point instead of the four of the forward-mode kernel.
+ * Range (as mp_mlp_sdf): a point with a hidden pre-activation beyond |z| = 454 gets a non-finite sdf, and then a non-finite
+ * normal too (0 x sdf is added to it: the byte-sized stored sigmoids cannot carry the overflow); mp_mlp_color turns a
+ * non-finite normal into a non-finite rgb.  Measured at 1.2x the limit: every output finite inside the range, and non-finite
+ * exactly at the points whose sdf is. */
 int mp_sig_bytes_per_point(void);
 int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet, const void* gpack,
                      const void* w8_slots, const float* xc, const float* jinv, const int* worklist, const int* count,

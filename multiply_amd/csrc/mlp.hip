@@ -402,7 +402,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
                                                          const op_t* __restrict__ w8_slots, const float* __restrict__ xc,
                                                          const float* __restrict__ jinv, const int* __restrict__ worklist,
                                                          const int* __restrict__ count_p, int max_count, int offset, int seg,
-                                                         const char* __restrict__ sigbuf, float* __restrict__ normal_out) {
+                                                         const char* __restrict__ sigbuf, const float* __restrict__ sdf_in,
+                                                         float* __restrict__ normal_out) {
     constexpr int KS_IN = 0, PTS = 16 * NB, TILE = PTS * WAVES;   // no input-fed K steps: 16 KiB weight chunks
     static_assert(NB == 2 && WAVES == 8, "matches k_mlp_fwdsave's tile / wave / point addressing");
     constexpr int RING = RING_SLOTS * chunk_bytes(KS_IN);
@@ -502,9 +503,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
                 float inv = 1.0f / fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-12f);  // F.normalize default eps
                 n0 *= inv; n1 *= inv; n2 *= inv;
                 inv = 1.0f / fmaxf(sqrtf(n0 * n0 + n1 * n1 + n2 * n2), 1e-6f);         // multiply.py:606
-                normal_out[3 * (size_t)pid] = n0 * inv;
-                normal_out[3 * (size_t)pid + 1] = n1 * inv;
-                normal_out[3 * (size_t)pid + 2] = n2 * inv;
+                // f16 overflow in the forward sweep reaches sdf as inf / NaN, but the stored sigmoids are bytes that cannot carry
+                // it (a NaN sigmoid quantises to 0): the normal would come out finite and wrong.  0 x sdf is +-0 for a finite sdf
+                // (the normal is unchanged, bit for bit) and NaN otherwise, so the normal is non-finite exactly where the sdf is.
+                const float poison = 0.0f * sdf_in[pid];
+                normal_out[3 * (size_t)pid] = n0 * inv + poison;
+                normal_out[3 * (size_t)pid + 1] = n1 * inv + poison;
+                normal_out[3 * (size_t)pid + 2] = n2 * inv + poison;
             }
         }
         __syncthreads();   // the tables are rebuilt by the next tile
@@ -569,8 +574,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
         for (int nb = 0; nb < NB; ++nb) {
             const int pid = __shfl(id, nb * 16 + (lane & 15));
             if (lane < 16 && pid >= 0) {
+                // a non-finite normal (the shading kernels' overflow signal) makes the colour non-finite: through the ReLU chain
+                // and the output sigmoid a NaN / inf input can come out as a finite 0 or 1.  +-0 for finite normals.
+                const float* nq = normal + 3 * (size_t)pid;
+                const float poison = 0.0f * (nq[0] + nq[1] + nq[2]);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) rgb_out[3 * (size_t)pid + c] = 1.0f / (1.0f + __expf(-out[nb][c]));
+                for (int c = 0; c < 3; ++c) rgb_out[3 * (size_t)pid + c] = 1.0f / (1.0f + __expf(-out[nb][c])) + poison;
             }
         }
         MP_STAMP_AT(HID_RELU, 121, 0);
@@ -795,7 +804,7 @@ extern "C" int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float
                            xc, worklist, count, max_count, off, seg_points, sdf_out, (char*)feat_frag, (char*)sig);
         hipLaunchKernelGGL((k_mlp_grad<PNB, PWAVES>), dim3(grid), dim3(PWAVES * 64), LDS_G, st, gd, (const char*)gpack,
                            (const op_t*)w8_slots, xc, jinv, worklist, count, max_count, off, seg_points, (const char*)sig,
-                           normal_out);
+                           sdf_out, normal_out);
     }
     return (int)hipGetLastError();
 }

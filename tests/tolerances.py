@@ -151,3 +151,34 @@ def within(stats, tol):
         p999 = float(torch_quantile(e, 0.999)) if (e.numel() and n >= P999_MIN_RAYS) else 0.0
         return stats[1] < tol["mean"] and int((ray > tol["bulk"]).sum()) <= allowed and stats[0] < tol["hard"] and p999 <= tol["p999"]
     return stats[0] < tol[0] and stats[1] < tol[1]
+# The inference network kernels per weight regime (tests/weight_regimes.py, tests/test_mlp_weights_gpu.py) against the FLOAT64
+# reference, max over the points of every ragged count (1 ... 4 099): sdf / features / rgb max |err|, sdf_rel = sdf max |err| / the
+# sdf's spread over the test points, normals as the largest angle in degrees.  Bounds <= 5x the maxima measured on MI355X (beside
+# them).  The fp32 oracle's own share (vs float64): sdf 1.1e-6, normals 5e-4 deg, rgb 1.3e-5 (trained) -- negligible.
+# Reasoned parts: a stored sigmoid byte is off by <= 1/510 on a unit in transition (trained: 26-30 % of the units per layer), the
+# reverse-mode normals are therefore the worst (4.3 deg trained where the forward mode's tangents give 1.9); the colour nets' rgb error
+# is the f16 arithmetic itself: the same network with every weight, input and activation rounded to half in float64 is off by
+# 1.07e-2 where the kernel is off by 1.15e-2 (trained).  The split kernels' sdf error is the rounding of the half-precision WEIGHTS
+# (mp_mlp_sdf_x2) or of the split-bfloat16 products (mp_tf_sdf_val).
+MLP_GEOMETRIC = dict(
+    sdf=3e-3, sdf_rel=2.5e-3, feat=5e-3,              # 6.2e-4, 5.0e-4, 9.2e-4
+    sdf_x2=9e-4, sdf_tf=4.5e-5,                       # 1.7e-4, 8.4e-6
+    shade_sdf=3e-3, shade_normal_deg=2.5, shade_normal_surf_deg=1.8, shade_rgb=3e-5,   # 6.2e-4; 0.50 deg (reverse), 0.35 (forward), zero set 0.35; 6.1e-6
+    normal_rev_vs_fwd_deg=1.7, color_rgb=2.5e-5, bg_rgb=1.8e-4)   # 0.34 deg; 4.6e-6; 3.6e-5
+MLP_TRAINED = dict(
+    sdf=2.2e-3, sdf_rel=4.5e-3, feat=6.5e-3,          # 4.3e-4, 9.4e-4, 1.3e-3
+    sdf_x2=1.3e-3, sdf_tf=3.5e-5,                     # 2.6e-4, 6.9e-6
+    shade_sdf=2.2e-3, shade_normal_deg=21.0, shade_normal_surf_deg=4.3, shade_rgb=0.11,  # 4.3e-4; 4.3 deg (reverse; 0.85 on the zero set), 1.9 (forward); 2.2e-2
+    normal_rev_vs_fwd_deg=20.0, color_rgb=0.057, bg_rgb=5.5e-3)   # 4.0 deg; 1.15e-2 (f16 arithmetic, above); 1.1e-3
+MLP_NEAR_RANGE = dict(
+    sdf=0.49, sdf_rel=3.7e-3, feat=0.94,              # 9.8e-2 (sdf spread 134), 7.3e-4, 0.19 (features up to ~400)
+    sdf_x2=0.21, sdf_tf=8.2e-3,                       # 4.3e-2, 1.6e-3
+    shade_sdf=0.49, shade_normal_deg=146.0, shade_normal_surf_deg=52.0, shade_rgb=1e-6,   # 9.8e-2; 29 deg (points of |grad| ~ 0), 10.4 on the zero set; rgb saturated: 0
+    normal_rev_vs_fwd_deg=7.0, color_rgb=1e-6, bg_rgb=5.5e-3)     # 1.4 deg; 0 (saturated); 1.1e-3 (bg net as in trained)
+MLP_BY_REGIME = {"geometric": MLP_GEOMETRIC, "trained": MLP_TRAINED, "near_range": MLP_NEAR_RANGE}
+# error ratio f16 kernel / near-fp32 sdf kernel on the same points (>= 255 points).  mp_tf_sdf_val: measured >= 59.7 in every regime.
+# mp_mlp_sdf_x2 keeps the half-precision weights, and their rounding is the larger part of the f16 kernel's error once units are in
+# transition: measured 3.6-3.9 (geometric), 1.4-1.7 (trained), 2.3-2.8 (near_range) -- not the order of magnitude DESIGN §4 once
+# stated; the bound pins what holds.
+MLP_PRECISE_RATIO = 5.0
+MLP_SPLIT_RATIO = 1.2
