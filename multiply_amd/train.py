@@ -13,7 +13,9 @@ The non-differentiable sampler (VolSDF Algorithm 1, ray_sampler.py:81-191, `torc
 the fused half-precision kernels exactly like in eval mode, with the training-mode randomness drawn by torch.rand on the device.
 """
 import ctypes as C
+import functools
 import math
+import os
 
 import numpy as np
 import torch
@@ -28,7 +30,7 @@ def _p(t):
     return hip.ptr(t)
 
 
-_DEBUG_SYNC = bool(int(__import__("os").environ.get("MP_DEBUG_SYNC", "0")))
+_DEBUG_SYNC = bool(int(os.environ.get("MP_DEBUG_SYNC", "0")))
 
 
 def _chk(code, what):
@@ -43,7 +45,7 @@ def _chk(code, what):
 #            (hi.hi + hi.lo + lo.hi), fp32 accumulation: ~2^-16 relative per product, the range of fp32 (no loss scaling),
 #            5x less matrix-pipe time than the exact-fp32 instruction -- the GEMMs run at the rate HBM delivers their operands;
 #   "f32":   v_mfma_f32_16x16x4_f32, bitwise an fmaf chain -- the cross-check (tests/test_train_step_gpu.py runs both).
-TRAIN_PRECISION = __import__("os").environ.get("MP_TRAIN_PRECISION", "bf16x3")
+TRAIN_PRECISION = os.environ.get("MP_TRAIN_PRECISION", "bf16x3")
 
 
 def gemm_nt(A, lda, B, ldb, Cm, ldc, M, N, K, bias=None, bias_rows=0, accumulate=False, relu=False):
@@ -142,22 +144,87 @@ class LinW:
         return [lin.weight_g, lin.weight_v, lin.bias] if self.wn else [lin.weight, lin.bias]
 
 
-class ImplicitTrain:
-    """ImplicitNet (networks.py:126-208) evaluated layer by layer for P points, optionally in forward mode."""
+class _NetParams:
+    """parameters and their gradients of a network evaluated for training, in matching order: `extra_*` (the colour net's lin_pose)
+    first, then every layer"""
+    extra_params = extra_grads = ()
 
-    def __init__(self, net, x, cond_vec, fwd, lins=None):
-        L = hip.lib()
-        self.net, self.fwd, self.x = net, fwd, x
+    def params(self):
+        return list(self.extra_params) + [p for lw in self.lins for p in lw.params()]
+
+    def param_grads(self):
+        return list(self.extra_grads) + [g for lw in self.lins for g in lw.param_grads()]
+
+
+def launch_tn_groups(groups):
+    """the deferred aligned weight-gradient contractions of one network or person (tn_group records) in one grouped launch"""
+    if TRAIN_PRECISION == "bf16x3":
+        gemm_tn_grouped(groups)
+    else:                                   # exact-fp32 cross-check: one launch per contraction
+        for g in groups:
+            gemm_tn(C.c_void_p(g.A), g.lda, C.c_void_p(g.B), g.ldb, C.c_void_p(g.C), g.ldc, g.M, g.N, g.K,
+                    C.c_void_p(g.colsum) if g.colsum else None, g.colsum_rows)
+
+
+def _layer0_adjoint(lw0, dZ0, X0, ldx, kx, rows, bias_rows, c0, n_h, hvec):
+    """Layer 0 of a network whose conditioning is hoisted into the bias (b0 = b + W0[:, c0:c0+n_h] hvec): the weight gradient
+    dW0[:, :kx] += dZ0^T X0 over `rows` rows, the bias gradient over the first `bias_rows`, dW0[:, c0:c0+n_h] += db0 (x) hvec;
+    returns d hvec = W0[:, c0:c0+n_h]^T db0.  dZ0 [rows][out], X0 [rows][ldx]: device pointers."""
+    out, dev = lw0.out_dim, lw0.W.device
+    # layer 0's bias gradient of THIS evaluation on its own (db0), then added to the accumulator: the hoisted
+    # conditioning's adjoint below must not see what other evaluations of the same network left in lw0.db
+    # (the zero-pose regulariser evaluates a network under two conditionings in one sweep)
+    db0 = _zeros(out, device=dev)
+    gemm_tn(dZ0, out, X0, ldx, _p(lw0.dW), lw0.in_dim, out, kx, rows, _p(db0), bias_rows)
+    lw0.db.add_(db0)
+    _chk(hip.lib().mp_tr_hoist_bwd(_p(db0), out, lw0.in_dim, c0, n_h, _p(hvec), _p(lw0.dW), hip.stream()), "mp_tr_hoist_bwd")
+    dh = _zeros(n_h, device=dev)
+    gemm_tn(_p(db0), 1, off(lw0.W, c0), lw0.in_dim, _p(dh), n_h, 1, n_h, out)
+    return dh
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# An SDF-type network (foreground ImplicitNet, background ImplicitNet) evaluated for training.  Four evaluators, ONE surface:
+#   .P                    points;  .lins  the layers (LinW / LinP)
+#   .sdf [>= P]           column 0 of the reference's output, contiguous
+#   .feat_ptr, .feat_ld   columns 1..256: device pointer to row 0 and the row stride (the colour net reads them in place)
+#   .grad [P][3] | None   d sdf / d x, where the evaluator differentiates in space
+#   new_dfeat(n)          the features' adjoint as THIS evaluator wants it delivered: a tensor in the evaluator's own layout, rows
+#                         [0, n) to be filled by a colour net, the others zero;  dfeat_target(dfeat) -> (pointer, leading
+#                         dimension, accumulate) for that colour net's backward (accumulate: it ADDS into a zeroed buffer;
+#                         else it WRITES its rows).  Layer-wise evaluators: the reference's [rows][257] adjoint, features in
+#                         columns 1..; fused ones: their own [P][256] matrix.
+#   backward(dfeat, dsdf [P], dgrad [P][3] | None, want_dx=False, tn_groups=None) -> d cond
+#                         accumulates dW / db of every layer.  want_dx: also self.dx [P][d_in], the adjoint of the points.
+#                         tn_groups (a list): an evaluator with aligned weight-gradient contractions appends them instead of
+#                         launching them (the caller: launch_tn_groups); the layer-wise ones launch their own.
+#                         Layer-wise evaluators also take dsdf / dgrad = None: the caller has written column 0 of dfeat itself.
+#   params(), param_grads()
+# sdf_evaluator() / bg_evaluator() choose among them.
+# ----------------------------------------------------------------------------------------------------------------------
+class _SdfEvaluator(_NetParams):
+    def dfeat_target(self, dfeat):
+        """where a colour net's backward delivers the features' adjoint inside this evaluator's new_dfeat() tensor"""
+        return off(dfeat, self.dfeat_col0), dfeat.shape[1], self.dfeat_accumulate
+
+
+class _LayerwiseImplicit(_SdfEvaluator):
+    """The ImplicitNet's value sweep layer by layer with every pre-activation kept, and its adjoint: shared by ImplicitTrain
+    (4P rows in forward mode: the tangent rows ride through mp_tr_softplus_fwd / _bwd) and ImplicitTrainRev (P rows; sigma''
+    enters the adjoint through dS, mp_tr_dz).  self.out [rows][257] is the reference's layout: column 0 = sdf."""
+    feat_ld = 257
+    dfeat_col0, dfeat_accumulate = 1, True
+
+    def _value_sweep(self, net, x, cond_vec, fwd, lins):
+        L, st = hip.lib(), hip.stream()
+        self.net, self.fwd, self.x, self.cond = net, fwd, x, cond_vec
         dev = x.device
         self.P = P = x.shape[0]
         self.rows = rows = 4 * P if fwd else P
         self.E = E = net.embed_dim
-        self.cond = cond_vec
         self.lins = lins if lins is not None else [LinW(l) for l in net.layers()]
-        nl = len(self.lins)
         self.IN = torch.empty(rows, E, dtype=F32, device=dev)
-        _chk(L.mp_tr_pe(_p(x), net.d_in, P, net.multires, int(fwd), C.c_float(1.0), _p(self.IN), E, 0, hip.stream()),
-             "mp_tr_pe")
+        _chk(L.mp_tr_pe(_p(x), net.d_in, P, net.multires, int(fwd), C.c_float(1.0), _p(self.IN), E, 0, st), "mp_tr_pe")
         self.Z, self.X = [], []          # pre-activations and layer inputs
         r2 = 1.0 / math.sqrt(2.0)
         Pm = P if fwd else 0
@@ -166,91 +233,109 @@ class ImplicitTrain:
             Z = torch.empty(rows, out, dtype=F32, device=dev)
             if l == 0:
                 self.b0 = torch.empty(out, dtype=F32, device=dev)
-                _chk(L.mp_tr_hoist_fwd(_p(lw.W), out, lw.in_dim, _p(lw.b), E, net.cond_dim, _p(cond_vec), _p(self.b0),
-                                       hip.stream()), "mp_tr_hoist_fwd")
+                _chk(L.mp_tr_hoist_fwd(_p(lw.W), out, lw.in_dim, _p(lw.b), E, net.cond_dim, _p(cond_vec), _p(self.b0), st),
+                     "mp_tr_hoist_fwd")
                 Xl = self.IN
                 gemm_nt(_p(Xl), E, _p(lw.W), lw.in_dim, _p(Z), out, rows, out, E, _p(self.b0), P)
             else:
-                Zp, prev_out = self.Z[l - 1], self.lins[l - 1].out_dim
-                if l in net.skip_in:
-                    Xl = torch.empty(rows, prev_out + E, dtype=F32, device=dev)
-                    _chk(L.mp_tr_softplus_fwd(_p(Zp), prev_out, rows, prev_out, Pm, C.c_float(r2), _p(Xl), prev_out + E, 0,
-                                              hip.stream()), "mp_tr_softplus_fwd")
-                    _chk(L.mp_tr_copy_cols(_p(self.IN), E, 0, _p(Xl), prev_out + E, prev_out, rows, E, C.c_float(r2), 0,
-                                           hip.stream()), "mp_tr_copy_cols")
-                else:
-                    Xl = torch.empty(rows, prev_out, dtype=F32, device=dev)
-                    _chk(L.mp_tr_softplus_fwd(_p(Zp), prev_out, rows, prev_out, Pm, C.c_float(1.0), _p(Xl), prev_out, 0,
-                                              hip.stream()), "mp_tr_softplus_fwd")
+                Zp, po = self.Z[l - 1], self.lins[l - 1].out_dim
+                skip = l in net.skip_in
+                Xl = torch.empty(rows, po + E if skip else po, dtype=F32, device=dev)
+                _chk(L.mp_tr_softplus_fwd(_p(Zp), po, rows, po, Pm, C.c_float(r2 if skip else 1.0), _p(Xl), Xl.shape[1], 0, st),
+                     "mp_tr_softplus_fwd")
+                if skip:
+                    _chk(L.mp_tr_copy_cols(_p(self.IN), E, 0, _p(Xl), po + E, po, rows, E, C.c_float(r2), 0, st), "mp_tr_copy_cols")
                 gemm_nt(_p(Xl), Xl.shape[1], _p(lw.W), lw.in_dim, _p(Z), out, rows, out, lw.in_dim, _p(lw.b), P)
             self.Z.append(Z)
             self.X.append(Xl)
         self.out = self.Z[-1]            # [rows][257]
+        self.feat_ptr = off(self.out, 1)
+        self.sdf = torch.empty(P, dtype=F32, device=dev)
+        _chk(L.mp_tr_copy_cols(_p(self.out), 257, 0, _p(self.sdf), 1, 0, P, 1, C.c_float(1.0), 0, st), "mp_tr_copy_cols")
 
-    def backward(self, dZ_last, want_dx=False):
-        """dZ_last [rows][257] -> accumulates dW/db of every layer; returns d cond (hoisted conditioning adjoint).
-        want_dx: also the adjoint of the input points, self.dx [P][d_in] (pose optimisation)."""
-        L = hip.lib()
+    def new_dfeat(self, n=0):
+        return torch.zeros(self.rows, 257, dtype=F32, device=self.x.device)
+
+    def _value_adjoint(self, dZ, dS=None, want_dx=False, grouped=False):
+        """dZ [rows][257]: the last layer's adjoint -> dW / db of every layer; returns d cond (hoisted conditioning adjoint).
+        dS[l] (reverse-over-reverse): the gradient sweep's adjoint w.r.t. sigma'(Z_l).  want_dx: adds the points' adjoint to
+        self.dx [P][d_in] (created here unless the caller's own sweep already did).  grouped: the 256 x 256 weight gradients in
+        one grouped launch."""
+        L, st = hip.lib(), hip.stream()
         net, rows, P, E = self.net, self.rows, self.P, self.E
+        dev = dZ.device
         Pm = P if self.fwd else 0
         r2 = 1.0 / math.sqrt(2.0)
-        dZ = dZ_last
-        dcond = None
-        dIN = torch.zeros(rows, E, dtype=F32, device=dZ.device) if want_dx else None
+        dIN = torch.zeros(rows, E, dtype=F32, device=dev) if want_dx else None
         # the 256 x 256 weight gradients wait for ONE grouped launch at the end (six small contractions launched one by one
         # cost 64 us each; their operands stay alive in `held`)
         groups, held = [], []
-        for l in range(len(self.lins) - 1, -1, -1):
+        for l in range(len(self.lins) - 1, 0, -1):
             lw, Xl = self.lins[l], self.X[l]
-            out = lw.out_dim
-            kin = E if l == 0 else lw.in_dim
-            if TRAIN_PRECISION == "bf16x3" and l > 0 and out == 256 and kin == 256 and Xl.shape[1] == 256:
-                groups.append(tn_group(_p(dZ), out, _p(Xl), 256, _p(lw.dW), lw.in_dim, out, kin, rows, _p(lw.db), P))
+            out, po = lw.out_dim, self.lins[l - 1].out_dim
+            if grouped and TRAIN_PRECISION == "bf16x3" and out == 256 and lw.in_dim == 256:
+                groups.append(tn_group(_p(dZ), out, _p(Xl), 256, _p(lw.dW), lw.in_dim, out, 256, rows, _p(lw.db), P))
                 held.append(dZ)
-            elif l == 0:
-                # layer 0's bias gradient of THIS evaluation on its own (db0), then added to the accumulator: the hoisted
-                # conditioning's adjoint below must not see what other evaluations of the same network left in lw.db
-                # (the zero-pose regulariser evaluates a network under two conditionings in one sweep)
-                db0 = _zeros(out, device=dZ.device)
-                gemm_tn(_p(dZ), out, _p(Xl), Xl.shape[1], _p(lw.dW), lw.in_dim, out, kin, rows, _p(db0), P)
-                lw.db.add_(db0)
             else:
-                gemm_tn(_p(dZ), out, _p(Xl), Xl.shape[1], _p(lw.dW), lw.in_dim, out, kin, rows, _p(lw.db), P)
-            if l == 0:
-                # hoisted conditioning: dW0[:, E:] += db (x) cond ; d cond = W0[:, E:]^T db
-                _chk(L.mp_tr_hoist_bwd(_p(db0), out, lw.in_dim, E, net.cond_dim, _p(self.cond), _p(lw.dW), hip.stream()),
-                     "mp_tr_hoist_bwd")
-                dcond = _zeros(net.cond_dim, device=dZ.device)
-                gemm_tn(_p(db0), 1, off(lw.W, E), lw.in_dim, _p(dcond), net.cond_dim, 1, net.cond_dim, out)
-                if want_dx:
-                    gemm_nt(_p(dZ), out, _p(lw.WT), out, _p(dIN), E, rows, E, out, accumulate=True)
-                    self.dx = torch.zeros(P, net.d_in, dtype=F32, device=dZ.device)
-                    _chk(L.mp_tr_pe_bwd(_p(self.x), net.d_in, P, net.multires, int(self.fwd), _p(dIN), E, _p(self.dx),
-                                        hip.stream()), "mp_tr_pe_bwd")
-                break
-            prev_out = self.lins[l - 1].out_dim
-            dX = torch.empty(rows, lw.in_dim, dtype=F32, device=dZ.device)
+                gemm_tn(_p(dZ), out, _p(Xl), lw.in_dim, _p(lw.dW), lw.in_dim, out, lw.in_dim, rows, _p(lw.db), P)
+            dX = torch.empty(rows, lw.in_dim, dtype=F32, device=dev)
             gemm_nt(_p(dZ), out, _p(lw.WT), out, _p(dX), lw.in_dim, rows, lw.in_dim, out)
-            if want_dx and l in net.skip_in:      # the skip connection's copy of the encoded input
-                _chk(L.mp_tr_copy_cols(_p(dX), lw.in_dim, prev_out, _p(dIN), E, 0, rows, E, C.c_float(r2), 1, hip.stream()),
-                     "mp_tr_copy_cols")
-            dZp = torch.empty(rows, prev_out, dtype=F32, device=dZ.device)
-            scale = r2 if l in net.skip_in else 1.0
-            _chk(L.mp_tr_softplus_bwd(_p(self.Z[l - 1]), prev_out, rows, prev_out, Pm, C.c_float(scale), _p(dX), lw.in_dim,
-                                      0, _p(dZp), prev_out, hip.stream()), "mp_tr_softplus_bwd")
+            skip = l in net.skip_in
+            if want_dx and skip:      # the skip connection's copy of the encoded input
+                _chk(L.mp_tr_copy_cols(_p(dX), lw.in_dim, po, _p(dIN), E, 0, rows, E, C.c_float(r2), 1, st), "mp_tr_copy_cols")
+            dZp = torch.empty(rows, po, dtype=F32, device=dev)
+            scale = C.c_float(r2 if skip else 1.0)
+            if dS is None:
+                _chk(L.mp_tr_softplus_bwd(_p(self.Z[l - 1]), po, rows, po, Pm, scale, _p(dX), lw.in_dim, 0, _p(dZp), po, st),
+                     "mp_tr_softplus_bwd")
+            else:
+                _chk(L.mp_tr_dz(_p(self.Z[l - 1]), po, P, po, _p(dX), lw.in_dim, scale, _p(dS[l - 1]), po, _p(dZp), po, st),
+                     "mp_tr_dz")
             dZ = dZp
+        lw0 = self.lins[0]
+        dcond = _layer0_adjoint(lw0, _p(dZ), _p(self.IN), E, E, rows, P, E, net.cond_dim, self.cond)
+        if want_dx:
+            gemm_nt(_p(dZ), lw0.out_dim, _p(lw0.WT), lw0.out_dim, _p(dIN), E, rows, E, lw0.out_dim, accumulate=True)
+            if self.dx is None:
+                self.dx = torch.zeros(P, net.d_in, dtype=F32, device=dev)
+            _chk(L.mp_tr_pe_bwd(_p(self.x), net.d_in, P, net.multires, int(self.fwd), _p(dIN), E, _p(self.dx), st), "mp_tr_pe_bwd")
         if groups:
             gemm_tn_grouped(groups)
         return dcond
 
-    def params(self):
-        return [p for lw in self.lins for p in lw.params()]
-
-    def param_grads(self):
-        return [g for lw in self.lins for g in lw.param_grads()]
+    def _dsdf_into(self, dZ, dsdf):
+        """d sdf -> column 0 of the value rows of dZ [rows][257]"""
+        _chk(hip.lib().mp_tr_copy_cols(_p(dsdf), 1, 0, _p(dZ), 257, 0, self.P, 1, C.c_float(1.0), 0, hip.stream()), "mp_tr_copy_cols")
 
 
-class ImplicitTrainRev:
+class ImplicitTrain(_LayerwiseImplicit):
+    """ImplicitNet (networks.py:126-208) evaluated layer by layer for P points; fwd=True: in FORWARD mode, three tangent row blocks
+    below the P value rows carry d / d x_k through every layer (self.out [4P][257]), gathered into self.grad [P][3]."""
+
+    def __init__(self, net, x, cond_vec, fwd, lins=None):
+        self._value_sweep(net, x, cond_vec, fwd, lins)
+        self.grad = None
+        if fwd:
+            L, P = hip.lib(), self.P
+            self.grad = torch.empty(P, 3, dtype=F32, device=x.device)
+            for k in range(3):           # column 0 of tangent block k
+                _chk(L.mp_tr_copy_cols(off(self.out, (k + 1) * P * 257), 257, 0, _p(self.grad), 3, k, P, 1, C.c_float(1.0), 0,
+                                       hip.stream()), "mp_tr_copy_cols")
+
+    def backward(self, dfeat, dsdf=None, dgrad=None, want_dx=False, tn_groups=None):
+        L, P, dZ = hip.lib(), self.P, dfeat
+        assert dZ.shape == (self.rows, 257) and (dgrad is None or self.fwd)
+        if dsdf is not None:
+            self._dsdf_into(dZ, dsdf)
+        if dgrad is not None:
+            for k in range(3):
+                _chk(L.mp_tr_copy_cols(_p(dgrad), 3, k, off(dZ, (k + 1) * P * 257), 257, 0, P, 1, C.c_float(1.0), 0, hip.stream()),
+                     "mp_tr_copy_cols")
+        self.dx = None
+        return self._value_adjoint(dZ, want_dx=want_dx, grouped=True)
+
+
+class ImplicitTrainRev(_LayerwiseImplicit):
     """Foreground ImplicitNet for P points with d sdf / d x by REVERSE-over-reverse differentiation:
 
         forward   Z_l = X_l W_l^T + b_l,  X_{l+1} = softplus(Z_l)                       (value only, P rows)
@@ -259,46 +344,18 @@ class ImplicitTrainRev:
 
     = what torch autograd does for the reference (multiply.py:643-659 with create_graph=True): 6 GEMMs per layer over P
     rows, where the forward-mode class above spends 3 GEMMs over 4P rows.  Same results, same parameter gradients.
-    self.out [P][257] = last layer, self.grad [P][3] = d sdf / d x."""
+    The value sweep and its adjoint are _LayerwiseImplicit's; this class adds the gradient sweep and that sweep's adjoint.
+    The only evaluator that yields the adjoint of the input points (pose optimisation)."""
 
     def __init__(self, net, x, cond_vec, lins=None):
         L = hip.lib()
         st = hip.stream()
-        self.net, self.x, self.cond = net, x, cond_vec
-        dev = x.device
-        self.P = P = x.shape[0]
-        self.E = E = net.embed_dim
         assert net.d_in == 3 and len(net.skip_in) == 1
-        self.lins = lins = lins if lins is not None else [LinW(l) for l in net.layers()]
+        self._value_sweep(net, x, cond_vec, False, lins)
+        lins, P, E = self.lins, self.P, self.E
         self.nl = nl = len(lins)
         r2 = 1.0 / math.sqrt(2.0)
-        f32 = dict(dtype=F32, device=dev)
-        self.IN = torch.empty(P, E, **f32)
-        _chk(L.mp_tr_pe(_p(x), 3, P, net.multires, 0, C.c_float(1.0), _p(self.IN), E, 0, st), "mp_tr_pe")
-        # ---- value sweep
-        self.Z, self.X = [], []
-        for l, lw in enumerate(lins):
-            out = lw.out_dim
-            Z = torch.empty(P, out, **f32)
-            if l == 0:
-                self.b0 = torch.empty(out, **f32)
-                _chk(L.mp_tr_hoist_fwd(_p(lw.W), out, lw.in_dim, _p(lw.b), E, net.cond_dim, _p(cond_vec), _p(self.b0), st),
-                     "mp_tr_hoist_fwd")
-                Xl = self.IN
-                gemm_nt(_p(Xl), E, _p(lw.W), lw.in_dim, _p(Z), out, P, out, E, _p(self.b0), P)
-            else:
-                po = lins[l - 1].out_dim
-                if l in net.skip_in:
-                    Xl = torch.empty(P, po + E, **f32)
-                    _chk(L.mp_tr_softplus_fwd(_p(self.Z[l - 1]), po, P, po, 0, C.c_float(r2), _p(Xl), po + E, 0, st), "softplus")
-                    _chk(L.mp_tr_copy_cols(_p(self.IN), E, 0, _p(Xl), po + E, po, P, E, C.c_float(r2), 0, st), "copy_cols")
-                else:
-                    Xl = torch.empty(P, po, **f32)
-                    _chk(L.mp_tr_softplus_fwd(_p(self.Z[l - 1]), po, P, po, 0, C.c_float(1.0), _p(Xl), po, 0, st), "softplus")
-                gemm_nt(_p(Xl), Xl.shape[1], _p(lw.W), lw.in_dim, _p(Z), out, P, out, lw.in_dim, _p(lw.b), P)
-            self.Z.append(Z)
-            self.X.append(Xl)
-        self.out = self.Z[-1]
+        f32 = dict(dtype=F32, device=x.device)
         # ---- reverse sweep for d sdf / d x
         nh = nl - 1                                   # hidden layers 0..nh-1
         self.w8 = lins[nh].W[0].contiguous()          # sdf row of the last layer
@@ -324,15 +381,17 @@ class ImplicitTrainRev:
         self.grad = torch.empty(P, 3, **f32)
         _chk(L.mp_tr_pe_grad_fwd(_p(x), P, net.multires, _p(self.Gpe), E, _p(self.grad), st), "mp_tr_pe_grad_fwd")
 
-    def backward(self, dZ_last, dgrad, want_dx=False):
-        """dZ_last [P][257], dgrad [P][3] -> dW/db of every layer; returns d cond; want_dx: self.dx [P][3]"""
+    def backward(self, dfeat, dsdf, dgrad, want_dx=False, tn_groups=None):
         L = hip.lib()
         st = hip.stream()
         net, P, E, lins = self.net, self.P, self.E, self.lins
         nh = self.nl - 1
-        dev = dZ_last.device
-        f32 = dict(dtype=F32, device=dev)
+        dZ = dfeat
+        assert dZ.shape == (P, 257)
+        f32 = dict(dtype=F32, device=dZ.device)
         r2 = 1.0 / math.sqrt(2.0)
+        if dsdf is not None:
+            self._dsdf_into(dZ, dsdf)
         # ---- adjoint of the reverse sweep (ascending l)
         dGpe = torch.empty(P, E, **f32)
         self.dx = torch.zeros(P, 3, **f32) if want_dx else None
@@ -370,44 +429,7 @@ class ImplicitTrainRev:
         _chk(L.mp_tr_colsum(_p(dU), top, P, top, _p(dw8), st), "mp_tr_colsum")
         lins[nh].dW[0] += dw8
         # ---- adjoint of the value sweep (descending l)
-        dZ = dZ_last
-        dcond = None
-        dIN = torch.zeros(P, E, **f32) if want_dx else None
-        for l in range(nh, -1, -1):
-            lw, Xl = lins[l], self.X[l]
-            out = lw.out_dim
-            kin = E if l == 0 else lw.in_dim
-            if l == 0:           # (this evaluation's own bias gradient: see ImplicitTrain.backward)
-                db0 = _zeros(out, device=dZ.device)
-                gemm_tn(_p(dZ), out, _p(Xl), Xl.shape[1], _p(lw.dW), lw.in_dim, out, kin, P, _p(db0), P)
-                lw.db.add_(db0)
-            else:
-                gemm_tn(_p(dZ), out, _p(Xl), Xl.shape[1], _p(lw.dW), lw.in_dim, out, kin, P, _p(lw.db), P)
-            if l == 0:
-                _chk(L.mp_tr_hoist_bwd(_p(db0), out, lw.in_dim, E, net.cond_dim, _p(self.cond), _p(lw.dW), st), "mp_tr_hoist_bwd")
-                dcond = torch.zeros(net.cond_dim, **f32)
-                gemm_tn(_p(db0), 1, off(lw.W, E), lw.in_dim, _p(dcond), net.cond_dim, 1, net.cond_dim, out)
-                if want_dx:
-                    gemm_nt(_p(dZ), out, _p(lw.WT), out, _p(dIN), E, P, E, out, accumulate=True)
-                    _chk(L.mp_tr_pe_bwd(_p(self.x), 3, P, net.multires, 0, _p(dIN), E, _p(self.dx), st), "mp_tr_pe_bwd")
-                break
-            po = lins[l - 1].out_dim
-            dX = torch.empty(P, lw.in_dim, **f32)
-            gemm_nt(_p(dZ), out, _p(lw.WT), out, _p(dX), lw.in_dim, P, lw.in_dim, out)
-            sc = r2 if l in net.skip_in else 1.0
-            if want_dx and l in net.skip_in:
-                _chk(L.mp_tr_copy_cols(_p(dX), lw.in_dim, po, _p(dIN), E, 0, P, E, C.c_float(r2), 1, st), "copy_cols")
-            dZp = torch.empty(P, po, **f32)
-            _chk(L.mp_tr_dz(_p(self.Z[l - 1]), po, P, po, _p(dX), lw.in_dim, C.c_float(sc), _p(dS[l - 1]), po, _p(dZp), po, st),
-                 "mp_tr_dz")
-            dZ = dZp
-        return dcond
-
-    def params(self):
-        return [p for lw in self.lins for p in lw.params()]
-
-    def param_grads(self):
-        return [g for lw in self.lins for g in lw.param_grads()]
+        return self._value_adjoint(dZ, dS, want_dx=want_dx)
 
 
 class MpWnDesc(C.Structure):
@@ -586,57 +608,162 @@ def fused_sdf_supported(net):
             and list(net.dims[1:-1]) == [256] * 8 and net.dims[-1] == 257)
 
 
-class FusedSDFState:
-    """Per-network device state of the layer-fused training kernels (csrc/tfuse.hip): persistent effective weights, the split-bf16
-    chunk stream, the bias table and the pointer tables mp_tf_sdf_pack reads."""
+def fused_bg_supported(net):
+    """the network shape the fused background kernels (csrc/tfuse.hip k_tf_bg_*) are specialised for: the shipped NeRF++ net"""
+    return (net.d_in == 4 and net.multires == 10 and list(net.skip_in) == [4] and net.num_layers - 1 == 9 and net.cond_dim == 32
+            and list(net.dims[1:-1]) == [256] * 8 and net.dims[-1] == 257 and not hasattr(net.lin0, "weight_g"))
 
-    def __init__(self, net, lins=None):
+
+def fused_col_supported(net):
+    """the RenderingNet shape the fused colour kernels of csrc/tfuse.hip are specialised for (the shipped foreground net)"""
+    return net.mode == "pose_no_view" and list(net.dims) == [270, 256, 256, 256, 256, 3]
+
+
+# the three kernel families of csrc/tfuse.hip: (sizes entry point, pack entry point, layers, layer whose accumulators are padded to
+# 256 rows -- its 217 / 172 rows are contracted as 256, see LinP)
+_FUSED_KINDS = {"sdf": ("mp_tf_sdf_sizes", "mp_tf_sdf_pack", 9, 3), "bg": ("mp_tf_bg_sizes", "mp_tf_bg_pack", 9, 3),
+                "col": ("mp_tf_col_sizes", "mp_tf_col_pack", 5, None)}
+
+
+class FusedState:
+    """Per-network device state of the layer-fused training kernels (csrc/tfuse.hip), kind 'sdf' | 'bg' | 'col': persistent
+    effective weights, the split-bf16 chunk stream, the bias table and the pointer tables mp_tf_<kind>_pack reads."""
+
+    def __init__(self, kind, net, lins=None):
         """lins: the network's LinP list of a TrainState (weights resolved and accumulators bound by TrainState.begin); None:
         standalone layers owned by this object (unit tests, tools)"""
-        self.net = net
+        self.kind, self.net = kind, net
+        sizes, self._pack, n_layers, pad = _FUSED_KINDS[kind]
         self.shared = lins is not None
-        self.lins = lins if self.shared else [LinP(l, pad_rows=256 if i == 3 else 0) for i, l in enumerate(net.layers())]
+        self.lins = lins if self.shared else [LinP(l, pad_rows=256 if i == pad else 0) for i, l in enumerate(net.layers())]
         dev = self.lins[0].W.device
-        arena, pack = C.c_longlong(0), C.c_longlong(0)
-        _chk(hip.lib().mp_tf_sdf_sizes(1, C.byref(arena), C.byref(pack)), "mp_tf_sdf_sizes")
-        self.arena_per_point = int(arena.value)
+        per_point, pack = C.c_longlong(0), C.c_longlong(0)
+        _chk(getattr(hip.lib(), sizes)(1, C.byref(per_point), C.byref(pack)), sizes)
+        self.arena_per_point = int(per_point.value)
         self.wpack = torch.empty(int(pack.value), dtype=torch.uint8, device=dev)
-        self.bias_all = torch.empty(9 * 288, dtype=F32, device=dev)
+        self.bias_all = torch.empty(n_layers * 288, dtype=F32, device=dev)
         self.b0 = torch.empty(256, dtype=F32, device=dev)
+        self.pose8 = torch.empty(8, dtype=F32, device=dev) if kind == "col" else None
         self.wtab = _table([lw.W for lw in self.lins], dev)
         self._btab_key, self.btab = None, None
 
     def refresh(self, cond_vec):
+        """this iteration's weights and conditioning -> chunk stream and bias table (layer 0's bias carries the hoisted conditioning)"""
         L, st = hip.lib(), hip.stream()
         net, lins = self.net, self.lins
         if not self.shared:
             for lw in lins:
                 lw.refresh()
+        if self.kind == "col":          # the colour net hoists lin_pose(cond) (8), columns 6..13 of its input
+            lp = net.lin_pose
+            self.lp_w, self.lp_b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
+            _chk(L.mp_tr_hoist_fwd(_p(self.lp_w), 8, 69, _p(self.lp_b), 0, 69, _p(cond_vec), _p(self.pose8), st), "mp_tr_hoist_fwd")
+            c0, n_h, hvec = 6, 8, self.pose8
+        else:
+            c0, n_h, hvec = net.embed_dim, net.cond_dim, cond_vec
         lw0 = lins[0]
-        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), 256, lw0.in_dim, _p(lw0.b), net.embed_dim, net.cond_dim, _p(cond_vec), _p(self.b0), st),
-             "mp_tr_hoist_fwd")
+        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), 256, lw0.in_dim, _p(lw0.b), c0, n_h, _p(hvec), _p(self.b0), st), "mp_tr_hoist_fwd")
         bs = [self.b0] + [lw.b for lw in lins[1:]]
         key = tuple(b.data_ptr() for b in bs)
         if key != self._btab_key:
             self._btab_key, self.btab = key, _table(bs, self.b0.device)
-        _chk(L.mp_tf_sdf_pack(_p(self.wtab), _p(self.btab), _p(self.wpack), _p(self.bias_all), st), "mp_tf_sdf_pack")
+        _chk(getattr(L, self._pack)(_p(self.wtab), _p(self.btab), _p(self.wpack), _p(self.bias_all), st), self._pack)
         return self
 
 
-def fused_sdf_state(net, lins=None):
+def fused_state(kind, net, lins=None):
+    """the network's FusedState: one for its TrainState's shared layers, one standalone (created on first use)"""
     key = "_mp_tfuse_shared" if lins is not None else "_mp_tfuse"
     st = net.__dict__.get(key)
     if st is None or (lins is not None and st.lins is not lins):
-        st = net.__dict__[key] = FusedSDFState(net, lins)
+        st = net.__dict__[key] = FusedState(kind, net, lins)
     return st
 
 
-class ImplicitTrainFused(ImplicitTrainRev):
+fused_sdf_state = functools.partial(fused_state, "sdf")      # (the eval sampler's near-fp32 mode, tests, tools)
+
+
+class _FusedImplicit(_SdfEvaluator):
+    """What the two layer-fused ImplicitNet evaluators share: the state, the stash arena and its layout, feat [P+1][256] and
+    sdf [P+1] as their own tensors (one pad row, csrc/tfuse.hip), the value sweep's weight gradients."""
+    feat_ld = 256
+    dfeat_col0, dfeat_accumulate = 0, False
+
+    def _begin(self, kind, net, x, cond_vec, lins, grain, p_cap=None, cap_bytes=6 << 30):
+        L = hip.lib()
+        self.net, self.x, self.cond = net, x, cond_vec
+        self.P = P = x.shape[0]
+        self.E = E = net.embed_dim
+        self.fs = fs = fused_state(kind, net, lins).refresh(cond_vec)
+        self.lins = fs.lins
+        sizes = getattr(L, _FUSED_KINDS[kind][0])
+        arena = C.c_longlong(0)
+        _chk(sizes(P, C.byref(arena), None), "mp_tf_sizes")
+        cap = None
+        if p_cap is not None and p_cap >= P:
+            capv = C.c_longlong(0)
+            _chk(sizes(int(p_cap), C.byref(capv), None), "mp_tf_sizes")
+            cap = int(capv.value)
+        self.arena = _big_empty(int(arena.value), x.device, grain=grain, cap=cap, cap_bytes=cap_bytes)
+        # the arena's layout (floats): [P+1][256] tensors dZ_l, (V_l,) X_l, (dT_l), then the [P][E] Fourier features (and the
+        # gradient sweep's dG, G)
+        self.R1 = R1 = 256 * (P + 1)
+        self.t_dZ, self.t_V, self.t_X, self.t_dT, n_t = (0, 8, 15, 23, 46) if kind == "sdf" else (0, None, 7, None, 16)
+        self.o_IN, self.o_dG, self.o_G = n_t * R1, n_t * R1 + E * P, n_t * R1 + 2 * E * P
+        _chk(L.mp_tr_pe(_p(x), net.d_in, P, net.multires, 0, C.c_float(1.0), off(self.arena, self.o_IN), E, 0, hip.stream()), "mp_tr_pe")
+        self.feat = torch.empty(P + 1, 256, dtype=F32, device=x.device)  # columns 1.. of the reference's output (+ the pad row)
+        self.sdf = torch.empty(P + 1, dtype=F32, device=x.device)        # column 0
+        self.feat_ptr = _p(self.feat)
+
+    def _at(self, t0, l):
+        """device pointer to stash tensor l of the family starting at tensor t0 (t_dZ, t_V, t_X, t_dT)"""
+        return off(self.arena, (t0 + l) * self.R1)
+
+    def _skip_features(self):
+        # the skip connection re-injects the Fourier features into layer 4's input (times 1/sqrt 2): the last E columns of X_4
+        E = self.E
+        _chk(hip.lib().mp_tr_copy_cols(off(self.arena, self.o_IN), E, 0, self._at(self.t_X, 4), 256, 256 - E, self.P, E,
+                                       C.c_float(1.0 / math.sqrt(2.0)), 0, hip.stream()), "mp_tr_copy_cols")
+
+    @property
+    def out(self):
+        """the reference's [P][257] layout (column 0 = sdf), assembled on demand (tests; the trainer reads feat / sdf)"""
+        return torch.cat([self.sdf[:self.P, None], self.feat[:self.P]], 1)
+
+    def new_dfeat(self, n=0):
+        d = torch.empty(self.P, 256, dtype=F32, device=self.x.device)    # its own aligned matrix, WRITTEN by the colour net
+        if n < self.P:
+            d[n:].zero_()
+        return d
+
+    def _weight_grads(self, dfeat, tn_groups, gradient_sweep):
+        """dW_l += dZ_l^T X_l (value sweep; bias gradient = its column sums) [+ V_l^T dT_l (gradient sweep)]; returns d cond"""
+        P, E, lins = self.P, self.E, self.lins
+        lw0, lw8 = lins[0], lins[8]
+        dcond = _layer0_adjoint(lw0, self._at(self.t_dZ, 0), off(self.arena, self.o_IN), E, E, P, P, E, self.net.cond_dim, self.cond)
+        if gradient_sweep:
+            gemm_tn(self._at(self.t_V, 0), 256, off(self.arena, self.o_dG), E, _p(lw0.dW), lw0.in_dim, 256, E, P)
+        groups = tn_groups if tn_groups is not None else []
+        for l in range(1, 8):
+            lw = lins[l]                                # (layer 3: its 217 / 172 rows contracted as 256, see LinP)
+            rows = lw.dW_full.shape[0]
+            groups.append(tn_group(self._at(self.t_dZ, l), 256, self._at(self.t_X, l), 256, _p(lw.dW_full), lw.in_dim, rows, lw.in_dim,
+                                   P, _p(lw.db_full), P))
+            if gradient_sweep:
+                groups.append(tn_group(self._at(self.t_V, l), 256, self._at(self.t_dT, l), 256, _p(lw.dW_full), lw.in_dim, rows,
+                                       lw.in_dim, P))
+        groups.append(tn_group(_p(dfeat), 256, self._at(self.t_X, 8), 256, off(lw8.dW, 256), 256, 256, 256, P, off(lw8.db, 1), P))
+        if tn_groups is None:
+            launch_tn_groups(groups)
+        return dcond
+
+
+class ImplicitTrainFused(_FusedImplicit):
     """ImplicitTrainRev's arithmetic (value sweep + gradient sweep, and the adjoint of both) on the LAYER-FUSED kernels of
     csrc/tfuse.hip: two launches instead of ~90 per person -- mp_tf_sdf_fwd (both forward sweeps) and mp_tf_sdf_bwd (the adjoint
     w.r.t. the activations) -- plus one weight-gradient contraction per layer over [dZ_l; V_l]^T [X_l; dT_l] (K = 2 P rows).
-    Same interface: self.out [P][257], self.grad [P][3], backward(dZ_last, dgrad) -> d cond.  The adjoint of the input points
-    (pose optimisation) is not produced here: TrainGraph takes ImplicitTrainRev when it is needed."""
+    The adjoint of the input points (pose optimisation) is not produced here: sdf_evaluator takes ImplicitTrainRev when it is
+    needed."""
 
     def __init__(self, net, x, cond_vec, lins=None, p_cap=None, cap_bytes=6 << 30):
         """p_cap: the largest P this caller can ever pass (all rays hit the body): the stash is then sized for it, i.e. the SAME
@@ -644,199 +771,79 @@ class ImplicitTrainFused(ImplicitTrainRev):
         number of persons whose stashes are alive together: a crowded scene must not hold n_persons x the all-rays-hit arena)"""
         L, st = hip.lib(), hip.stream()
         assert fused_sdf_supported(net)
-        self.net, self.x, self.cond = net, x, cond_vec
-        self.P = P = x.shape[0]
-        self.E = E = net.embed_dim
-        dev = x.device
-        self.fs = fs = fused_sdf_state(net, lins).refresh(cond_vec)
-        self.lins, self.nl = fs.lins, len(fs.lins)
-        arena = C.c_longlong(0)
-        _chk(L.mp_tf_sdf_sizes(P, C.byref(arena), None), "mp_tf_sdf_sizes")
-        cap = None
-        if p_cap is not None and p_cap >= P:
-            capv = C.c_longlong(0)
-            _chk(L.mp_tf_sdf_sizes(int(p_cap), C.byref(capv), None), "mp_tf_sdf_sizes")
-            cap = int(capv.value)
-        self.arena = _big_empty(int(arena.value), dev, cap=cap, cap_bytes=cap_bytes)
-        R1 = 256 * (P + 1)                               # every [P][256] stash tensor carries one pad row (csrc/tfuse.hip)
-        self.o_dZ = lambda l: l * R1
-        self.o_V = lambda l: (8 + l) * R1
-        self.o_X = lambda l: (15 + l) * R1
-        self.o_dT = lambda l: (23 + l) * R1
-        self.o_IN, self.o_dG, self.o_G = 46 * R1, 46 * R1 + E * P, 46 * R1 + 2 * E * P
-        r2 = 1.0 / math.sqrt(2.0)
-        _chk(L.mp_tr_pe(_p(x), 3, P, net.multires, 0, C.c_float(1.0), off(self.arena, self.o_IN), E, 0, st), "mp_tr_pe")
-        self.feat = torch.empty(P + 1, 256, dtype=F32, device=dev)  # columns 1.. of the reference's output (+ the pad row)
-        self.sdf = torch.empty(P + 1, dtype=F32, device=dev)        # column 0
+        self._begin("sdf", net, x, cond_vec, lins, 1 << 26, p_cap, cap_bytes)
+        fs, P, E = self.fs, self.P, self.E
+        self.nl = len(fs.lins)
         self.w8 = fs.lins[8].W                          # row 0 = the sdf row of the last layer
         _chk(L.mp_tf_sdf_fwd(_p(fs.wpack), _p(fs.bias_all), _p(self.w8), _p(self.arena), P, _p(self.feat), _p(self.sdf), st),
              "mp_tf_sdf_fwd")
-        # the skip connection re-injects the Fourier features into layer 4's input (times 1/sqrt 2): columns 217.. of X_4
-        _chk(L.mp_tr_copy_cols(off(self.arena, self.o_IN), E, 0, off(self.arena, self.o_X(4)), 256, 256 - E, P, E, C.c_float(r2), 0,
-                               st), "mp_tr_copy_cols")
-        self.grad = torch.empty(P, 3, dtype=F32, device=dev)
+        self._skip_features()
+        self.grad = torch.empty(P, 3, dtype=F32, device=x.device)
         _chk(L.mp_tr_pe_grad_fwd(_p(x), P, net.multires, off(self.arena, self.o_G), E, _p(self.grad), st), "mp_tr_pe_grad_fwd")
 
-    @staticmethod
-    def _launch(groups):
-        if TRAIN_PRECISION == "bf16x3":
-            gemm_tn_grouped(groups)
-        else:                                   # exact-fp32 cross-check: one launch per contraction
-            for g in groups:
-                gemm_tn(C.c_void_p(g.A), g.lda, C.c_void_p(g.B), g.ldb, C.c_void_p(g.C), g.ldc, g.M, g.N, g.K,
-                        C.c_void_p(g.colsum) if g.colsum else None, g.colsum_rows)
-
-    @property
-    def out(self):
-        """the reference's [P][257] layout (column 0 = sdf), assembled on demand (tests; the trainer reads feat / sdf)"""
-        return torch.cat([self.sdf[:self.P, None], self.feat[:self.P]], 1)
-
     def backward(self, dfeat, dsdf, dgrad, want_dx=False, tn_groups=None):
-        """dfeat [P][256], dsdf [P], dgrad [P][3] -> dW / db of every layer; returns d cond.  tn_groups (a list): the aligned
-        weight-gradient contractions are appended to it instead of launched (the caller launches them grouped)"""
         assert not want_dx, "the fused SDF kernels do not produce the adjoint of the input points"
+        assert dfeat.shape[1] == 256
         L, st = hip.lib(), hip.stream()
-        net, P, E, lins, fs, A = self.net, self.P, self.E, self.lins, self.fs, self.arena
-        dev = dfeat.device
-        r2 = 1.0 / math.sqrt(2.0)
+        net, P, E, fs, A = self.net, self.P, self.E, self.fs, self.arena
         dG = off(A, self.o_dG)
         _chk(L.mp_tr_pe_grad_bwd(_p(self.x), P, net.multires, _p(dgrad), off(A, self.o_G), E, dG, E, None, st), "mp_tr_pe_grad_bwd")
-        lw8 = lins[8]                                   # the sdf row's gradient goes straight into row 0 of dW_8 / db_8
+        lw8 = self.lins[8]                              # the sdf row's gradient goes straight into row 0 of dW_8 / db_8
         _chk(L.mp_tf_sdf_bwd(_p(fs.wpack), _p(self.w8), _p(A), P, _p(dfeat), _p(dsdf), _p(lw8.dW), _p(lw8.db), st), "mp_tf_sdf_bwd")
-        _chk(L.mp_tr_copy_cols(dG, E, 0, off(A, self.o_dT(4)), 256, 256 - E, P, E, C.c_float(r2), 0, st), "mp_tr_copy_cols")
-        # weight gradients  dW_l += dZ_l^T X_l (value sweep; bias gradient = its column sums) + V_l^T dT_l (gradient sweep)
-        lw0 = lins[0]
-        db0 = _zeros(256, device=dev)        # layer 0's bias gradient of THIS evaluation (see ImplicitTrain.backward)
-        gemm_tn(off(A, self.o_dZ(0)), 256, off(A, self.o_IN), E, _p(lw0.dW), lw0.in_dim, 256, E, P, _p(db0), P)
-        lw0.db.add_(db0)
-        gemm_tn(off(A, self.o_V(0)), 256, dG, E, _p(lw0.dW), lw0.in_dim, 256, E, P)
-        groups = tn_groups if tn_groups is not None else []
-        for l in range(1, 8):
-            lw = lins[l]                                # (layer 3: 217 rows contracted as 256, see LinP)
-            rows = lw.dW_full.shape[0]
-            groups.append(tn_group(off(A, self.o_dZ(l)), 256, off(A, self.o_X(l)), 256, _p(lw.dW_full), lw.in_dim, rows, lw.in_dim, P,
-                                   _p(lw.db_full), P))
-            groups.append(tn_group(off(A, self.o_V(l)), 256, off(A, self.o_dT(l)), 256, _p(lw.dW_full), lw.in_dim, rows, lw.in_dim, P))
-        groups.append(tn_group(_p(dfeat), 256, off(A, self.o_X(8)), 256, off(lw8.dW, 256), 256, 256, 256, P, off(lw8.db, 1), P))
-        if tn_groups is None:
-            self._launch(groups)
-        _chk(L.mp_tr_hoist_bwd(_p(db0), 256, lw0.in_dim, E, net.cond_dim, _p(self.cond), _p(lw0.dW), st), "mp_tr_hoist_bwd")
-        dcond = _zeros(net.cond_dim, device=dev)
-        gemm_tn(_p(db0), 1, off(lw0.W, E), lw0.in_dim, _p(dcond), net.cond_dim, 1, net.cond_dim, 256)
+        _chk(L.mp_tr_copy_cols(dG, E, 0, self._at(self.t_dT, 4), 256, 256 - E, P, E, C.c_float(1.0 / math.sqrt(2.0)), 0, st),
+             "mp_tr_copy_cols")
         self.dx = None
-        return dcond
+        return self._weight_grads(dfeat, tn_groups, gradient_sweep=True)
 
 
-def fused_bg_supported(net):
-    """the network shape the fused background kernels (csrc/tfuse.hip k_tf_bg_*) are specialised for: the shipped NeRF++ net"""
-    return (net.d_in == 4 and net.multires == 10 and list(net.skip_in) == [4] and net.num_layers - 1 == 9 and net.cond_dim == 32
-            and list(net.dims[1:-1]) == [256] * 8 and net.dims[-1] == 257 and not hasattr(net.lin0, "weight_g"))
-
-
-class FusedBGState:
-    """chunk stream, bias table and pointer tables of the fused background kernels for one ImplicitNet (LinP layers shared with the
-    TrainState, or its own)"""
-
-    def __init__(self, net, lins=None):
-        self.net = net
-        self.shared = lins is not None
-        self.lins = lins if self.shared else [LinP(l, pad_rows=256 if i == 3 else 0) for i, l in enumerate(net.layers())]
-        dev = self.lins[0].W.device
-        arena, pack = C.c_longlong(0), C.c_longlong(0)
-        _chk(hip.lib().mp_tf_bg_sizes(1, C.byref(arena), C.byref(pack)), "mp_tf_bg_sizes")
-        self.wpack = torch.empty(int(pack.value), dtype=torch.uint8, device=dev)
-        self.bias_all = torch.empty(9 * 288, dtype=F32, device=dev)
-        self.b0 = torch.empty(256, dtype=F32, device=dev)
-        self.wtab = _table([lw.W for lw in self.lins], dev)
-        self._btab_key, self.btab = None, None
-
-    def refresh(self, code):
-        L, st = hip.lib(), hip.stream()
-        net, lins = self.net, self.lins
-        if not self.shared:
-            for lw in lins:
-                lw.refresh()
-        lw0 = lins[0]
-        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), 256, lw0.in_dim, _p(lw0.b), net.embed_dim, net.cond_dim, _p(code), _p(self.b0), st),
-             "mp_tr_hoist_fwd")
-        bs = [self.b0] + [lw.b for lw in lins[1:]]
-        key = tuple(b.data_ptr() for b in bs)
-        if key != self._btab_key:
-            self._btab_key, self.btab = key, _table(bs, self.b0.device)
-        _chk(L.mp_tf_bg_pack(_p(self.wtab), _p(self.btab), _p(self.wpack), _p(self.bias_all), st), "mp_tf_bg_pack")
-        return self
-
-
-def fused_bg_state(net, lins=None):
-    key = "_mp_tfuse_shared" if lins is not None else "_mp_tfuse"
-    st = net.__dict__.get(key)
-    if st is None or (lins is not None and st.lins is not lins):
-        st = net.__dict__[key] = FusedBGState(net, lins)
-    return st
-
-
-class ImplicitTrainFusedBG:
+class ImplicitTrainFusedBG(_FusedImplicit):
     """ImplicitTrain(fwd=False)'s arithmetic for the background ImplicitNet on the layer-fused kernels (csrc/tfuse.hip
     mp_tf_bg_fwd / mp_tf_bg_bwd): the nine layers in one launch each way, the weight gradients as one contraction per layer.
-    x [P][4] (the inverted-sphere points), code (32,) the frame's latent row.  self.sdf [P+1], self.feat [P+1][256]."""
+    x [P][4] (the inverted-sphere points), code (32,) the frame's latent row."""
+    grad = None
 
     def __init__(self, net, x, code, lins=None):
-        L, st = hip.lib(), hip.stream()
         assert fused_bg_supported(net)
-        self.net, self.x, self.cond = net, x, code
-        self.P = P = x.shape[0]
-        self.E = E = net.embed_dim                       # 84
-        dev = x.device
-        self.fs = fs = fused_bg_state(net, lins).refresh(code)
-        self.lins = fs.lins
-        arena = C.c_longlong(0)
-        _chk(L.mp_tf_bg_sizes(P, C.byref(arena), None), "mp_tf_bg_sizes")
-        self.arena = A = _big_empty(int(arena.value), dev, grain=1 << 22)
-        R1 = 256 * (P + 1)
-        self.o_dZ = lambda l: l * R1
-        self.o_X = lambda l: (7 + l) * R1
-        self.o_IN = 16 * R1
-        _chk(L.mp_tr_pe(_p(x), 4, P, net.multires, 0, C.c_float(1.0), off(A, self.o_IN), E, 0, st), "mp_tr_pe")
-        self.feat = torch.empty(P + 1, 256, dtype=F32, device=dev)
-        self.sdf = torch.empty(P + 1, dtype=F32, device=dev)
-        _chk(L.mp_tf_bg_fwd(_p(fs.wpack), _p(fs.bias_all), _p(A), P, _p(self.feat), _p(self.sdf), st), "mp_tf_bg_fwd")
-        # the skip connection re-injects the Fourier features into layer 4's input (times 1/sqrt 2): columns 172.. of X_4
-        _chk(L.mp_tr_copy_cols(off(A, self.o_IN), E, 0, off(A, self.o_X(4)), 256, 256 - E, P, E, C.c_float(1.0 / math.sqrt(2.0)), 0,
-                               st), "mp_tr_copy_cols")
+        self._begin("bg", net, x, code, lins, 1 << 22)
+        fs = self.fs
+        _chk(hip.lib().mp_tf_bg_fwd(_p(fs.wpack), _p(fs.bias_all), _p(self.arena), self.P, _p(self.feat), _p(self.sdf), hip.stream()),
+             "mp_tf_bg_fwd")
+        self._skip_features()
 
-    def backward(self, dfeat, dsdf):
-        """dfeat [P][256], dsdf [P] -> dW / db of every layer; returns d code (the hoisted conditioning's adjoint)"""
-        L, st = hip.lib(), hip.stream()
-        net, P, E, lins, fs, A = self.net, self.P, self.E, self.lins, self.fs, self.arena
-        lw8 = lins[8]
-        _chk(L.mp_tf_bg_bwd(_p(fs.wpack), _p(lw8.W), _p(A), P, _p(dfeat), _p(dsdf), _p(lw8.dW), _p(lw8.db), st), "mp_tf_bg_bwd")
-        lw0 = lins[0]
-        db0 = _zeros(256, device=dfeat.device)      # layer 0's bias gradient of THIS evaluation (see ImplicitTrain.backward)
-        gemm_tn(off(A, self.o_dZ(0)), 256, off(A, self.o_IN), E, _p(lw0.dW), lw0.in_dim, 256, E, P, _p(db0), P)
-        lw0.db.add_(db0)
-        groups = []
-        for l in range(1, 8):
-            lw = lins[l]                                # (layer 3: 172 rows contracted as 256, see LinP)
-            rows = lw.dW_full.shape[0]
-            groups.append(tn_group(off(A, self.o_dZ(l)), 256, off(A, self.o_X(l)), 256, _p(lw.dW_full), lw.in_dim, rows, lw.in_dim, P,
-                                   _p(lw.db_full), P))
-        groups.append(tn_group(_p(dfeat), 256, off(A, self.o_X(8)), 256, off(lw8.dW, 256), 256, 256, 256, P, off(lw8.db, 1), P))
-        ImplicitTrainFused._launch(groups)
-        _chk(L.mp_tr_hoist_bwd(_p(db0), 256, lw0.in_dim, E, net.cond_dim, _p(self.cond), _p(lw0.dW), st), "mp_tr_hoist_bwd")
-        dcode = _zeros(net.cond_dim, device=dfeat.device)
-        gemm_tn(_p(db0), 1, off(lw0.W, E), lw0.in_dim, _p(dcode), net.cond_dim, 1, net.cond_dim, 256)
-        return dcode
-
-    def params(self):
-        return [p for lw in self.lins for p in lw.params()]
-
-    def param_grads(self):
-        return [g for lw in self.lins for g in lw.param_grads()]
+    def backward(self, dfeat, dsdf, dgrad=None, want_dx=False, tn_groups=None):
+        assert dgrad is None and not want_dx and dfeat.shape[1] == 256
+        lw8 = self.lins[8]
+        _chk(hip.lib().mp_tf_bg_bwd(_p(self.fs.wpack), _p(lw8.W), _p(self.arena), self.P, _p(dfeat), _p(dsdf), _p(lw8.dW), _p(lw8.db),
+                                    hip.stream()), "mp_tf_bg_bwd")
+        return self._weight_grads(dfeat, tn_groups, gradient_sweep=False)
 
 
-class RenderTrain:
-    """RenderingNet (networks.py:263-312): mode 'pose_no_view' (inputs XA = [x_c, n] (6), feat) or 'nerf_frame_encoding'
-    (XA = PE_4(view) (27), feat).  feat is read in place from the SDF net's last layer (ld 257, column 1..)."""
+# ----------------------------------------------------------------------------------------------------------------------
+# A colour network evaluated for training.  Two evaluators, one surface:
+#   (net, XA [n][na], feat_ptr, feat_ld, n, cond_vec, lins)      the features are read in place from the SDF evaluator
+#   .rgb [n][3]
+#   backward(drgb [n][3], dXA [n][na] (written), dfeat_ptr, dfeat_ld, feat_accumulate=True, tn_groups=None) -> d hoisted vector
+#                         d feat: rows [0, n) at dfeat_ptr, added into (feat_accumulate) or written; an SDF evaluator's
+#                         dfeat_target() says which
+#   dcond()               the adjoint of the pose conditioning through lin_pose (after backward)
+# colour_evaluator() chooses.
+# ----------------------------------------------------------------------------------------------------------------------
+class _ColourNet(_NetParams):
+    def _lin_pose_adjoint(self, dh, lp_w):
+        """lin_pose's own gradients from d pose8: dW = dh (x) cond, db = dh"""
+        dlp_w = _zeros(8, 69, device=dh.device)
+        _chk(hip.lib().mp_tr_hoist_bwd(_p(dh), 8, 69, 0, 69, _p(self.cond), _p(dlp_w), hip.stream()), "mp_tr_hoist_bwd")
+        self.extra_grads = [dlp_w, dh]
+        self._dcond = (lp_w, dh)
+
+    def dcond(self):
+        lp_w, dh = self._dcond
+        return torch.mv(lp_w.t(), dh)
+
+
+class RenderTrain(_ColourNet):
+    """RenderingNet (networks.py:263-312) layer by layer: mode 'pose_no_view' (inputs XA = [x_c, n] (6), feat) or
+    'nerf_frame_encoding' (XA = PE_4(view) (27), feat)."""
 
     def __init__(self, net, XA, feat_ptr, feat_ld, n, cond_vec, lins=None):
         L = hip.lib()
@@ -851,6 +858,7 @@ class RenderTrain:
         self.cond = cond_vec
         if self.pose_mode:
             lp = net.lin_pose
+            self.extra_params = [lp.weight, lp.bias]
             self.lp_w, self.lp_b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
             self.pose8 = torch.empty(8, dtype=F32, device=dev)
             _chk(L.mp_tr_hoist_fwd(_p(self.lp_w), 8, 69, _p(self.lp_b), 0, 69, _p(cond_vec), _p(self.pose8), hip.stream()),
@@ -879,9 +887,7 @@ class RenderTrain:
         self.rgb = torch.empty(n, 3, dtype=F32, device=dev)
         _chk(L.mp_tr_sigmoid_fwd(_p(self.H[-1]), n * 3, _p(self.rgb), hip.stream()), "mp_tr_sigmoid_fwd")
 
-    def backward(self, drgb, dXA, dfeat_ptr, dfeat_ld, feat_accumulate=True):
-        """drgb [n][3] -> dW/db, dXA [n][na] (written), d feat (+= into dfeat_ptr, or written with feat_accumulate=False);
-        returns d hoisted-vector"""
+    def backward(self, drgb, dXA, dfeat_ptr, dfeat_ld, feat_accumulate=True, tn_groups=None):
         L = hip.lib()
         n, dev = self.n, drgb.device
         nl = len(self.lins)
@@ -898,152 +904,69 @@ class RenderTrain:
             dZ = dZp
         lw0 = self.lins[0]
         o0 = lw0.out_dim
-        db0 = _zeros(o0, device=dev)                  # this evaluation's own bias gradient (see ImplicitTrain.backward)
-        gemm_tn(_p(dZ), o0, _p(self.XA), self.na, _p(lw0.dW), lw0.in_dim, o0, self.na, n, _p(db0), n)
-        lw0.db.add_(db0)
+        dh = _layer0_adjoint(lw0, _p(dZ), _p(self.XA), self.na, self.na, n, n, self.c_h0, self.n_h, self.hvec)
         gemm_tn(_p(dZ), o0, self.feat_ptr, self.feat_ld, off(lw0.dW, self.c_feat), lw0.in_dim, o0, 256, n)
-        _chk(L.mp_tr_hoist_bwd(_p(db0), o0, lw0.in_dim, self.c_h0, self.n_h, _p(self.hvec), _p(lw0.dW), hip.stream()),
-             "mp_tr_hoist_bwd")
-        dh = _zeros(self.n_h, device=dev)
-        gemm_tn(_p(db0), 1, off(lw0.W, self.c_h0), lw0.in_dim, _p(dh), self.n_h, 1, self.n_h, o0)
         # data gradients
         gemm_nt(_p(dZ), o0, _p(lw0.WT), o0, _p(dXA), self.na, n, self.na, o0)
         gemm_nt(_p(dZ), o0, off(lw0.WT, self.c_feat * o0), o0, dfeat_ptr, dfeat_ld, n, 256, o0, None, 0, accumulate=feat_accumulate)
-        self.extra_grads = []
         if self.pose_mode:
-            dlp_w = torch.zeros(8, 69, dtype=F32, device=dev)
-            _chk(L.mp_tr_hoist_bwd(_p(dh), 8, 69, 0, 69, _p(self.cond), _p(dlp_w), hip.stream()), "mp_tr_hoist_bwd")
-            self.extra_grads = [dlp_w, dh]
+            self._lin_pose_adjoint(dh, self.lp_w)
         return dh
 
-    def params(self):
-        ps = [self.net.lin_pose.weight, self.net.lin_pose.bias] if self.pose_mode else []
-        return ps + [p for lw in self.lins for p in lw.params()]
 
-    def param_grads(self):
-        return list(self.extra_grads) + [g for lw in self.lins for g in lw.param_grads()]
-
-
-def fused_col_supported(net):
-    """the RenderingNet shape the fused colour kernels of csrc/tfuse.hip are specialised for (the shipped foreground net)"""
-    return net.mode == "pose_no_view" and list(net.dims) == [270, 256, 256, 256, 256, 3]
-
-
-class FusedColState:
-    """chunk stream, bias table and pointer tables of the fused colour kernels for one RenderingNet (its LinP layers shared with
-    the TrainState, or its own)"""
-
-    def __init__(self, net, lins=None):
-        self.net = net
-        self.shared = lins is not None
-        self.lins = lins if self.shared else [LinP(l) for l in net.layers()]
-        dev = self.lins[0].W.device
-        stash, pack = C.c_longlong(0), C.c_longlong(0)
-        _chk(hip.lib().mp_tf_col_sizes(1, C.byref(stash), C.byref(pack)), "mp_tf_col_sizes")
-        self.stash_per_point = int(stash.value)
-        self.wpack = torch.empty(int(pack.value), dtype=torch.uint8, device=dev)
-        self.bias_all = torch.empty(5 * 288, dtype=F32, device=dev)
-        self.b0 = torch.empty(256, dtype=F32, device=dev)
-        self.pose8 = torch.empty(8, dtype=F32, device=dev)
-        self.wtab = _table([lw.W for lw in self.lins], dev)
-        self._btab_key, self.btab = None, None
-
-    def refresh(self, cond_vec):
-        L, st = hip.lib(), hip.stream()
-        net, lins = self.net, self.lins
-        if not self.shared:
-            for lw in lins:
-                lw.refresh()
-        lp = net.lin_pose
-        self.lp_w, self.lp_b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
-        _chk(L.mp_tr_hoist_fwd(_p(self.lp_w), 8, 69, _p(self.lp_b), 0, 69, _p(cond_vec), _p(self.pose8), st), "mp_tr_hoist_fwd")
-        lw0 = lins[0]
-        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), 256, lw0.in_dim, _p(lw0.b), 6, 8, _p(self.pose8), _p(self.b0), st), "mp_tr_hoist_fwd")
-        bs = [self.b0] + [lw.b for lw in lins[1:]]
-        key = tuple(b.data_ptr() for b in bs)
-        if key != self._btab_key:
-            self._btab_key, self.btab = key, _table(bs, self.b0.device)
-        _chk(L.mp_tf_col_pack(_p(self.wtab), _p(self.btab), _p(self.wpack), _p(self.bias_all), st), "mp_tf_col_pack")
-        return self
-
-
-def fused_col_state(net, lins=None):
-    key = "_mp_tfuse_shared" if lins is not None else "_mp_tfuse"
-    st = net.__dict__.get(key)
-    if st is None or (lins is not None and st.lins is not lins):
-        st = net.__dict__[key] = FusedColState(net, lins)
-    return st
-
-
-class RenderTrainFused:
+class RenderTrainFused(_ColourNet):
     """RenderTrain's arithmetic for the foreground colour net on the layer-fused kernels (csrc/tfuse.hip: mp_tf_col_fwd /
-    mp_tf_col_bwd): the five layers in one launch each way, the weight gradients as one contraction per layer.  feat [>= n][256]
-    (row stride 256: the fused SDF net's feature rows), XA [n][6]."""
+    mp_tf_col_bwd): the five layers in one launch each way, the weight gradients as one contraction per layer.  The features are
+    a contiguous [>= n][256] matrix (the fused SDF net's feature rows), XA [n][6]."""
 
-    def __init__(self, net, XA, feat, n, cond_vec, lins=None):
+    def __init__(self, net, XA, feat_ptr, feat_ld, n, cond_vec, lins=None):
         L, st = hip.lib(), hip.stream()
-        assert fused_col_supported(net) and feat.shape[1] == 256 and feat.is_contiguous()
-        self.net, self.n, self.XA, self.feat, self.cond = net, n, XA, feat, cond_vec
-        dev = XA.device
-        self.cs = cs = fused_col_state(net, lins).refresh(cond_vec)
+        assert fused_col_supported(net) and feat_ld == 256
+        self.net, self.n, self.XA, self.feat_ptr, self.cond = net, n, XA, feat_ptr, cond_vec
+        self.cs = cs = fused_state("col", net, lins).refresh(cond_vec)
         self.lins = cs.lins
+        self.extra_params = [net.lin_pose.weight, net.lin_pose.bias]
         stash = C.c_longlong(0)
         _chk(L.mp_tf_col_sizes(n, C.byref(stash), None), "mp_tf_col_sizes")
-        self.stash = _big_empty(int(stash.value), dev)
-        self.rgb = torch.empty(n, 3, dtype=F32, device=dev)
-        _chk(L.mp_tf_col_fwd(_p(cs.wpack), _p(cs.bias_all), _p(self.stash), _p(feat), _p(XA), n, _p(self.rgb), st), "mp_tf_col_fwd")
+        self.stash = _big_empty(int(stash.value), XA.device)
+        self.rgb = torch.empty(n, 3, dtype=F32, device=XA.device)
+        _chk(L.mp_tf_col_fwd(_p(cs.wpack), _p(cs.bias_all), _p(self.stash), feat_ptr, _p(XA), n, _p(self.rgb), st), "mp_tf_col_fwd")
 
-    def backward(self, drgb, dXA, dfeat, tn_groups=None):
-        """drgb [n][3] -> dW / db, dXA [n][6] and rows [0, n) of dfeat [.][256] (both written); returns d pose-embedding.
-        tn_groups: see ImplicitTrainFused.backward"""
+    def backward(self, drgb, dXA, dfeat_ptr, dfeat_ld, feat_accumulate=False, tn_groups=None):
+        assert not feat_accumulate and dfeat_ld == 256       # rows [0, n) of dfeat are written; see ImplicitTrainFused for tn_groups
         L, st = hip.lib(), hip.stream()
         n, lins, cs, S = self.n, self.lins, self.cs, self.stash
-        dev = drgb.device
         NL = 256 * (n + 1)                               # one pad row per stash tensor
-        dz4 = torch.empty(n, 3, dtype=F32, device=dev)
-        _chk(L.mp_tf_col_bwd(_p(cs.wpack), _p(S), _p(lins[4].W), _p(self.rgb), _p(drgb), n, _p(dfeat), _p(dXA), _p(dz4), st),
+        dz4 = torch.empty(n, 3, dtype=F32, device=drgb.device)
+        _chk(L.mp_tf_col_bwd(_p(cs.wpack), _p(S), _p(lins[4].W), _p(self.rgb), _p(drgb), n, dfeat_ptr, _p(dXA), _p(dz4), st),
              "mp_tf_col_bwd")
         H = lambda l: off(S, l * NL)
         dZ = lambda l: off(S, (4 + l) * NL)
         lw0 = lins[0]
-        db0 = _zeros(256, device=dev)                 # this evaluation's own bias gradient (see ImplicitTrain.backward)
-        gemm_tn(dZ(0), 256, _p(self.XA), 6, _p(lw0.dW), lw0.in_dim, 256, 6, n, _p(db0), n)
-        lw0.db.add_(db0)
+        # the hoisted pose embedding: dW_0[:, 6:14] += db_0 (x) pose8 ; d pose8 = W_0[:, 6:14]^T db_0
+        dh = _layer0_adjoint(lw0, dZ(0), _p(self.XA), 6, 6, n, n, 6, 8, cs.pose8)
         groups = tn_groups if tn_groups is not None else []
-        groups.append(tn_group(dZ(0), 256, _p(self.feat), 256, off(lw0.dW, 14), lw0.in_dim, 256, 256, n))
+        groups.append(tn_group(dZ(0), 256, self.feat_ptr, 256, off(lw0.dW, 14), lw0.in_dim, 256, 256, n))
         for l in range(1, 4):
             lw = lins[l]
             groups.append(tn_group(dZ(l), 256, H(l - 1), 256, _p(lw.dW), 256, 256, 256, n, _p(lw.db), n))
         if tn_groups is None:
-            ImplicitTrainFused._launch(groups)
+            launch_tn_groups(groups)
         lw4 = lins[4]
         gemm_tn(_p(dz4), 3, H(3), 256, _p(lw4.dW), 256, 3, 256, n, _p(lw4.db), n)
-        # the hoisted pose embedding: dW_0[:, 6:14] += db_0 (x) pose8 ; d pose8 = W_0[:, 6:14]^T db_0 ; then lin_pose's own gradients
-        _chk(L.mp_tr_hoist_bwd(_p(db0), 256, lw0.in_dim, 6, 8, _p(cs.pose8), _p(lw0.dW), st), "mp_tr_hoist_bwd")
-        dh = _zeros(8, device=dev)
-        gemm_tn(_p(db0), 1, off(lw0.W, 6), lw0.in_dim, _p(dh), 8, 1, 8, 256)
-        dlp_w = _zeros(8, 69, device=dev)
-        _chk(L.mp_tr_hoist_bwd(_p(dh), 8, 69, 0, 69, _p(self.cond), _p(dlp_w), st), "mp_tr_hoist_bwd")
-        self.extra_grads = [dlp_w, dh]
-        self.lp_w = cs.lp_w
+        self._lin_pose_adjoint(dh, cs.lp_w)
         return dh
-
-    def params(self):
-        return [self.net.lin_pose.weight, self.net.lin_pose.bias] + [p for lw in self.lins for p in lw.params()]
-
-    def param_grads(self):
-        return list(self.extra_grads) + [g for lw in self.lins for g in lw.param_grads()]
 
 
 # ======================================================================================================================
 # Training-mode Multiply.forward (multiply.py:174-588, `self.training` branches) as ONE autograd node
 # ======================================================================================================================
 N_EIKONAL = 512          # multiply.py:324
-ARENA_BUDGET_BYTES = int(__import__("os").environ.get("MP_TRAIN_ARENA_GB", "24")) << 30   # fixed-size SDF stashes of one iteration, all persons
+ARENA_BUDGET_BYTES = int(os.environ.get("MP_TRAIN_ARENA_GB", "24")) << 30   # fixed-size SDF stashes of one iteration, all persons
 # 'fused' (ImplicitTrainFused: layer-fused kernels, default) | 'reverse' (ImplicitTrainRev, layer by layer) | 'forward'
-SDF_TRAIN_MODE = __import__("os").environ.get("MP_SDF_TRAIN_MODE", "fused")
+SDF_TRAIN_MODE = os.environ.get("MP_SDF_TRAIN_MODE", "fused")
 # background ImplicitNet: 'fused' (ImplicitTrainFusedBG, default) | 'layerwise' (ImplicitTrain: the cross-check)
-BG_TRAIN_MODE = __import__("os").environ.get("MP_BG_TRAIN_MODE", "fused")
+BG_TRAIN_MODE = os.environ.get("MP_BG_TRAIN_MODE", "fused")
 
 
 ZERO_POSE_SAMPLES = 2000          # multiply.py:363
@@ -1115,6 +1038,32 @@ def make_draws(model, cx, gen=None):
     return draws
 
 
+def sdf_evaluator(net, x, cond_vec, lins, pose_grad, p_cap, cap_bytes):
+    """THE choice of the foreground SDF evaluator (SDF_TRAIN_MODE, TRAIN_PRECISION, pose_grad, the network's shape)"""
+    mode = SDF_TRAIN_MODE
+    if mode == "fused" and (pose_grad or TRAIN_PRECISION != "bf16x3" or not fused_sdf_supported(net)):
+        mode = "reverse"      # the fused kernels: split-bf16 arithmetic, the shipped network shape, no d x_c
+    if mode == "fused":
+        return ImplicitTrainFused(net, x, cond_vec, lins=lins, p_cap=p_cap, cap_bytes=cap_bytes)
+    if mode == "forward":
+        return ImplicitTrain(net, x, cond_vec, fwd=True, lins=lins)
+    return ImplicitTrainRev(net, x, cond_vec, lins=lins)
+
+
+def bg_evaluator(net, x, code, lins):
+    """THE choice of the background ImplicitNet's evaluator (BG_TRAIN_MODE, TRAIN_PRECISION, the network's shape)"""
+    if BG_TRAIN_MODE == "fused" and TRAIN_PRECISION == "bf16x3" and fused_bg_supported(net):
+        return ImplicitTrainFusedBG(net, x, code, lins=lins)       # the nine layers in one launch (csrc/tfuse.hip k_tf_bg_fwd)
+    return ImplicitTrain(net, x, code, fwd=False, lins=lins)
+
+
+def colour_evaluator(net, XA, it, n, cond_vec, lins):
+    """THE choice of a colour net's evaluator on the first n points of SDF evaluator `it`: the fused kernels read a contiguous
+    [.][256] feature matrix (which the fused SDF evaluators deliver) in split-bf16 arithmetic"""
+    fused = TRAIN_PRECISION == "bf16x3" and it.feat_ld == 256 and fused_col_supported(net)
+    return (RenderTrainFused if fused else RenderTrain)(net, XA, it.feat_ptr, it.feat_ld, n, cond_vec, lins=lins)
+
+
 class TrainGraph:
     """Everything one training forward keeps for its backward."""
 
@@ -1125,19 +1074,16 @@ class TrainGraph:
         self.model, self.cx, self.input, self.cond_zero, self.draws = model, cx, input, cond_zero, draws
         self.surface_flags, self.pose_grad, self.shard = surface_flags, pose_grad, shard
         self.ts = ts if ts is not None else train_state(model).begin()     # shared layers: weights resolved, accumulators zeroed
+        self.reg_items, self.reg_losses = [], (None, None)
+        self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the regularisers (pose optimisation)
+        self.reg_surf = {}              # person -> (d tfs [24][16], d posed vertices [V][3]) of the surface term (pose optimisation)
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def run(self):
-        m, cx, L = self.model, self.cx, hip.lib()
-        dev, R, dirs, pose, beta = cx["dev"], cx["R"], cx["dirs"], cx["pose"], cx["beta"]
-        st = hip.stream()
-        f32 = dict(dtype=F32, device=dev)
+        m, cx = self.model, self.cx
         rs = m.ray_sampler
-        NZ = rs.N_samples + rs.N_samples_extra + 2
-        S = NZ - 1
+        self.NZ = rs.N_samples + rs.N_samples_extra + 2
         persons = cx["persons"]
-        self.fg = {}
-        z_l, sdf_l, rgb_l, nrm_l, inv_l = [], [], [], [], []
         if self.cond_zero:                                            # multiply.py:271-273
             for p in persons:
                 cx["per"][p]["cond"] = torch.zeros_like(cx["per"][p]["cond"])
@@ -1149,215 +1095,204 @@ class TrainGraph:
             sampled = m._sample_persons(cx, {p: self.draws["person"][p] for p in todo}, persons=todo) if todo else {}
         finally:
             m.__dict__["_mp_in_train_graph"] = False
-        for n, p in enumerate(persons):
-            pp = cx["per"][p]
-            dr = self.draws["person"][p]
-            Rp = max(int(cx["n_hit"][n]), 1)
-            imp, ren, dfm = m.foreground_implicit_network_list[p], m.foreground_rendering_network_list[p], m.deformer_list[p]
-            server = m.smpl_server_list[p]
-            skin_w = server.tables.lbs_weights
-            if dr.get("z_given") is not None:
-                # depths handed in by the caller instead of sampled here (the sampler runs without gradients in the reference,
-                # ray_sampler.py:86-87): lets a test drive everything downstream from an INDEPENDENT sampler's depths
-                zfinal, iters, wcount = dr["z_given"].to(dev).float().contiguous(), None, None
-                assert zfinal.shape == (Rp, NZ), f"z_given of person {p}: {tuple(zfinal.shape)} != {(Rp, NZ)}"
-            else:
-                zfinal, iters, wcount = sampled[p]
-            npts = Rp * S
-            E = N_EIKONAL
-            Pt = npts + E
-            X = torch.empty(Pt, 3, **f32)                             # canonical points: samples, then eikonal points
-            # the nearest POSED vertex of every sample: the pose adjoint needs it, and it seeds the canonical nearest-vertex search
-            # of the Jacobian (csrc/geom.hip k_warp_jacobian: its canonical distance is a tight, exact search radius -- the
-            # unseeded search opens every cluster: 228 us instead of ~30 per person)
-            nn_posed = torch.empty(npts, dtype=torch.int32, device=dev)
-            nn_cano = torch.empty(npts, dtype=torch.int32, device=dev) if self.pose_grad else None
-            # (a training batch's rays are random pixels: the warp first groups the samples by their nearest vertex cluster)
-            bin_work = torch.empty(int(L.mp_warp_bin_work_bytes(npts)), dtype=torch.uint8, device=dev)
-            _chk(L.mp_warp_inverse_shade(_p(dirs), _p(pose), _p(pp["hit_index"]), _p(pp["count"]), _p(zfinal), NZ, S, Rp,
-                                         _p(pp["vsorted"]), _p(pp["cbound"]), _p(pp["btab"]), 0, _p(beta),
-                                         _p(X), None, None, None, None, None, _p(nn_posed), _p(bin_work), st), "mp_warp_inverse_shade")
-            jinv = torch.empty(npts, 9, **f32)
-            _chk(L.mp_warp_jacobian(_p(X), None, None, 0, 0, npts, _p(dfm.vsorted_c), _p(dfm.cbound_c), _p(pp["btab"]),
-                                    _p(jinv), _p(nn_cano), _p(nn_posed), _p(dfm.verts_c_flat), st), "mp_warp_jacobian")
-            flags = None
-            if self.surface_flags:        # multiply.py:311-315: in / off-surface rays w.r.t. the current canonical mesh
-                fv = m.mesh_face_vertices_list[p].detach().reshape(-1, 9).to(dev).float().contiguous()
-                sd = torch.empty(npts, **f32)
-                _chk(L.mp_mesh_signed_distance(_p(X), npts, _p(fv), fv.shape[0], _p(sd), st), "mp_mesh_signed_distance")
-                off_p = torch.empty(Rp, dtype=torch.uint8, device=dev); in_p = torch.empty(Rp, dtype=torch.uint8, device=dev)
-                _chk(L.mp_mesh_ray_flags(_p(sd), Rp, S, C.c_float(m.threshold), _p(off_p), _p(in_p), st), "mp_mesh_ray_flags")
-                flags = (off_p.bool(), in_p.bool(), sd)
-            # eikonal points near the canonical surface (multiply.py:322-327, sampler.py:84-108 with global_ratio 0)
-            vc = server.verts_c.reshape(-1, 3)
-            X[npts:] = vc[dr["eik_idx"]] + dr["eik_noise"] * m.sampler.local_sigma
-            mode = SDF_TRAIN_MODE
-            if mode == "fused" and (self.pose_grad or TRAIN_PRECISION != "bf16x3" or not fused_sdf_supported(imp)):
-                mode = "reverse"      # the fused kernels: split-bf16 arithmetic, the shipped network shape, no d x_c
-            rev = mode != "forward"
-            li, lr = self.ts.lins[id(imp)], self.ts.lins[id(ren)]
-            if mode == "fused":
-                # all persons' stashes live from forward to backward: the fixed all-rays-hit size only while the sum stays in budget
-                it = ImplicitTrainFused(imp, X, pp["cond"], lins=li, p_cap=R * S + E,
-                                        cap_bytes=min(6 << 30, ARENA_BUDGET_BYTES // max(len(persons), 1)))
-            else:
-                it = ImplicitTrainRev(imp, X, pp["cond"], lins=li) if rev else ImplicitTrain(imp, X, pp["cond"], fwd=True, lins=li)
-            gptr = _p(it.grad) if rev else None
-            fusedp = mode == "fused"     # the fused kernels hand the last layer over as feat [Pt][256] + sdf [Pt], not [Pt][257]
-            XA = torch.empty(npts, 6, **f32); nrm = torch.empty(npts, 3, **f32)
-            sdf = it.sdf[:npts] if fusedp else torch.empty(npts, **f32)
-            z8 = None if fusedp else _p(it.out)
-            _chk(L.mp_tr_shade_in_fwd(z8, Pt, npts, _p(X), _p(jinv), _p(XA), _p(nrm), None if fusedp else _p(sdf), gptr, st),
-                 "mp_tr_shade_in_fwd")
-            gth = torch.empty(E, 3, **f32)
-            _chk(L.mp_tr_eik_fwd(z8, Pt, npts, E, _p(gth), gptr, st), "mp_tr_eik_fwd")
-            if fusedp and fused_col_supported(ren):
-                rt = RenderTrainFused(ren, XA, it.feat, npts, pp["cond"], lins=lr)
-            else:
-                rt = RenderTrain(ren, XA, _p(it.feat), 256, npts, pp["cond"], lins=lr) if fusedp else \
-                    RenderTrain(ren, XA, off(it.out, 1), 257, npts, pp["cond"], lins=lr)
-            self.fg[p] = dict(it=it, rt=rt, X=X, jinv=jinv, XA=XA, sdf=sdf, nrm=nrm, gth=gth, zfinal=zfinal, iters=iters,
-                              wcount=wcount, npts=npts, Pt=Pt, Rp=Rp, flags=flags, nn_posed=nn_posed,
-                              nn_cano=nn_cano)
-            z_l.append(zfinal); sdf_l.append(sdf); rgb_l.append(rt.rgb); nrm_l.append(nrm); inv_l.append(pp["inv_index"])
-
-        self.reg_items, self.reg_losses = [], (None, None)
+        self.fg = {}
+        local = [self._person_forward(n, p, sampled.get(p)) for n, p in enumerate(persons)]
         if m.smpl_surface_weight > 0 or m.zero_pose_weight > 0:
             self._regularisers_forward()
-        all_persons = list(persons)
-        self.remote = {}
-        s0, s1 = 0, R
+        # the composited persons, in person order: one record each, the same fields whether this rank evaluated the person or not
+        self.all_persons, self.composited, self.ray_slice = list(persons), local, (0, cx["R"])
         if self.shard is not None:
-            world, rank = self.shard
-            P_total = int(self.input["smpl_trans"].shape[1])
-            all_persons = list(range(P_total))
-            n_slot = (P_total + world - 1) // world
-            E = N_EIKONAL
-            width = NZ + 7 * S + 3                                   # z, sdf, rgb3, nrm3 per sample; hit, off, in flags
-            send = torch.zeros(n_slot, R * width + E * 3, **f32)
-            for j, p in enumerate(persons):
-                f, pp = self.fg[p], cx["per"][p]
-                n_hit = int(cx["n_hit"][j])
-                rows = pp["hit_index"][:n_hit].long()
-                dense = torch.zeros(R, width, **f32)
-                dense[rows, :NZ] = f["zfinal"][:n_hit]
-                dense[rows, NZ:NZ + S] = f["sdf"][:n_hit * S].reshape(n_hit, S)
-                dense[rows, NZ + S:NZ + 4 * S] = f["rt"].rgb[:n_hit * S].reshape(n_hit, 3 * S)
-                dense[rows, NZ + 4 * S:NZ + 7 * S] = f["nrm"][:n_hit * S].reshape(n_hit, 3 * S)
-                dense[rows, NZ + 7 * S] = 1.0
-                if f["flags"] is not None:
-                    dense[rows, NZ + 7 * S + 1] = f["flags"][0][:n_hit].float()
-                    dense[rows, NZ + 7 * S + 2] = f["flags"][1][:n_hit].float()
-                send[j, :R * width] = dense.reshape(-1)
-                send[j, R * width:] = f["gth"].reshape(-1)
-            bufs = [torch.empty_like(send) for _ in range(world)]
-            dist.all_gather(bufs, send)                               # THE exchange step of the forward
-            ar = torch.arange(R, device=dev, dtype=torch.int32)
-            for p in all_persons:
-                if p in self.fg:
-                    continue
+            self._exchange(local)
+        self.bg_rgb = self._background_forward()
+        return self._composite()
+
+    def _person_forward(self, n, p, sampled):
+        """person p (the n-th of this call): canonical points of its samples, SDF net, normals, colour net -> its compositing record"""
+        m, cx, L, st = self.model, self.cx, hip.lib(), hip.stream()
+        dev, R, NZ = cx["dev"], cx["R"], self.NZ
+        f32 = dict(dtype=F32, device=dev)
+        S = NZ - 1
+        pp = cx["per"][p]
+        dr = self.draws["person"][p]
+        Rp = max(int(cx["n_hit"][n]), 1)
+        imp, ren, dfm = m.foreground_implicit_network_list[p], m.foreground_rendering_network_list[p], m.deformer_list[p]
+        server = m.smpl_server_list[p]
+        if dr.get("z_given") is not None:
+            # depths handed in by the caller instead of sampled here (the sampler runs without gradients in the reference,
+            # ray_sampler.py:86-87): lets a test drive everything downstream from an INDEPENDENT sampler's depths
+            zfinal, iters, wcount = dr["z_given"].to(dev).float().contiguous(), None, None
+            assert zfinal.shape == (Rp, NZ), f"z_given of person {p}: {tuple(zfinal.shape)} != {(Rp, NZ)}"
+        else:
+            zfinal, iters, wcount = sampled
+        npts = Rp * S
+        E = N_EIKONAL
+        Pt = npts + E
+        X = torch.empty(Pt, 3, **f32)                             # canonical points: samples, then eikonal points
+        # the nearest POSED vertex of every sample: the pose adjoint needs it, and it seeds the canonical nearest-vertex search
+        # of the Jacobian (csrc/geom.hip k_warp_jacobian: its canonical distance is a tight, exact search radius -- the
+        # unseeded search opens every cluster: 228 us instead of ~30 per person)
+        nn_posed = torch.empty(npts, dtype=torch.int32, device=dev)
+        nn_cano = torch.empty(npts, dtype=torch.int32, device=dev) if self.pose_grad else None
+        # (a training batch's rays are random pixels: the warp first groups the samples by their nearest vertex cluster)
+        bin_work = torch.empty(int(L.mp_warp_bin_work_bytes(npts)), dtype=torch.uint8, device=dev)
+        _chk(L.mp_warp_inverse_shade(_p(cx["dirs"]), _p(cx["pose"]), _p(pp["hit_index"]), _p(pp["count"]), _p(zfinal), NZ, S, Rp,
+                                     _p(pp["vsorted"]), _p(pp["cbound"]), _p(pp["btab"]), 0, _p(cx["beta"]),
+                                     _p(X), None, None, None, None, None, _p(nn_posed), _p(bin_work), st), "mp_warp_inverse_shade")
+        jinv = torch.empty(npts, 9, **f32)
+        _chk(L.mp_warp_jacobian(_p(X), None, None, 0, 0, npts, _p(dfm.vsorted_c), _p(dfm.cbound_c), _p(pp["btab"]),
+                                _p(jinv), _p(nn_cano), _p(nn_posed), _p(dfm.verts_c_flat), st), "mp_warp_jacobian")
+        flags = None
+        if self.surface_flags:        # multiply.py:311-315: in / off-surface rays w.r.t. the current canonical mesh
+            fv = m.mesh_face_vertices_list[p].detach().reshape(-1, 9).to(dev).float().contiguous()
+            sd = torch.empty(npts, **f32)
+            _chk(L.mp_mesh_signed_distance(_p(X), npts, _p(fv), fv.shape[0], _p(sd), st), "mp_mesh_signed_distance")
+            off_p = torch.empty(Rp, dtype=torch.uint8, device=dev); in_p = torch.empty(Rp, dtype=torch.uint8, device=dev)
+            _chk(L.mp_mesh_ray_flags(_p(sd), Rp, S, C.c_float(m.threshold), _p(off_p), _p(in_p), st), "mp_mesh_ray_flags")
+            flags = (off_p.bool(), in_p.bool(), sd)
+        # eikonal points near the canonical surface (multiply.py:322-327, sampler.py:84-108 with global_ratio 0)
+        vc = server.verts_c.reshape(-1, 3)
+        X[npts:] = vc[dr["eik_idx"]] + dr["eik_noise"] * m.sampler.local_sigma
+        # all persons' stashes live from forward to backward: the fixed all-rays-hit size only while the sum stays in budget
+        it = sdf_evaluator(imp, X, pp["cond"], self.ts.lins[id(imp)], self.pose_grad, p_cap=R * S + E,
+                           cap_bytes=min(6 << 30, ARENA_BUDGET_BYTES // max(len(cx["persons"]), 1)))
+        XA = torch.empty(npts, 6, **f32); nrm = torch.empty(npts, 3, **f32)
+        sdf = it.sdf[:npts]
+        # (sdf and d sdf / d x come from the evaluator as arrays of their own: the kernels' "no Z8" form)
+        _chk(L.mp_tr_shade_in_fwd(None, Pt, npts, _p(X), _p(jinv), _p(XA), _p(nrm), None, _p(it.grad), st), "mp_tr_shade_in_fwd")
+        gth = torch.empty(E, 3, **f32)
+        _chk(L.mp_tr_eik_fwd(None, Pt, npts, E, _p(gth), _p(it.grad), st), "mp_tr_eik_fwd")
+        rt = colour_evaluator(ren, XA, it, npts, pp["cond"], self.ts.lins[id(ren)])
+        self.fg[p] = dict(it=it, rt=rt, X=X, jinv=jinv, XA=XA, sdf=sdf, nrm=nrm, gth=gth, zfinal=zfinal, iters=iters,
+                          wcount=wcount, npts=npts, Pt=Pt, Rp=Rp, flags=flags, nn_posed=nn_posed, nn_cano=nn_cano)
+        # rows of z / sdf / rgb / nrm = the person's hit rays `rays`, found per ray through inv; hit (a mask over all rays) only
+        # where the rows are all rays (_exchange); dsdf_rows: rows of the d sdf vector the backward hands to the SDF evaluator
+        return dict(z=zfinal, sdf=sdf, rgb=rt.rgb, nrm=nrm, inv=pp["inv_index"], gth=gth, rays=pp["hit_index"][:Rp], hit=None,
+                    off=flags[0] if flags else None, inn=flags[1] if flags else None, dsdf_rows=Pt)
+
+    def _exchange(self, local):
+        """person-sharded: THE exchange step of the forward.  Every rank's persons travel as dense per-ray rows; the persons of
+        other ranks become records of R rows each (nothing of theirs is differentiated here: their owners compute the same
+        compositing adjoint).  Also this rank's ray slice of the background branch."""
+        cx = self.cx
+        dev, R, NZ = cx["dev"], cx["R"], self.NZ
+        f32 = dict(dtype=F32, device=dev)
+        S, E = NZ - 1, N_EIKONAL
+        world, rank = self.shard
+        P_total = int(self.input["smpl_trans"].shape[1])
+        n_slot = (P_total + world - 1) // world
+        width = NZ + 7 * S + 3                                   # z, sdf, rgb3, nrm3 per sample; hit, off, in flags
+        send = torch.zeros(n_slot, R * width + E * 3, **f32)
+        for j, rec in enumerate(local):
+            n_hit = int(cx["n_hit"][j])
+            rows = rec["rays"][:n_hit].long()
+            dense = torch.zeros(R, width, **f32)
+            dense[rows, :NZ] = rec["z"][:n_hit]
+            dense[rows, NZ:NZ + S] = rec["sdf"][:n_hit * S].reshape(n_hit, S)
+            dense[rows, NZ + S:NZ + 4 * S] = rec["rgb"][:n_hit * S].reshape(n_hit, 3 * S)
+            dense[rows, NZ + 4 * S:NZ + 7 * S] = rec["nrm"][:n_hit * S].reshape(n_hit, 3 * S)
+            dense[rows, NZ + 7 * S] = 1.0
+            if rec["off"] is not None:
+                dense[rows, NZ + 7 * S + 1] = rec["off"][:n_hit].float()
+                dense[rows, NZ + 7 * S + 2] = rec["inn"][:n_hit].float()
+            send[j, :R * width] = dense.reshape(-1)
+            send[j, R * width:] = rec["gth"].reshape(-1)
+        bufs = [torch.empty_like(send) for _ in range(world)]
+        dist.all_gather(bufs, send)
+        ar = torch.arange(R, device=dev, dtype=torch.int32)
+        mine = dict(zip(cx["persons"], local))
+        self.all_persons, self.composited = list(range(P_total)), []
+        for p in self.all_persons:
+            rec = mine.get(p)
+            if rec is None:
                 blk = bufs[p % world][p // world]
                 d = blk[:R * width].reshape(R, width)
                 hit = d[:, NZ + 7 * S] > 0.5
-                self.remote[p] = dict(z=d[:, :NZ].contiguous(), sdf=d[:, NZ:NZ + S].contiguous(),
-                                      rgb=d[:, NZ + S:NZ + 4 * S].contiguous(), nrm=d[:, NZ + 4 * S:NZ + 7 * S].contiguous(),
-                                      inv=torch.where(hit, ar, torch.full_like(ar, -1)).contiguous(), hit=hit,
-                                      off=d[:, NZ + 7 * S + 1] > 0.5, inn=d[:, NZ + 7 * S + 2] > 0.5,
-                                      gth=blk[R * width:].reshape(E, 3).contiguous())
-            z_l, sdf_l, rgb_l, nrm_l, inv_l = [], [], [], [], []
-            for p in all_persons:
-                if p in self.fg:
-                    f = self.fg[p]
-                    z_l.append(f["zfinal"]); sdf_l.append(f["sdf"]); rgb_l.append(f["rt"].rgb); nrm_l.append(f["nrm"])
-                    inv_l.append(cx["per"][p]["inv_index"])
-                else:
-                    r = self.remote[p]
-                    z_l.append(r["z"]); sdf_l.append(r["sdf"]); rgb_l.append(r["rgb"]); nrm_l.append(r["nrm"]); inv_l.append(r["inv"])
-            n_slice = (R + world - 1) // world
-            s0, s1 = min(R, rank * n_slice), min(R, (rank + 1) * n_slice)
-            self.n_slice = n_slice
-        self.all_persons, self.ray_slice = all_persons, (s0, s1)
+                # (a ray the person misses is off its surface and not inside it: multiply.py:549-557)
+                rec = dict(z=d[:, :NZ].contiguous(), sdf=d[:, NZ:NZ + S].contiguous(), rgb=d[:, NZ + S:NZ + 4 * S].contiguous(),
+                           nrm=d[:, NZ + 4 * S:NZ + 7 * S].contiguous(), inv=torch.where(hit, ar, torch.full_like(ar, -1)).contiguous(),
+                           gth=blk[R * width:].reshape(E, 3).contiguous(), rays=ar, hit=hit,
+                           off=~hit | (d[:, NZ + 7 * S + 1] > 0.5), inn=hit & (d[:, NZ + 7 * S + 2] > 0.5), dsdf_rows=R * S)
+            self.composited.append(rec)
+        self.n_slice = n_slice = (R + world - 1) // world
+        self.ray_slice = (min(R, rank * n_slice), min(R, (rank + 1) * n_slice))
 
-        # ---- background (multiply.py:482-484, 514-539); depths jittered per ray in training (ray_sampler.py:32-40)
+    def _background_forward(self):
+        """the background branch (multiply.py:482-484, 514-539) on this rank's ray slice; depths jittered per ray in training
+        (ray_sampler.py:32-40).  -> bg_rgb [R][3] of all rays, or None without a frame index"""
+        m, cx, L, st = self.model, self.cx, hip.lib(), hip.stream()
+        dev, R, dirs = cx["dev"], cx["R"], cx["dirs"]
+        f32 = dict(dtype=F32, device=dev)
+        rs = m.ray_sampler
+        s0, s1 = self.ray_slice
         self.bg = None
-        bg_rgb = None
-        if self.input.get("idx", None) is not None:
-            key = "image_id" if "image_id" in self.input else "idx"
-            # the frame's row of the latent table, looked up ON THE DEVICE: int(<device tensor>) is a device -> host copy that
-            # waits for everything enqueued so far (the whole previous iteration), i.e. the host could never run ahead
-            w_lat = m.frame_latent_encoder.weight
-            self.frame = torch.as_tensor(self.input[key]).reshape(-1)[:1].to(w_lat.device, torch.long, non_blocking=True)
-            code = w_lat.detach().index_select(0, self.frame)[0].contiguous()
-            NB = rs.N_samples_inverse_sphere
-            Rb = s1 - s0                                              # this rank's rays of the background branch
-            bdirs = dirs[s0:s1].contiguous()
-            # stratified depths (ray_sampler.py:32-40): the bin edges are constants of (NB, bounding sphere) -- built once per model,
-            # already flipped and scaled, so that the iteration pays one fused multiply-add instead of ten small launches
-            strata = m.__dict__.get("_mp_bg_strata")
-            if strata is None or strata[0] != (NB, float(rs.scene_bounding_sphere), str(dev)):
-                t = torch.linspace(0.0, 1.0, NB, device=dev)[None]
-                mids = 0.5 * (t[:, 1:] + t[:, :-1])
-                upper = torch.cat([mids, t[:, -1:]], -1); lower = torch.cat([t[:, :1], mids], -1)
-                c = 1.0 / rs.scene_bounding_sphere
-                strata = m.__dict__["_mp_bg_strata"] = ((NB, float(rs.scene_bounding_sphere), str(dev)),
-                                                        torch.flip(lower * c, dims=[-1]).contiguous(),
-                                                        torch.flip((upper - lower) * c, dims=[-1]).contiguous())
-            # zbg = flip((lower + (upper - lower) u) / r) = flip(lower / r) + flip((upper - lower) / r) flip(u)
-            zbg = torch.addcmul(strata[1], strata[2], torch.flip(self.draws["bg_rand"][s0:s1], dims=[-1])).contiguous()
-            bg_rgb = torch.zeros(R, 3, **f32) if Rb != R else None
-            if Rb > 0:
-                pts = torch.empty(Rb * NB, 4, **f32)
-                cam = pose.reshape(4, 4)[:3, 3].contiguous()
-                _chk(L.mp_tr_bg_points(_p(bdirs), _p(cam), _p(zbg), Rb, NB, C.c_float(m.sdf_bounding_sphere), _p(pts), st),
-                     "mp_tr_bg_points")
-                bgnet = m.bg_implicit_network
-                fused_bg = BG_TRAIN_MODE == "fused" and TRAIN_PRECISION == "bf16x3" and fused_bg_supported(bgnet)
-                if fused_bg:       # the nine layers in one launch (csrc/tfuse.hip k_tf_bg_fwd)
-                    bit = ImplicitTrainFusedBG(bgnet, pts, code, lins=self.ts.lins[id(bgnet)])
-                else:
-                    bit = ImplicitTrain(bgnet, pts, code, fwd=False, lins=self.ts.lins[id(bgnet)])
-                drep = bdirs[:, None, :].expand(Rb, NB, 3).reshape(-1, 3).contiguous()
-                XAb = torch.empty(Rb * NB, 27, **f32)
-                _chk(L.mp_tr_pe(_p(drep), 3, Rb * NB, 4, 0, C.c_float(1.0), _p(XAb), 27, 0, st), "mp_tr_pe")
-                if fused_bg:
-                    brt = RenderTrain(m.bg_rendering_network, XAb, _p(bit.feat), 256, Rb * NB, code,
-                                      lins=self.ts.lins[id(m.bg_rendering_network)])
-                    sdfb = bit.sdf[:Rb * NB]
-                else:
-                    brt = RenderTrain(m.bg_rendering_network, XAb, off(bit.out, 1), 257, Rb * NB, code,
-                                      lins=self.ts.lins[id(m.bg_rendering_network)])
-                    sdfb = torch.empty(Rb * NB, **f32)
-                    _chk(L.mp_tr_copy_cols(_p(bit.out), 257, 0, _p(sdfb), 1, 0, Rb * NB, 1, C.c_float(1.0), 0, st),
-                         "mp_tr_copy_cols")
-                bg_slice = torch.empty(Rb, 3, **f32)
-                _chk(L.mp_tr_bg_comp_fwd(_p(sdfb), _p(brt.rgb), _p(zbg), Rb, NB, _p(bg_slice), st), "mp_tr_bg_comp_fwd")
-                if bg_rgb is None:
-                    bg_rgb = bg_slice                                 # the whole call's rays: no scatter into a zero image
-                else:
-                    bg_rgb[s0:s1] = bg_slice
-                self.bg = dict(it=bit, rt=brt, zbg=zbg, sdfb=sdfb, XAb=XAb, NB=NB, code=code, pts=pts, Rb=Rb)
-            if self.shard is not None:                                # every rank composites all rays
-                pad = torch.zeros(self.n_slice, 3, **f32)
-                pad[:Rb] = bg_rgb[s0:s1]
-                parts = [torch.empty_like(pad) for _ in range(self.shard[0])]
-                dist.all_gather(parts, pad)
-                bg_rgb = torch.cat(parts, 0)[:R].contiguous()
-        self.bg_rgb = bg_rgb
+        if self.input.get("idx", None) is None:
+            return None
+        key = "image_id" if "image_id" in self.input else "idx"
+        # the frame's row of the latent table, looked up ON THE DEVICE: int(<device tensor>) is a device -> host copy that
+        # waits for everything enqueued so far (the whole previous iteration), i.e. the host could never run ahead
+        w_lat = m.frame_latent_encoder.weight
+        self.frame = torch.as_tensor(self.input[key]).reshape(-1)[:1].to(w_lat.device, torch.long, non_blocking=True)
+        code = w_lat.detach().index_select(0, self.frame)[0].contiguous()
+        NB = rs.N_samples_inverse_sphere
+        Rb = s1 - s0                                              # this rank's rays of the background branch
+        bdirs = dirs[s0:s1].contiguous()
+        # stratified depths (ray_sampler.py:32-40): the bin edges are constants of (NB, bounding sphere) -- built once per model,
+        # already flipped and scaled, so that the iteration pays one fused multiply-add instead of ten small launches
+        strata = m.__dict__.get("_mp_bg_strata")
+        if strata is None or strata[0] != (NB, float(rs.scene_bounding_sphere), str(dev)):
+            t = torch.linspace(0.0, 1.0, NB, device=dev)[None]
+            mids = 0.5 * (t[:, 1:] + t[:, :-1])
+            upper = torch.cat([mids, t[:, -1:]], -1); lower = torch.cat([t[:, :1], mids], -1)
+            c = 1.0 / rs.scene_bounding_sphere
+            strata = m.__dict__["_mp_bg_strata"] = ((NB, float(rs.scene_bounding_sphere), str(dev)),
+                                                    torch.flip(lower * c, dims=[-1]).contiguous(),
+                                                    torch.flip((upper - lower) * c, dims=[-1]).contiguous())
+        # zbg = flip((lower + (upper - lower) u) / r) = flip(lower / r) + flip((upper - lower) / r) flip(u)
+        zbg = torch.addcmul(strata[1], strata[2], torch.flip(self.draws["bg_rand"][s0:s1], dims=[-1])).contiguous()
+        bg_rgb = torch.zeros(R, 3, **f32) if Rb != R else None
+        if Rb > 0:
+            rows = Rb * NB
+            pts = torch.empty(rows, 4, **f32)
+            cam = cx["pose"].reshape(4, 4)[:3, 3].contiguous()
+            _chk(L.mp_tr_bg_points(_p(bdirs), _p(cam), _p(zbg), Rb, NB, C.c_float(m.sdf_bounding_sphere), _p(pts), st),
+                 "mp_tr_bg_points")
+            bit = bg_evaluator(m.bg_implicit_network, pts, code, self.ts.lins[id(m.bg_implicit_network)])
+            drep = bdirs[:, None, :].expand(Rb, NB, 3).reshape(-1, 3).contiguous()
+            XAb = torch.empty(rows, 27, **f32)
+            _chk(L.mp_tr_pe(_p(drep), 3, rows, 4, 0, C.c_float(1.0), _p(XAb), 27, 0, st), "mp_tr_pe")
+            brt = colour_evaluator(m.bg_rendering_network, XAb, bit, rows, code, self.ts.lins[id(m.bg_rendering_network)])
+            sdfb = bit.sdf[:rows]
+            bg_slice = torch.empty(Rb, 3, **f32)
+            _chk(L.mp_tr_bg_comp_fwd(_p(sdfb), _p(brt.rgb), _p(zbg), Rb, NB, _p(bg_slice), st), "mp_tr_bg_comp_fwd")
+            if bg_rgb is None:
+                bg_rgb = bg_slice                                 # the whole call's rays: no scatter into a zero image
+            else:
+                bg_rgb[s0:s1] = bg_slice
+            self.bg = dict(it=bit, rt=brt, zbg=zbg, sdfb=sdfb, XAb=XAb, NB=NB, code=code, pts=pts, Rb=Rb)
+        if self.shard is not None:                                # every rank composites all rays
+            pad = torch.zeros(self.n_slice, 3, **f32)
+            pad[:Rb] = bg_rgb[s0:s1]
+            parts = [torch.empty_like(pad) for _ in range(self.shard[0])]
+            dist.all_gather(parts, pad)
+            bg_rgb = torch.cat(parts, 0)[:R].contiguous()
+        return bg_rgb
 
-        # ---- compositing (multiply.py:425-480, 544-545)
-        self.tabs = tuple(_table(ts, dev) for ts in (inv_l, z_l, sdf_l, rgb_l, nrm_l))
+    def _composite(self):
+        """compositing of all persons and the background (multiply.py:425-480, 544-545) -> the node's outputs"""
+        cx, L, bg_rgb = self.cx, hip.lib(), self.bg_rgb
+        dev, R = cx["dev"], cx["R"]
+        f32 = dict(dtype=F32, device=dev)
+        self.tabs = tuple(_table([rec[k] for rec in self.composited], dev) for k in ("inv", "z", "sdf", "rgb", "nrm"))
         t_inv, t_z, t_sdf, t_rgb, t_nrm = self.tabs
-        P = len(all_persons)
+        P = len(self.composited)
         rgb_values = torch.empty(R, 3, **f32); fg_rgb_values = torch.empty(R, 3, **f32)
         normal_values = torch.empty(R, 3, **f32); acc_map = torch.empty(R, **f32)
         acc_person = torch.empty(R, P, **f32); bg_T = torch.empty(R, **f32)
-        _chk(L.mp_composite(R, P, NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(t_nrm), _p(beta),
+        _chk(L.mp_composite(R, P, self.NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(t_nrm), _p(cx["beta"]),
                             _p(bg_rgb) if bg_rgb is not None else None, _p(rgb_values), _p(fg_rgb_values),
-                            _p(normal_values), _p(acc_map), _p(acc_person), _p(bg_T), st), "mp_composite")
-        grad_theta = torch.cat([self.fg[p]["gth"] if p in self.fg else self.remote[p]["gth"] for p in all_persons],
-                               0)[None]                                            # multiply.py:565
+                            _p(normal_values), _p(acc_map), _p(acc_person), _p(bg_T), hip.stream()), "mp_composite")
+        grad_theta = torch.cat([rec["gth"] for rec in self.composited], 0)[None]               # multiply.py:565
         self.bg_T = bg_T
-        self.NZ = NZ
         if self.reg_items:
             return (rgb_values, normal_values, acc_map, acc_person, grad_theta) + self.reg_losses
         return rgb_values, normal_values, acc_map, acc_person, grad_theta
@@ -1419,8 +1354,7 @@ class TrainGraph:
 
     def _regularisers_backward(self, d_ssl, d_zpl):
         dev = self.cx["dev"]
-        self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the regularisers (pose optimisation)
-        self.reg_surf = {}              # person -> (d tfs [24][16], d posed vertices [V][3]) of the surface term (pose optimisation)
+        self.reg_dcond, self.reg_surf = {}, {}
         L, st = hip.lib(), hip.stream()
         for item in self.reg_items:
             if item[0] == "surf":
@@ -1463,140 +1397,142 @@ class TrainGraph:
     # ---- backward -----------------------------------------------------------------------------------------------
     def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None):
         """-> {id(parameter): gradient}"""
-        m, cx, L = self.model, self.cx, hip.lib()
-        dev, R, beta = cx["dev"], cx["R"], cx["beta"]
-        st = hip.stream()
-        f32 = dict(dtype=F32, device=dev)
-        persons = cx["persons"]
-        all_persons = self.all_persons
+        m, dev = self.model, self.cx["dev"]
         self.ts.start_backward()                  # this sweep's own accumulators / gradient buffer (TrainState.start_backward)
-        if self.reg_items:
+        if self.reg_items:                        # before any finish_group retires a network's accumulators
             self._regularisers_backward(d_ssl, d_zpl)
-        P = len(all_persons)
-        S = self.NZ - 1
-        t_inv, t_z, t_sdf, t_rgb, _ = self.tabs
-        zp = self.zp = _ZP[0] = hip.ZeroPool(dev)          # this sweep's zero-initialised tensors: views of one zero-filled block
-        zero = lambda t, shape: zp.take(shape) if t is None else t.contiguous().float()
-        d_rgb_values = zero(d_rgb_values, (R, 3)); d_acc_map = zero(d_acc_map, (R,)); d_acc_person = zero(d_acc_person, (R, P))
-        # remote persons (person-sharded mode) get scratch rows: their owners compute the same compositing adjoint
-        # (a fused person's d sdf vector also covers its eikonal points, which no compositing term reaches: zeros)
-        dsdf_l = [zp.take((self.fg[p]["Pt"] if isinstance(self.fg[p]["it"], ImplicitTrainFused) else self.fg[p]["npts"])
-                          if p in self.fg else R * S) for p in all_persons]
-        drgb_l = [zp.take(self.fg[p]["npts"] if p in self.fg else R * S, 3) for p in all_persons]
-        d_bg_rgb = zp.take(R, 3)
-        d_beta = zp.take(1)
-        t_dsdf, t_drgb = _table(dsdf_l, dev), _table(drgb_l, dev)
-        _chk(L.mp_tr_composite_bwd(R, P, self.NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(beta),
-                                   _p(self.bg_rgb) if self.bg_rgb is not None else None, _p(d_rgb_values), _p(d_acc_map),
-                                   _p(d_acc_person), _p(t_dsdf), _p(t_drgb), _p(d_bg_rgb), _p(d_beta), st),
-             "mp_tr_composite_bwd")
-        grads = {}
-        self.pose_grads = {}
+        self.zp = _ZP[0] = hip.ZeroPool(dev)      # this sweep's zero-initialised tensors: views of one zero-filled block
+        dsdf_l, drgb_l, d_bg_rgb, d_beta = self._composite_backward(d_rgb_values, d_acc_map, d_acc_person)
+        self.grads, self.pose_grads = {}, {}
         # data-parallel training: buckets of retired gradients are all-reduced while the sweep goes on (parallel.BucketedGradientSync)
-        sync = getattr(m, "grad_bucket_sync", None)
+        sync = self.sync = getattr(m, "grad_bucket_sync", None)
         # the buckets retire in the order of THIS rank's persons: person-sharded ranks own different persons, so their bucket
         # sizes and counts differ and the collectives would mismatch -- that mode sums its shared gradients with PersonShardedGradSync
         assert sync is None or self.shard is None, "grad_bucket_sync (ray-/frame-sharded data parallelism) cannot be combined with shard="
-
-        def collect(obj):
-            for prm, g in zip(obj.params(), obj.param_grads()):
-                grads[id(prm)] = g if id(prm) not in grads else grads[id(prm)] + g
-
-        def retire(*objs):
-            if sync is not None:
-                prms = [prm for o in objs for prm in o.params()]
-                sync.retire(prms, [grads[id(prm)] for prm in prms])
-
-        for p in persons:
-            n = all_persons.index(p)                                  # position among the composited persons
-            f = self.fg[p]
-            it, rt, npts, Pt = f["it"], f["rt"], f["npts"], f["Pt"]
-            rev = isinstance(it, ImplicitTrainRev)
-            fusedp = isinstance(it, ImplicitTrainFused)
-            dgrad = zp.take(Pt, 3) if rev else None
-            dXA = torch.empty(npts, 6, **f32)
-            if fusedp:                 # d features as their own aligned matrix, written (not accumulated) by the colour net
-                dZ8 = None
-                dfeat = torch.empty(Pt, 256, **f32)
-                dfeat[npts:].zero_()   # the eikonal points have no colour path
-                tn_groups = []             # the person's aligned weight-gradient contractions: ONE grouped launch below
-                if isinstance(rt, RenderTrainFused):
-                    rt.backward(drgb_l[n], dXA, dfeat, tn_groups=tn_groups)
-                else:
-                    rt.backward(drgb_l[n], dXA, _p(dfeat), 256, feat_accumulate=False)
-            else:
-                dZ8 = torch.zeros(Pt if rev else 4 * Pt, 257, **f32)
-                rt.backward(drgb_l[n], dXA, off(dZ8, 1), 257)
-            djinv = torch.empty(npts, 9, **f32) if self.pose_grad else None
-            _chk(L.mp_tr_shade_in_bwd(None if fusedp else _p(it.out), Pt, npts, _p(f["jinv"]), _p(dXA), _p(dsdf_l[n]), None, _p(dZ8),
-                                      _p(djinv), _p(it.grad) if rev else None, _p(dgrad), st), "mp_tr_shade_in_bwd")
+        for p in self.cx["persons"]:
+            n = self.all_persons.index(p)                             # position among the composited persons
+            dgth = None
             if d_grad_theta is not None:
-                dg = d_grad_theta.reshape(-1, 3)[n * N_EIKONAL:(n + 1) * N_EIKONAL].contiguous().float()
-                _chk(L.mp_tr_eik_bwd(Pt, npts, N_EIKONAL, _p(dg), _p(dZ8), _p(dgrad), st), "mp_tr_eik_bwd")
-            if fusedp:
-                dcond = it.backward(dfeat, dsdf_l[n], dgrad, tn_groups=tn_groups)
-                ImplicitTrainFused._launch(tn_groups)
-            else:
-                dcond = it.backward(dZ8, dgrad, want_dx=self.pose_grad) if rev else it.backward(dZ8, want_dx=self.pose_grad)
-            self.ts.finish_group(p)                                   # one batched weight-norm adjoint for the person's two nets
-            collect(it); collect(rt)
-            retire(it, rt)
+                dgth = d_grad_theta.reshape(-1, 3)[n * N_EIKONAL:(n + 1) * N_EIKONAL].contiguous().float()
+            dcond, dXA, djinv = self._person_backward(p, dsdf_l[n], drgb_l[n], dgth)
             if self.pose_grad:
-                # x_c enters the SDF net (value + tangent rows) and the colour net (XA[:, :3]); the transforms also shape
-                # the normals through Jinv.  -> d tfs -> d (scale, transl, thetas, betas)   (multiply.py:196-206, 270)
-                pp = cx["per"][p]
-                server = m.smpl_server_list[p]
-                dxc = (it.dx[:npts] + dXA[:, :3]).contiguous()
-                dtfs = torch.zeros(24, 16, **f32)
-                _chk(L.mp_tr_warp_bwd(_p(f["X"]), _p(dxc), _p(f["jinv"]), _p(djinv), _p(f["nn_posed"]), _p(f["nn_cano"]),
-                                      npts, _p(server.tables.lbs_weights), _p(pp["tfs"]), _p(dtfs), st), "mp_tr_warp_bwd")
-                surf = getattr(self, "reg_surf", {}).get(p)
-                if surf is None:
-                    dprm = torch.empty(86, **f32)
-                    _chk(L.mp_smpl_pose_bwd(_p(server.tables.parents), _p(pp["prm"]), _p(server.tfs_c_inv),
-                                            _p(pp["rest_joints"]), _p(server.tables.j_shapedirs), _p(dtfs), _p(dprm), st),
-                         "mp_smpl_pose_bwd")
-                else:                                                    # + the surface term's posed vertices and transforms
-                    dprm = server.pose_backward(pp["prm"], dverts=surf[1], dtfs=dtfs + surf[0])
-                if not self.cond_zero:                                   # cond = smpl_pose[3:] / pi  (multiply.py:270)
-                    dc = dcond + torch.mv(rt.lp_w.t(), rt.extra_grads[1])
-                    if p in getattr(self, "reg_dcond", {}):             # + the regularisers' share (zero pose; surface, opt-in)
-                        dc = dc + self.reg_dcond[p]
-                    dprm[7:76] += dc / math.pi
-                self.pose_grads[p] = dprm
+                self._pose_backward(p, dcond, dXA, djinv)
         if self.bg is not None:
-            b = self.bg
-            bit, brt, NB, Rb = b["it"], b["rt"], b["NB"], b["Rb"]
-            rows = Rb * NB
-            s0, s1 = self.ray_slice
-            d_bg_slice = d_bg_rgb[s0:s1].contiguous()
-            dsdfb = torch.empty(rows, **f32); drgbb = torch.empty(rows, 3, **f32)
-            _chk(L.mp_tr_bg_comp_bwd(_p(b["sdfb"]), _p(brt.rgb), _p(b["zbg"]), Rb, NB, _p(d_bg_slice), _p(dsdfb), _p(drgbb),
-                                     st), "mp_tr_bg_comp_bwd")
-            dXAb = torch.empty(rows, 27, **f32)
-            if isinstance(bit, ImplicitTrainFusedBG):
-                dfeatb = torch.empty(rows, 256, **f32)         # written (not accumulated) by the colour net
-                dcode = brt.backward(drgbb, dXAb, _p(dfeatb), 256, feat_accumulate=False)
-                dcode = dcode + bit.backward(dfeatb, dsdfb)
-            else:
-                dZ8b = torch.zeros(rows, 257, **f32)
-                dcode = brt.backward(drgbb, dXAb, off(dZ8b, 1), 257)
-                _chk(L.mp_tr_copy_cols(_p(dsdfb), 1, 0, _p(dZ8b), 257, 0, rows, 1, C.c_float(1.0), 0, st), "mp_tr_copy_cols")
-                dcode = dcode + bit.backward(dZ8b)
-            self.ts.finish_group("bg")
-            collect(bit); collect(brt)
-            w = m.frame_latent_encoder.weight
-            gw = zp.take(tuple(w.shape), dtype=w.dtype)
-            gw.index_copy_(0, self.frame, dcode.reshape(1, -1))
-            grads[id(w)] = gw
+            self._background_backward(d_bg_rgb)
         bp = m.density.beta
+        # (handed over, not kept: autograd takes a gradient as param.grad without a copy only while nothing else references it)
+        grads, self.grads = self.grads, None
         grads[id(bp)] = (d_beta.reshape(bp.shape) * torch.sign(bp.detach())).to(bp.dtype)     # density.py:31-33
         if sync is not None:
-            tail = [bp] + ([m.frame_latent_encoder.weight] + b["it"].params() + b["rt"].params() if self.bg is not None else [])
+            b = self.bg
+            tail = [bp] + ([m.frame_latent_encoder.weight] + b["it"].params() + b["rt"].params() if b is not None else [])
             sync.retire(tail, [grads[id(prm)] for prm in tail])
             grads = sync.finish(grads)
         _ZP[0] = None
         return grads
+
+    def _collect(self, *objs, retire=True):
+        """the evaluators' parameter gradients into self.grads; retire: in data-parallel training they leave as one bucket"""
+        grads = self.grads
+        for obj in objs:
+            for prm, g in zip(obj.params(), obj.param_grads()):
+                grads[id(prm)] = g if id(prm) not in grads else grads[id(prm)] + g
+        if retire and self.sync is not None:
+            prms = [prm for o in objs for prm in o.params()]
+            self.sync.retire(prms, [grads[id(prm)] for prm in prms])
+
+    def _composite_backward(self, d_rgb_values, d_acc_map, d_acc_person):
+        """adjoint of mp_composite -> per composited person d sdf and d rgb, d bg_rgb [R][3], d beta"""
+        cx, zp = self.cx, self.zp
+        dev, R = cx["dev"], cx["R"]
+        P = len(self.composited)
+        t_inv, t_z, t_sdf, t_rgb, _ = self.tabs
+        zero = lambda t, shape: zp.take(shape) if t is None else t.contiguous().float()
+        d_rgb_values = zero(d_rgb_values, (R, 3)); d_acc_map = zero(d_acc_map, (R,)); d_acc_person = zero(d_acc_person, (R, P))
+        # persons of other ranks (person-sharded mode) get scratch rows: their owners compute the same compositing adjoint
+        # (a local person's d sdf vector also covers its eikonal points, which no compositing term reaches: zeros)
+        dsdf_l = [zp.take(rec["dsdf_rows"]) for rec in self.composited]
+        drgb_l = [zp.take(rec["rgb"].numel() // 3, 3) for rec in self.composited]
+        d_bg_rgb = zp.take(R, 3)
+        d_beta = zp.take(1)
+        t_dsdf, t_drgb = _table(dsdf_l, dev), _table(drgb_l, dev)
+        _chk(hip.lib().mp_tr_composite_bwd(R, P, self.NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(cx["beta"]),
+                                           _p(self.bg_rgb) if self.bg_rgb is not None else None, _p(d_rgb_values), _p(d_acc_map),
+                                           _p(d_acc_person), _p(t_dsdf), _p(t_drgb), _p(d_bg_rgb), _p(d_beta), hip.stream()),
+             "mp_tr_composite_bwd")
+        return dsdf_l, drgb_l, d_bg_rgb, d_beta
+
+    def _person_backward(self, p, dsdf, drgb, dgth):
+        """colour net, normals / eikonal term, SDF net of person p; retires the person's two networks.
+        -> d cond, dXA [npts][6], d Jinv [npts][9] (pose optimisation)"""
+        L, st = hip.lib(), hip.stream()
+        f = self.fg[p]
+        it, rt, npts, Pt = f["it"], f["rt"], f["npts"], f["Pt"]
+        f32 = dict(dtype=F32, device=self.cx["dev"])
+        dgrad = self.zp.take(Pt, 3)
+        dXA = torch.empty(npts, 6, **f32)
+        dfeat = it.new_dfeat(npts)     # (the eikonal points have no colour path)
+        tn_groups = []                 # the person's aligned weight-gradient contractions: ONE grouped launch below
+        rt.backward(drgb, dXA, *it.dfeat_target(dfeat), tn_groups=tn_groups)
+        djinv = torch.empty(npts, 9, **f32) if self.pose_grad else None
+        _chk(L.mp_tr_shade_in_bwd(None, Pt, npts, _p(f["jinv"]), _p(dXA), _p(dsdf), None, None, _p(djinv), _p(it.grad), _p(dgrad), st),
+             "mp_tr_shade_in_bwd")
+        if dgth is not None:
+            _chk(L.mp_tr_eik_bwd(Pt, npts, N_EIKONAL, _p(dgth), None, _p(dgrad), st), "mp_tr_eik_bwd")
+        dcond = it.backward(dfeat, dsdf, dgrad, want_dx=self.pose_grad, tn_groups=tn_groups)
+        launch_tn_groups(tn_groups)
+        self.ts.finish_group(p)                                   # one batched weight-norm adjoint for the person's two nets
+        self._collect(it, rt)
+        return dcond, dXA, djinv
+
+    def _pose_backward(self, p, dcond, dXA, djinv):
+        """pose optimisation: x_c enters the SDF net (value + gradient sweep) and the colour net (XA[:, :3]); the transforms also shape
+        the normals through Jinv.  -> d tfs -> d (scale, transl, thetas, betas)   (multiply.py:196-206, 270)"""
+        m, cx, L, st = self.model, self.cx, hip.lib(), hip.stream()
+        f32 = dict(dtype=F32, device=cx["dev"])
+        f, pp, server = self.fg[p], cx["per"][p], m.smpl_server_list[p]
+        npts = f["npts"]
+        dxc = (f["it"].dx[:npts] + dXA[:, :3]).contiguous()
+        dtfs = torch.zeros(24, 16, **f32)
+        _chk(L.mp_tr_warp_bwd(_p(f["X"]), _p(dxc), _p(f["jinv"]), _p(djinv), _p(f["nn_posed"]), _p(f["nn_cano"]),
+                              npts, _p(server.tables.lbs_weights), _p(pp["tfs"]), _p(dtfs), st), "mp_tr_warp_bwd")
+        surf = self.reg_surf.get(p)
+        if surf is None:
+            dprm = torch.empty(86, **f32)
+            _chk(L.mp_smpl_pose_bwd(_p(server.tables.parents), _p(pp["prm"]), _p(server.tfs_c_inv),
+                                    _p(pp["rest_joints"]), _p(server.tables.j_shapedirs), _p(dtfs), _p(dprm), st),
+                 "mp_smpl_pose_bwd")
+        else:                                                    # + the surface term's posed vertices and transforms
+            dprm = server.pose_backward(pp["prm"], dverts=surf[1], dtfs=dtfs + surf[0])
+        if not self.cond_zero:                                   # cond = smpl_pose[3:] / pi  (multiply.py:270)
+            dc = dcond + f["rt"].dcond()
+            if p in self.reg_dcond:                              # + the regularisers' share (zero pose; surface, opt-in)
+                dc = dc + self.reg_dcond[p]
+            dprm[7:76] += dc / math.pi
+        self.pose_grads[p] = dprm
+
+    def _background_backward(self, d_bg_rgb):
+        """inverse-sphere compositing, colour net, ImplicitNet of the background on this rank's ray slice; d frame code"""
+        m, L, st = self.model, hip.lib(), hip.stream()
+        f32 = dict(dtype=F32, device=self.cx["dev"])
+        b = self.bg
+        bit, brt, NB, Rb = b["it"], b["rt"], b["NB"], b["Rb"]
+        rows = Rb * NB
+        s0, s1 = self.ray_slice
+        d_bg_slice = d_bg_rgb[s0:s1].contiguous()
+        dsdfb = torch.empty(rows, **f32); drgbb = torch.empty(rows, 3, **f32)
+        _chk(L.mp_tr_bg_comp_bwd(_p(b["sdfb"]), _p(brt.rgb), _p(b["zbg"]), Rb, NB, _p(d_bg_slice), _p(dsdfb), _p(drgbb),
+                                 st), "mp_tr_bg_comp_bwd")
+        dXAb = torch.empty(rows, 27, **f32)
+        dfeatb = bit.new_dfeat(rows)
+        dcode = brt.backward(drgbb, dXAb, *bit.dfeat_target(dfeatb))
+        dcode = dcode + bit.backward(dfeatb, dsdfb)
+        self.ts.finish_group("bg")
+        self._collect(bit, brt, retire=False)                     # (they leave with the sweep's tail bucket)
+        w = m.frame_latent_encoder.weight
+        gw = self.zp.take(tuple(w.shape), dtype=w.dtype)
+        gw.index_copy_(0, self.frame, dcode.reshape(1, -1))
+        self.grads[id(w)] = gw
 
 
 class _TrainFn(torch.autograd.Function):
@@ -1657,36 +1593,28 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
         temporal_loss = torch.zeros(1, device=dev)
         if epoch > 250:                                                             # multiply.py:242-243
             temporal_loss = torch.mean(torch.square(input["smpl_pose_last"].to(dev) - input["smpl_pose"].to(dev)))
-    last = graph.all_persons[-1]
     cam = cx["pose"].reshape(4, 4)[:3, 3]
-    if last in graph.fg:
-        fl = graph.fg[last]
-        hit = cx["per"][last]["hit_index"][:fl["Rp"]].long()
-        points = cam[None, None, :] + fl["zfinal"][:, :-1, None] * cx["dirs"][hit][:, None, :]
-    else:                                   # person-sharded: the last person lives on another rank
-        rl = graph.remote[last]
-        hit = torch.nonzero(rl["hit"]).flatten()
+    last = graph.composited[-1]
+    hit, z = last["rays"], last["z"]
+    if last["hit"] is not None:             # person-sharded, the last person lives on another rank: its rows are all rays
+        hit = torch.nonzero(last["hit"]).flatten()
         if hit.numel() == 0:
             hit = torch.zeros(1, dtype=torch.long, device=dev)      # the reference's empty-hit fallback, multiply.py:262-263
-        points = cam[None, None, :] + rl["z"][hit][:, :-1, None] * cx["dirs"][hit][:, None, :]
+        z = z[hit]
+    hit = hit.long()
+    points = cam[None, None, :] + z[:, :-1, None] * cx["dirs"][hit][:, None, :]
     _z3 = torch.zeros(3, device=dev)            # the dict's constant zero entries: one fill
     _zi = iter(range(3))
     zeros1 = lambda: _z3[next(_zi):][:1]
     index_off_surface = index_in_surface = None
     if epoch < 250:                                                                 # multiply.py:549-557
-        P = len(graph.all_persons)
+        P = len(graph.composited)
         off_all = torch.ones(cx["R"], P, dtype=torch.bool, device=dev)
         in_all = torch.zeros(cx["R"], P, dtype=torch.bool, device=dev)
-        for n, p in enumerate(graph.all_persons):
-            if p in graph.fg:
-                f = graph.fg[p]
-                rays = cx["per"][p]["hit_index"][:f["Rp"]].long()
-                off_all[rays, n] = f["flags"][0]
-                in_all[rays, n] = f["flags"][1]
-            else:
-                r = graph.remote[p]
-                off_all[:, n] = torch.where(r["hit"], r["off"], off_all[:, n])
-                in_all[:, n] = torch.where(r["hit"], r["inn"], in_all[:, n])
+        for n, rec in enumerate(graph.composited):
+            rays = rec["rays"].long()
+            off_all[rays, n] = rec["off"]
+            in_all[rays, n] = rec["inn"]
         index_off_surface, index_in_surface = off_all.all(dim=1), in_all.any(dim=1)
     out = {
         "zero_pose_loss": zero_pose_loss if zero_pose_loss is not None else zeros1(), "t_list": [], "fg_rgb_values_each_person_list": [],

@@ -136,7 +136,7 @@ def test_fused_sdf_kernels_against_autograd(P):
     plist = [p for n, p in m.named_parameters() if n.startswith("foreground_implicit_network_list.0.")]
     want = torch.autograd.grad(loss, plist, allow_unused=True)
     dc_f = fus.backward(a_out[:, 1:].contiguous(), a_out[:, 0].contiguous(), a_g.clone())
-    dc_r = ref.backward(a_out.clone(), a_g.clone())
+    dc_r = ref.backward(a_out.clone(), None, a_g.clone())      # (column 0 of the [P][257] adjoint already holds d sdf)
     assert rel("d cond, fused vs layer-wise", dc_f, dc_r) < 2e-4
     got = dict(zip([id(p) for p in fus.params()], fus.param_grads()))
     gref = dict(zip([id(p) for p in ref.params()], ref.param_grads()))
@@ -201,7 +201,7 @@ def test_fused_colour_kernels_against_autograd(n):
     XA = torch.randn(n, 6, device="cuda")
     feat = (torch.randn(n + 7, 256, device="cuda") * 0.3).contiguous()      # more rows than points, like the SDF net's batch
     cond = torch.randn(69, device="cuda") * 0.1
-    rt = T.RenderTrainFused(ren, XA, feat, n, cond)
+    rt = T.RenderTrainFused(ren, XA, T._p(feat), 256, n, cond)
     sd = {k: v for k, v in m.named_parameters()}
     XAg, featg = XA.clone().requires_grad_(True), feat[:n].clone().requires_grad_(True)
     want_rgb = O.rendering_forward_pose_no_view(sd, "foreground_rendering_network_list.0.", XAg[:, :3], XAg[:, 3:], cond, featg)
@@ -212,7 +212,7 @@ def test_fused_colour_kernels_against_autograd(n):
     want = torch.autograd.grad((want_rgb * a).sum(), plist + [XAg, featg])
     dXA = torch.empty(n, 6, device="cuda")
     dfeat = torch.full((n + 7, 256), 7.0, device="cuda")
-    rt.backward(a, dXA, dfeat)
+    rt.backward(a, dXA, T._p(dfeat), 256, feat_accumulate=False)
     assert bool((dfeat[n:] == 7.0).all()), "rows past the n points are not touched"
     got = dict(zip([id(p) for p in rt.params()], rt.param_grads()))
     assert len(got) == len(plist)

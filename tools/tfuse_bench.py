@@ -45,10 +45,8 @@ for name, cls in (("fused", T.ImplicitTrainFused), ("layer-wise", T.ImplicitTrai
 
     def bwd():
         it = holder["it"]
-        if isinstance(it, T.ImplicitTrainFused):
-            it.backward(dfeat, dsdf, dg)
-        else:
-            it.backward(dZ, dg)
+        # the features' adjoint in the evaluator's own layout: its own [P][256] matrix, or columns 1.. of the [P][257] adjoint
+        it.backward(dfeat if it.dfeat_col0 == 0 else dZ, dsdf, dg)
         it.param_grads()
 
     t_f = timed(fwd, reps)
