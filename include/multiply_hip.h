@@ -594,6 +594,31 @@ int mp_raster_soft(const float* verts, int n_verts, const int* faces, int n_face
                    float zfar, const float* background_host, int* tile_n, const int* offsets, int* list, float* image, int* sel,
                    void* stream);
 
+/* ---- fitting an SDF network to a closed triangle mesh (multiply_amd/smpl_init.py; the reference only LOADS such a fit,
+ * multiply.py:101-108, its producer is not in its tree): the training points of one iteration and the IGR-style objective
+ * (Gropp et al. 2020) with its adjoints.  Randomness comes in as explicit arrays (uniforms in [0,1), standard normals).
+ *   mp_fit_area_cdf : face_verts [F][3][3] -> area [F], normal [F][3] (unit, (b-a) x (c-a)), cdf [F] = inclusive cumulative
+ *                     area / total (sums in double, fixed order, one workgroup).  A face whose cross product is shorter than
+ *                     1e-12 is degenerate: area 0, normal 0, and the search below never selects it.
+ *   mp_fit_sample   : surface point i < n_s from u_surf [n_s][3]: face = first f with cdf[f] > u0, barycentrics
+ *                     (1 - r, r (1 - u2), r u2), r = sqrt(u1) -> surf_pts [n_s][3], surf_nrm [n_s][3], face_id [n_s];
+ *                     volume point j < n_near: surface point (j mod n_s) + sigma_local z_near[j]; j >= n_near: uniform in
+ *                     box = [lo3, hi3] (device) from u_box [n_v - n_near][3] -> vol_pts [n_v][3].
+ *   mp_fit_loss     : points = the n_s surface points, then the n_v volume points.  sdf [n], grad [n][3] of the network,
+ *                     normals [n_s][3], dist [n_v] exact signed distances ->
+ *                     terms[5] = total, mean_S |f|, mean_S |grad f - n|_2, mean_V |c(f) - c(dist)| (c = clamp to
+ *                     [-truncation, truncation] when truncation > 0, identity otherwise), mean_{S+V} (|grad f|_2 - 1)^2;
+ *                     total = w_surface t1 + w_normal t2 + w_distance t3 + w_eikonal t4; d_sdf [n], d_grad [n][3] = its
+ *                     gradient.  Norms < 1e-12 and |.| at 0 contribute 0; an empty set's mean is 0.  One workgroup, sums in
+ *                     a fixed order: bit-identical from call to call. */
+int mp_fit_area_cdf(const float* face_verts, int n_faces, float* area, float* normal, float* cdf, void* stream);
+int mp_fit_sample(const float* face_verts, const float* normal, const float* cdf, int n_faces, const float* u_surf, int n_s,
+                  const float* z_near, int n_near, float sigma_local, const float* u_box, const float* box, int n_v,
+                  float* surf_pts, float* surf_nrm, int* face_id, float* vol_pts, void* stream);
+int mp_fit_loss(const float* sdf, const float* grad, const float* normals, const float* dist, int n_s, int n_v,
+                float w_surface, float w_normal, float w_distance, float w_eikonal, float truncation, float* terms,
+                float* d_sdf, float* d_grad, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

@@ -685,3 +685,61 @@ def background(bg_imp, bg_ren, dirs, cam, z_bg, frame_code, radius=3.0):
                               ptr(pkr.bias), ptr(dirs), ptr(cam), ptr(z_bg), int(z_bg.dim() == 2), R,
                               C.c_float(radius), ptr(out), stream()), "mp_background")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh fit (csrc/fit.hip)
+def fit_area_cdf(face_verts):
+    """face_verts (F,3,3) -> area (F,), unit normal (F,3), inclusive area CDF (F,) normalised to 1 (mp_fit_area_cdf)"""
+    require_device()
+    fv = face_verts.detach().float().reshape(-1, 3, 3).contiguous()
+    F, dev = fv.shape[0], fv.device
+    area = torch.empty(F, dtype=torch.float32, device=dev)
+    normal = torch.empty(F, 3, dtype=torch.float32, device=dev)
+    cdf = torch.empty(F, dtype=torch.float32, device=dev)
+    check(lib().mp_fit_area_cdf(ptr(fv), F, ptr(area), ptr(normal), ptr(cdf), stream()), "mp_fit_area_cdf")
+    return area, normal, cdf
+
+
+def fit_sample(face_verts, normal, cdf, u_surf, z_near, sigma_local, u_box, box, out=None):
+    """One iteration's points of the mesh fit (mp_fit_sample).  u_surf (n_s,3) uniforms, z_near (n_near,3) standard normals,
+    u_box (n_v - n_near,3) uniforms, box (2,3) = lo, hi.  Returns pts (n_s + n_v,3) -- surface points first, then the volume
+    points, one tensor so that the network reads them in place --, the surface normals (n_s,3) and the face ids (n_s,) int32.
+    out: (pts, normals, face_id) tensors of a previous call to write into."""
+    n_s, n_near, n_box = u_surf.shape[0], z_near.shape[0], u_box.shape[0]
+    n_v, dev = n_near + n_box, face_verts.device
+    if out is None:
+        out = (torch.empty(n_s + n_v, 3, dtype=torch.float32, device=dev), torch.empty(n_s, 3, dtype=torch.float32, device=dev),
+               torch.empty(n_s, dtype=torch.int32, device=dev))
+    pts, nrm, fid = out
+    assert pts.shape[0] == n_s + n_v and nrm.shape[0] == n_s and fid.dtype == torch.int32
+    check(lib().mp_fit_sample(ptr(face_verts), ptr(normal), ptr(cdf), cdf.shape[0], ptr(u_surf) if n_s else None, n_s,
+                              ptr(z_near) if n_near else None, n_near, C.c_float(sigma_local), ptr(u_box) if n_box else None,
+                              ptr(box), n_v, ptr(pts), ptr(nrm), ptr(fid), C.c_void_p(pts.data_ptr() + 12 * n_s), stream()),
+          "mp_fit_sample")
+    return pts, nrm, fid
+
+
+def fit_loss(sdf, grad, normals, dist, weights, truncation=0.0, out=None):
+    """The fit's objective and its adjoints in one launch (mp_fit_loss).  sdf (>= n,), grad (n,3): the network on the n_s surface
+    points followed by the n_v volume points; normals (n_s,3); dist (n_v,); weights = (surface, normal, distance, eikonal).
+    Returns terms (5,) = total, surface, normal, distance, eikonal; d_sdf (n,); d_grad (n,3)."""
+    n_s, n_v, dev = normals.shape[0], dist.shape[0], grad.device
+    n = n_s + n_v
+    assert grad.shape[0] == n and sdf.numel() >= n
+    if out is None:
+        out = (torch.empty(5, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+               torch.empty(n, 3, dtype=torch.float32, device=dev))
+    terms, d_sdf, d_grad = out
+    w = [C.c_float(float(x)) for x in weights]
+    check(lib().mp_fit_loss(ptr(sdf), ptr(grad), ptr(normals) if n_s else None, ptr(dist) if n_v else None, n_s, n_v, w[0], w[1],
+                            w[2], w[3], C.c_float(float(truncation)), ptr(terms), ptr(d_sdf), ptr(d_grad), stream()), "mp_fit_loss")
+    return terms, d_sdf, d_grad
+
+
+def mesh_signed_distance(pts, face_verts, out=None):
+    """exact signed distance (negative inside) of pts (n,3) to the closed mesh face_verts (F,3,3): mp_mesh_signed_distance"""
+    n = pts.shape[0]
+    sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
+    check(lib().mp_mesh_signed_distance(ptr(pts), n, ptr(face_verts), face_verts.shape[0], ptr(sd), stream()),
+          "mp_mesh_signed_distance")
+    return sd

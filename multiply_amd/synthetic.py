@@ -183,3 +183,37 @@ def write_sequence(root, n_frames=4, H=96, W=128, num_person=2, seed=0, with_edg
     np.save(os.path.join(root, "gender.npy"), np.array(["male"] * num_person))
     np.savez(os.path.join(root, "cameras_normalize.npz"), **cams)
     return dict(images=np.stack(images), masks=np.stack(masks), poses=poses, trans=trans, shape=shape, intrinsics=K, pose=pose)
+
+
+def body_capsules(joints):
+    """the 24 capsules of the synthetic body (make_smpl_tables) on the given joints (24,3): segment starts, ends, radii.
+    Bone j runs from its parent's joint to joint j; the root gets a short pelvis segment, the head extends above its joint."""
+    J = np.asarray(joints, dtype=np.float64).reshape(NUM_JOINTS, 3)
+    seg_a = np.where(SMPL_PARENTS[:, None] >= 0, J[np.maximum(SMPL_PARENTS, 0)], J - np.array([0, 0.05, 0]))
+    seg_b = J.copy()
+    seg_b[15] = J[15] + np.array([0.0, 0.12, 0.0])
+    return seg_a, seg_b, _BONE_RADIUS.copy()
+
+
+def closed_body_mesh(smpl_server, res_up=2):
+    """A CLOSED surface of the synthetic body in canonical space, to fit an SDF network to (smpl_init.fit_smpl_init): the zero set
+    of the union of the 24 capsules (min over the bones of distance-to-segment minus _BONE_RADIUS) placed on the server's
+    canonical-pose joints, extracted with mesh.generate_mesh (device function, largest component).  The tables' own `f` is only a
+    list of near-neighbour triangles.  Returns vertices (V,3) float32 and faces (F,3) int64 as device tensors."""
+    import torch
+    from .mesh import generate_mesh
+    dev = smpl_server.joints_c.device
+    a, b, r = body_capsules(smpl_server.joints_c.detach().reshape(-1, 3).cpu().numpy())
+    A, B, R = (torch.tensor(x, dtype=torch.float32, device=dev) for x in (a, b, r))
+    AB = B - A
+    ab2 = (AB * AB).sum(1).clamp_min(1e-12)
+
+    def sdf(x):
+        ap = x[:, None, :] - A[None]
+        t = ((ap * AB[None]).sum(-1) / ab2[None]).clamp(0.0, 1.0)
+        d = (ap - t[..., None] * AB[None]).norm(dim=-1) - R[None]
+        return d.min(dim=1).values
+
+    corners = torch.cat([A - R[:, None], A + R[:, None], B - R[:, None], B + R[:, None]])    # the capsules' bounding box
+    m = generate_mesh(sdf, corners, 0.0, res_init=32, res_up=res_up, point_batch=1 << 18)
+    return m.vertices_t.float().contiguous(), m.faces_t.long().contiguous()
