@@ -102,9 +102,8 @@ class SceneStore:
             extra = extra.to(self.device).float().contiguous()
             n_extra = extra.shape[-1]
             ex_out = torch.empty(n, n_extra, **f32)
-        hip.check(L.mp_sample_pixels(hip.ptr(self.images[frame]), hip.ptr(self.object_masks[frame]), hip.ptr(extra), n_extra,
-                                     hip.ptr(dpos), n, H, W, hip.ptr(rgb), hip.ptr(uv), hip.ptr(om), hip.ptr(ex_out),
-                                     hip.stream()), "mp_sample_pixels")
+        L.mp_sample_pixels(self.images[frame], self.object_masks[frame], extra, n_extra, dpos, n, H, W, rgb, uv, om, ex_out,
+                           hip.stream())
         self._keep = (dpos, extra)
         return rgb, uv, om, ex_out
 

@@ -30,10 +30,7 @@ class SMPLDeformer(nn.Module):
         self.verts_c_flat = self.smpl_verts[0].detach().float().contiguous()      # (V,3), original vertex order
         dev = self.smpl_verts.device
         self.knn_perm = torch.from_numpy(knn_cluster_perm(self.smpl_verts[0].cpu().numpy())).to(dev)
-        self.vsorted_c = torch.empty(hip.KNN_NC * hip.KNN_CLUSTER, 4, dtype=torch.float32, device=dev)
-        self.cbound_c = torch.empty(hip.KNN_CB_ROWS, 4, dtype=torch.float32, device=dev)
-        hip.check(hip.lib().mp_knn_build(hip.ptr(self.smpl_verts[0].contiguous()), hip.ptr(self.knn_perm),
-                                         hip.ptr(self.vsorted_c), hip.ptr(self.cbound_c), hip.stream()), "mp_knn_build")
+        self.vsorted_c, self.cbound_c = hip.knn_tables(self.smpl_verts[0].contiguous(), self.knn_perm)
 
     def forward(self, x, smpl_tfs, return_weights=True, inverse=False, smpl_verts=None):
         """deformer.py:19-30.  The hot-path call pattern (return_weights=False, inverse=True, K=1) takes the fused warp
@@ -52,35 +49,26 @@ class SMPLDeformer(nn.Module):
                 return w[None]
             tfs = smpl_tfs.detach().float().reshape(24, 16).contiguous()
             out = torch.empty(n, 3, dtype=torch.float32, device=dev)
-            hip.check(L.mp_skinning(hip.ptr(x), hip.ptr(w), n, hip.ptr(tfs), int(bool(inverse)), hip.ptr(out), hip.stream()),
-                      "mp_skinning")
+            L.mp_skinning(x, w, n, tfs, int(bool(inverse)), out, hip.stream())
             return out, outl.bool()
-        vs = torch.empty(hip.KNN_NC * hip.KNN_CLUSTER, 4, dtype=torch.float32, device=dev)
-        cb = torch.empty(hip.KNN_CB_ROWS, 4, dtype=torch.float32, device=dev)
-        hip.check(L.mp_knn_build(hip.ptr(verts), hip.ptr(self.knn_perm), hip.ptr(vs), hip.ptr(cb), hip.stream()),
-                  "mp_knn_build")
+        vs, cb = hip.knn_tables(verts, self.knn_perm)
         xc = torch.empty(n, 3, dtype=torch.float32, device=dev)
         outl = torch.empty(n, dtype=torch.uint8, device=dev)
-        hip.check(L.mp_warp_inverse(hip.ptr(x), None, None, None, None, None, 0, 1, n, hip.ptr(vs), hip.ptr(cb),
-                                    hip.ptr(self._blend_table(smpl_tfs)), 0, None, None, hip.ptr(xc),
-                                    hip.ptr(outl), None, None, None, None, hip.stream()), "mp_warp_inverse")
+        L.mp_warp_inverse(x, None, None, None, None, None, 0, 1, n, vs, cb, self._blend_table(smpl_tfs), 0, None, None, xc, outl,
+                          None, None, None, None, hip.stream())
         return xc, outl.bool()
 
     def _blend_table(self, smpl_tfs):
         """per-vertex inverse blended transforms of one pose (mp_blend_table), (V,12)"""
         tfs = smpl_tfs.detach().float().reshape(24, 16).contiguous()
-        w = self.smpl_weights[0].contiguous()
-        tab = torch.empty(w.shape[0], 12, dtype=torch.float32, device=w.device)
-        hip.check(hip.lib().mp_blend_table(hip.ptr(w), hip.ptr(tfs), w.shape[0], hip.ptr(tab), hip.stream()), "mp_blend_table")
-        return tab
+        return hip.blend_table(self.smpl_weights[0].contiguous(), tfs)
 
     def _query(self, x, verts):
         n = x.shape[0]
         w = torch.empty(n, 24, dtype=torch.float32, device=x.device)
         outl = torch.empty(n, dtype=torch.uint8, device=x.device)
-        hip.check(hip.lib().mp_query_weights(hip.ptr(x), n, hip.ptr(verts), verts.shape[0],
-                                             hip.ptr(self.smpl_weights[0].contiguous()), int(self.K), hip.ptr(w),
-                                             hip.ptr(outl), hip.stream()), "mp_query_weights")
+        hip.lib().mp_query_weights(x, n, verts, verts.shape[0], self.smpl_weights[0].contiguous(), int(self.K), w, outl,
+                                   hip.stream())
         return w, outl
 
     def query_skinning_weights_smpl_multi(self, pts, smpl_verts, smpl_weights=None):
@@ -98,8 +86,7 @@ class SMPLDeformer(nn.Module):
         w, _ = self._query(x, self.smpl_verts[0].contiguous())
         tfs = smpl_tfs.detach().float().reshape(24, 16).contiguous()
         out = torch.empty_like(x)
-        hip.check(hip.lib().mp_skinning(hip.ptr(x), hip.ptr(w), x.shape[0], hip.ptr(tfs), 0, hip.ptr(out), hip.stream()),
-                  "mp_skinning")
+        hip.lib().mp_skinning(x, w, x.shape[0], tfs, 0, out, hip.stream())
         return out[None]
 
     def forward_skinning_jacobian_inverse(self, xc, smpl_tfs):
@@ -107,7 +94,6 @@ class SMPLDeformer(nn.Module):
         xc = xc.detach().float().contiguous()
         n = xc.shape[0]
         jinv = torch.empty(n, 9, dtype=torch.float32, device=xc.device)
-        hip.check(hip.lib().mp_warp_jacobian(hip.ptr(xc), None, None, 0, 0, n, hip.ptr(self.vsorted_c),
-                                             hip.ptr(self.cbound_c), hip.ptr(self._blend_table(smpl_tfs)),
-                                             hip.ptr(jinv), None, None, None, hip.stream()), "mp_warp_jacobian")
+        hip.lib().mp_warp_jacobian(xc, None, None, 0, 0, n, self.vsorted_c, self.cbound_c, self._blend_table(smpl_tfs), jinv,
+                                   None, None, None, hip.stream())
         return jinv.reshape(n, 3, 3)

@@ -81,10 +81,23 @@ def lib_source_sha16():
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "multiply_hip.h")
 
 
+class DevPtr(C.c_void_p):
+    """argtype of every pointer parameter: the one place a tensor becomes a device pointer.  Anything else (None, a c_void_p
+    from ptr() / an offset pointer, byref(struct), a ctypes array, an int) converts as for c_void_p.  A refused tensor surfaces
+    from the call as ctypes.ArgumentError, which names the argument's position."""
+
+    @classmethod
+    def from_param(cls, t):
+        if isinstance(t, torch.Tensor):
+            assert t.is_cuda and t.is_contiguous(), "device-resident contiguous tensors only"
+            return C.c_void_p(t.data_ptr())
+        return C.c_void_p.from_param(t)
+
+
 def header_prototypes(path=HEADER_PATH):
     """{name: (restype, [argtypes])} parsed from include/multiply_hip.h -- the header is the single source of truth
     for the C ABI; scalars map to their exact ctypes width (a `long long` or `float` passed as a default Python int /
-    double would otherwise be widened or truncated by ctypes' default conversions), every pointer to c_void_p."""
+    double would otherwise be widened or truncated by ctypes' default conversions), every pointer to DevPtr."""
     import re
     with open(path) as f:
         txt = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
@@ -97,7 +110,7 @@ def header_prototypes(path=HEADER_PATH):
             if a in ("void", ""):
                 continue
             if "*" in a:
-                at.append(C.c_void_p)
+                at.append(DevPtr)
             else:
                 ty = re.sub(r"\bconst\b", "", a).strip().rsplit(" ", 1)[0].strip()
                 at.append(scal[ty])
@@ -105,10 +118,28 @@ def header_prototypes(path=HEADER_PATH):
     return protos
 
 
+# Every entry point returns a status (0, or a hipError_t / negative argument-error code: the header's top comment) except these,
+# which return a value
+VALUE_RETURNING = ("mp_device_ok", "mp_sig_bytes_per_point", "mp_obb_hull_device_work_bytes", "mp_warp_bin_work_bytes",
+                   "mp_debug_hull_abandon", "mp_arch")
+_DEBUG_SYNC = bool(int(os.environ.get("MP_DEBUG_SYNC", "0")))
+
+
+def _errcheck(code, fn, args):
+    """ctypes errcheck of every status-returning entry point: no launch's status goes unread"""
+    check(code, fn.__name__)
+    if _DEBUG_SYNC:                      # debugging aid: attribute asynchronous faults to the launch that caused them
+        torch.cuda.synchronize()
+        print("[mp sync ok]", fn.__name__, flush=True)
+    return code
+
+
 def _declare_prototypes(l):
     for name, (rt, at) in header_prototypes().items():
         fn = getattr(l, name)
         fn.restype, fn.argtypes = rt, at
+        if name not in VALUE_RETURNING:
+            fn.errcheck = _errcheck
 
 
 def require_device():
@@ -232,10 +263,8 @@ class PackedNet:
         h0, hn = p.hoist if (p.hoist is not None and hoist_vec is not None) else (0, 0)
         wp = C.c_void_p(self.wpack.data_ptr() + self.offsets[i] * self.chunk_bytes) if weights else None
         bp = C.c_void_p(self.bias.data_ptr() + 4 * i * BIAS_STRIDE)
-        check(lib().mp_pack_layer(ptr(v), ptr(g), ptr(b), v.shape[0], v.shape[1], ptr(self.rowmaps[i]),
-                                  len(p.rowmap), ptr(self.colmaps[i]), ptr(self.colscales[i]), self.ks_in, h0, hn,
-                                  ptr(hoist_vec) if hn else None, C.c_float(p.bias_scale), wp, bp, stream()),
-              "mp_pack_layer")
+        lib().mp_pack_layer(v, g, b, v.shape[0], v.shape[1], self.rowmaps[i], len(p.rowmap), self.colmaps[i], self.colscales[i],
+                            self.ks_in, h0, hn, hoist_vec if hn else None, p.bias_scale, wp, bp, stream())
 
     def param_version(self):
         vs = [_GENERATION[0]]
@@ -283,7 +312,7 @@ class PackedNet:
                 self._hoist_buf[:hn].copy_(hoist_vec.detach().reshape(-1)[:hn].float(), non_blocking=True)
             if full or hoisted:
                 tab = self._table(bool(full), hoisted)
-                check(lib().mp_pack_layers(ptr(tab), len(self.plans), self.ks_in, stream()), "mp_pack_layers")
+                lib().mp_pack_layers(tab, len(self.plans), self.ks_in, stream())
             self.version = ver
             return
         for i, p in enumerate(self.plans):
@@ -494,14 +523,38 @@ class PoseEmbed:
     def __call__(self, cond_vec):
         lp = self.net.lin_pose
         w, b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
-        check(lib().mp_pack_layer(ptr(w), None, ptr(b), 8, 69, ptr(self.rowmap), 32, ptr(self.colmap),
-                                  ptr(self.colscale), 2, 0, 69, ptr(cond_vec), C.c_float(1.0), None, ptr(self.out),
-                                  stream()),
-              "mp_pack_layer(lin_pose)")
+        lib().mp_pack_layer(w, None, b, 8, 69, self.rowmap, 32, self.colmap, self.colscale, 2, 0, 69, cond_vec, 1.0, None,
+                            self.out, stream())
         return self.out  # first 8 floats
 
 
+def pose_embed(ren):
+    """the PoseEmbed of a 'pose_no_view' RenderingNet (cached on the module)"""
+    pe = ren.__dict__.get("_mp_pose_embed")
+    if pe is None:
+        pe = ren.__dict__["_mp_pose_embed"] = PoseEmbed(ren)
+    return pe
+
+
 # ------------------------------------------------------------------------------------------------ module-level ops
+def knn_tables(verts, perm):
+    """nearest-vertex structure of posed / canonical vertices (V,3) under the static cluster order `perm` (mp_knn_build):
+    vsorted (KNN_NC * KNN_CLUSTER, 4) and the clusters' bounding spheres cbound (KNN_CB_ROWS, 4)"""
+    f32 = dict(dtype=torch.float32, device=verts.device)
+    vsorted = torch.empty(KNN_NC * KNN_CLUSTER, 4, **f32)
+    cbound = torch.empty(KNN_CB_ROWS, 4, **f32)
+    lib().mp_knn_build(verts, perm, vsorted, cbound, stream())
+    return vsorted, cbound
+
+
+def blend_table(lbs_weights, tfs):
+    """(V,12) per-vertex inverse blended transform of the bone transforms tfs (24 x 16 floats) (mp_blend_table)"""
+    n = lbs_weights.shape[0]
+    tab = torch.empty(n, 12, dtype=torch.float32, device=lbs_weights.device)
+    lib().mp_blend_table(lbs_weights, tfs, n, tab, stream())
+    return tab
+
+
 def implicit_forward(net, x, cond_vec):
     """ImplicitNet.forward for external callers: (N, d_in) -> (N, 257) fp32 (features are f16-rounded)."""
     require_device()
@@ -510,8 +563,7 @@ def implicit_forward(net, x, cond_vec):
     pk = packed(net, "full", ks_in)
     pk.refresh(None if cond_vec is None else cond_vec.detach().float().contiguous())
     out = torch.empty(x.shape[0], 257, dtype=torch.float32, device=x.device)
-    check(lib().mp_mlp_full(C.byref(pk.net), ptr(pk.wpack), ptr(pk.bias), ptr(x), net.d_in, x.shape[0], ptr(out),
-                            stream()), "mp_mlp_full")
+    lib().mp_mlp_full(C.byref(pk.net), pk.wpack, pk.bias, x, net.d_in, x.shape[0], out, stream())
     return out
 
 
@@ -524,8 +576,7 @@ def implicit_sdf(net, x_c, cond_vec, mode="f16"):
     pk.refresh(cond_vec.detach().float().contiguous())
     out = torch.empty(x_c.shape[0], dtype=torch.float32, device=x_c.device)
     fn = {"f16": lib().mp_mlp_sdf, "f16x2": lib().mp_mlp_sdf_x2}[mode]
-    check(fn(C.byref(pk.net), ptr(pk.wpack), ptr(pk.bias), ptr(x_c), None, None, x_c.shape[0], ptr(out), stream()),
-          "mp_mlp_sdf" + ("_x2" if mode == "f16x2" else ""))
+    fn(C.byref(pk.net), pk.wpack, pk.bias, x_c, None, None, x_c.shape[0], out, stream())
     return out
 
 
@@ -583,9 +634,8 @@ _SCRATCH = {}
 
 def shade_rev_launch(pki, gn, x_c, jinv, worklist, count, n, sdf, nrm, feat):
     buf, seg = sig_scratch(x_c.device, n)
-    check(lib().mp_mlp_shade_rev(C.byref(pki.net), ptr(pki.wpack), ptr(pki.bias), C.byref(gn.pk.net), ptr(gn.pk.wpack),
-                                 ptr(gn.w8), ptr(x_c), ptr(jinv), ptr(worklist), ptr(count), n, ptr(sdf), ptr(nrm),
-                                 ptr(feat), ptr(buf), seg, stream()), "mp_mlp_shade_rev")
+    lib().mp_mlp_shade_rev(C.byref(pki.net), pki.wpack, pki.bias, C.byref(gn.pk.net), gn.pk.wpack, gn.w8, x_c, jinv, worklist,
+                           count, n, sdf, nrm, feat, buf, seg, stream())
 
 
 def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
@@ -599,9 +649,7 @@ def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
     pki = packed(imp, "full", 2)
     pki.refresh(cond_vec)
     pkr = packed(ren, "color", 2)
-    pe = ren.__dict__.setdefault("_mp_pose_embed", None) or PoseEmbed(ren)
-    ren.__dict__["_mp_pose_embed"] = pe
-    pkr.refresh(pe(cond_vec))
+    pkr.refresh(pose_embed(ren)(cond_vec))
     dev = x_c.device
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
     nrm = torch.empty(n, 3, dtype=torch.float32, device=dev)
@@ -611,10 +659,8 @@ def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
     if (mode or SHADE_MODE) == "reverse":
         shade_rev_launch(pki, grad_net(imp), x_c, jinv, None, None, n, sdf, nrm, feat)
     else:
-        check(lib().mp_mlp_shade(C.byref(pki.net), ptr(pki.wpack), ptr(pki.bias), ptr(x_c), ptr(jinv), None, None, n,
-                                 ptr(sdf), ptr(nrm), ptr(feat), stream()), "mp_mlp_shade")
-    check(lib().mp_mlp_color(C.byref(pkr.net), ptr(pkr.wpack), ptr(pkr.bias), ptr(x_c), ptr(nrm), ptr(feat), None,
-                             None, n, ptr(rgb), stream()), "mp_mlp_color")
+        lib().mp_mlp_shade(C.byref(pki.net), pki.wpack, pki.bias, x_c, jinv, None, None, n, sdf, nrm, feat, stream())
+    lib().mp_mlp_color(C.byref(pkr.net), pkr.wpack, pkr.bias, x_c, nrm, feat, None, None, n, rgb, stream())
     return sdf, nrm, rgb
 
 
@@ -655,13 +701,10 @@ def rendering_forward(net, points, normals, view_dirs, body_pose, feature_vector
     n = x.shape[0]
     cond_vec = body_pose.detach().float().reshape(-1).contiguous()
     pk = packed(net, "color", 2)
-    pe = net.__dict__.get("_mp_pose_embed") or PoseEmbed(net)
-    net.__dict__["_mp_pose_embed"] = pe
-    pk.refresh(pe(cond_vec))
+    pk.refresh(pose_embed(net)(cond_vec))
     frag = pack_feature_fragments(feature_vectors.detach().float().reshape(n, -1))
     rgb = torch.empty(n, 3, dtype=torch.float32, device=x.device)
-    check(lib().mp_mlp_color(C.byref(pk.net), ptr(pk.wpack), ptr(pk.bias), ptr(x), ptr(nrm), ptr(frag), None, None, n, ptr(rgb),
-                             stream()), "mp_mlp_color")
+    lib().mp_mlp_color(C.byref(pk.net), pk.wpack, pk.bias, x, nrm, frag, None, None, n, rgb, stream())
     return rgb
 
 
@@ -681,9 +724,8 @@ def background(bg_imp, bg_ren, dirs, cam, z_bg, frame_code, radius=3.0):
         raise NotImplementedError("the fused background kernel is specialised for the 32 inverse-sphere samples of the shipped "
                                   f"configs (N_samples_inverse_sphere), got {z_bg.shape[-1]}")
     out = torch.empty(R, 3, dtype=torch.float32, device=dirs.device)
-    check(lib().mp_background(C.byref(pki.net), ptr(pki.wpack), ptr(pki.bias), C.byref(pkr.net), ptr(pkr.wpack),
-                              ptr(pkr.bias), ptr(dirs), ptr(cam), ptr(z_bg), int(z_bg.dim() == 2), R,
-                              C.c_float(radius), ptr(out), stream()), "mp_background")
+    lib().mp_background(C.byref(pki.net), pki.wpack, pki.bias, C.byref(pkr.net), pkr.wpack, pkr.bias, dirs, cam, z_bg,
+                        int(z_bg.dim() == 2), R, radius, out, stream())
     return out
 
 
@@ -696,7 +738,7 @@ def fit_area_cdf(face_verts):
     area = torch.empty(F, dtype=torch.float32, device=dev)
     normal = torch.empty(F, 3, dtype=torch.float32, device=dev)
     cdf = torch.empty(F, dtype=torch.float32, device=dev)
-    check(lib().mp_fit_area_cdf(ptr(fv), F, ptr(area), ptr(normal), ptr(cdf), stream()), "mp_fit_area_cdf")
+    lib().mp_fit_area_cdf(fv, F, area, normal, cdf, stream())
     return area, normal, cdf
 
 
@@ -712,10 +754,9 @@ def fit_sample(face_verts, normal, cdf, u_surf, z_near, sigma_local, u_box, box,
                torch.empty(n_s, dtype=torch.int32, device=dev))
     pts, nrm, fid = out
     assert pts.shape[0] == n_s + n_v and nrm.shape[0] == n_s and fid.dtype == torch.int32
-    check(lib().mp_fit_sample(ptr(face_verts), ptr(normal), ptr(cdf), cdf.shape[0], ptr(u_surf) if n_s else None, n_s,
-                              ptr(z_near) if n_near else None, n_near, C.c_float(sigma_local), ptr(u_box) if n_box else None,
-                              ptr(box), n_v, ptr(pts), ptr(nrm), ptr(fid), C.c_void_p(pts.data_ptr() + 12 * n_s), stream()),
-          "mp_fit_sample")
+    lib().mp_fit_sample(face_verts, normal, cdf, cdf.shape[0], u_surf if n_s else None, n_s, z_near if n_near else None, n_near,
+                        sigma_local, u_box if n_box else None, box, n_v, pts, nrm, fid, C.c_void_p(pts.data_ptr() + 12 * n_s),
+                        stream())
     return pts, nrm, fid
 
 
@@ -730,9 +771,9 @@ def fit_loss(sdf, grad, normals, dist, weights, truncation=0.0, out=None):
         out = (torch.empty(5, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
                torch.empty(n, 3, dtype=torch.float32, device=dev))
     terms, d_sdf, d_grad = out
-    w = [C.c_float(float(x)) for x in weights]
-    check(lib().mp_fit_loss(ptr(sdf), ptr(grad), ptr(normals) if n_s else None, ptr(dist) if n_v else None, n_s, n_v, w[0], w[1],
-                            w[2], w[3], C.c_float(float(truncation)), ptr(terms), ptr(d_sdf), ptr(d_grad), stream()), "mp_fit_loss")
+    w = [float(x) for x in weights]
+    lib().mp_fit_loss(sdf, grad, normals if n_s else None, dist if n_v else None, n_s, n_v, w[0], w[1], w[2], w[3],
+                      float(truncation), terms, d_sdf, d_grad, stream())
     return terms, d_sdf, d_grad
 
 
@@ -740,6 +781,5 @@ def mesh_signed_distance(pts, face_verts, out=None):
     """exact signed distance (negative inside) of pts (n,3) to the closed mesh face_verts (F,3,3): mp_mesh_signed_distance"""
     n = pts.shape[0]
     sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
-    check(lib().mp_mesh_signed_distance(ptr(pts), n, ptr(face_verts), face_verts.shape[0], ptr(sd), stream()),
-          "mp_mesh_signed_distance")
+    lib().mp_mesh_signed_distance(pts, n, face_verts, face_verts.shape[0], sd, stream())
     return sd

@@ -51,7 +51,7 @@ class _FusedTerms(torch.autograd.Function):
         p = lambda t: None if t is None else t.data_ptr()
         args = MpLossArgs(p(rgb), p(rgb_gt), p(acc), p(accp), p(gth), p(sam), p(in_mask), p(d_rgb), p(d_acc), p(d_accp), p(d_gth),
                           p(terms), R, P, N, *w)
-        hip.check(hip.lib().mp_loss_fused(C.byref(args), hip.stream()), "mp_loss_fused")
+        hip.lib().mp_loss_fused(C.byref(args), hip.stream())
         ctx.grads = (d_rgb, d_acc, d_accp, d_gth)
         ctx.mark_non_differentiable(terms)
         return terms[0].reshape(1), terms

@@ -93,20 +93,18 @@ class MISE:
         self.count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n_split = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.n_queried = []
-        hip.check(hip.lib().mp_mise_init(self.resolution_0, self.depth, hip.ptr(self.state), hip.ptr(self.vox), hip.stream()),
-                  "mp_mise_init")
+        hip.lib().mp_mise_init(self.resolution_0, self.depth, self.state, self.vox, hip.stream())
 
     def query(self):
         """lattice points (k, 3) int32 whose value is unknown (device tensor; order unspecified)"""
         L, n = hip.lib(), self.resolution + 1
         self.count.zero_()
-        hip.check(L.mp_mise_collect(n, hip.ptr(self.state), hip.ptr(self.count), 0, None, hip.stream()), "mp_mise_collect")
+        L.mp_mise_collect(n, self.state, self.count, 0, None, hip.stream())
         k = int(self.count.item())
         pts = torch.empty(max(k, 1), 3, dtype=torch.int32, device=self.device)
         if k:
             self.count.zero_()
-            hip.check(L.mp_mise_collect(n, hip.ptr(self.state), hip.ptr(self.count), k, hip.ptr(pts), hip.stream()),
-                      "mp_mise_collect")
+            L.mp_mise_collect(n, self.state, self.count, k, pts, hip.stream())
         return pts[:k]
 
     def update(self, points, values):
@@ -115,19 +113,17 @@ class MISE:
         pts = points.to(self.device).to(torch.int32).contiguous()
         vals = values.to(self.device).float().reshape(-1).contiguous()
         assert pts.shape[0] == vals.shape[0]
-        hip.check(L.mp_mise_scatter(n, hip.ptr(pts), hip.ptr(vals), pts.shape[0], hip.ptr(self.state), hip.ptr(self.val),
-                                    hip.stream()), "mp_mise_scatter")
+        L.mp_mise_scatter(n, pts, vals, pts.shape[0], self.state, self.val, hip.stream())
         self.pos.zero_()
         self.neg.zero_()
-        hip.check(L.mp_mise_refine(self.resolution_0, self.depth, self.threshold, hip.ptr(self.state), hip.ptr(self.val),
-                                   hip.ptr(self.vox), hip.ptr(self.pos), hip.ptr(self.neg), hip.ptr(self.n_split),
-                                   hip.stream()), "mp_mise_refine")
+        L.mp_mise_refine(self.resolution_0, self.depth, self.threshold, self.state, self.val, self.vox, self.pos, self.neg,
+                         self.n_split, hip.stream())
         self.n_queried.append(pts.shape[0])
 
     def to_dense(self):
         """(resolution+1)^3 fp32 values; lattice points that never became grid points inherit along x, then y, then z"""
         state, val = self.state.clone(), self.val.clone()
-        hip.check(hip.lib().mp_mise_fill(self.resolution + 1, hip.ptr(state), hip.ptr(val), hip.stream()), "mp_mise_fill")
+        hip.lib().mp_mise_fill(self.resolution + 1, state, val, hip.stream())
         return val
 
 
@@ -141,7 +137,7 @@ def marching_cubes(volume, level=0.0):
     dev = vol.device
     table = torch.from_numpy(build_tri_table()).to(dev)
     counts = torch.empty((n - 1) ** 3, dtype=torch.int32, device=dev)
-    hip.check(L.mp_mc_count(hip.ptr(vol), n, float(level), hip.ptr(table), hip.ptr(counts), hip.stream()), "mp_mc_count")
+    L.mp_mc_count(vol, n, float(level), table, counts, hip.stream())
     ends = torch.cumsum(counts.long(), 0)
     T = int(ends[-1].item())
     if T == 0:
@@ -149,8 +145,7 @@ def marching_cubes(volume, level=0.0):
     offsets = (ends - counts.long()).contiguous()
     corners = torch.empty(3 * T, 3, dtype=torch.float32, device=dev)
     edge_id = torch.empty(3 * T, dtype=torch.int64, device=dev)
-    hip.check(L.mp_mc_emit(hip.ptr(vol), n, float(level), hip.ptr(table), hip.ptr(offsets), hip.ptr(corners), hip.ptr(edge_id),
-                           hip.stream()), "mp_mc_emit")
+    L.mp_mc_emit(vol, n, float(level), table, offsets, corners, edge_id, hip.stream())
     uniq, inverse = torch.unique(edge_id, return_inverse=True)
     verts = torch.empty(uniq.shape[0], 3, dtype=torch.float32, device=dev)
     verts[inverse] = corners                      # every corner of one lattice edge carries identical bits

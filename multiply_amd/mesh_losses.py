@@ -100,8 +100,7 @@ def interpenetration_loss(vertex_list, face_list, num_points=5120, draws=None):
                 continue
             fv = partner[0].detach()[face_list[qid].reshape(-1, 3).long()].float().contiguous()     # (F,3,3)
             sd = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
-            hip.check(L.mp_mesh_signed_distance(hip.ptr(pts), pts.shape[0], hip.ptr(fv), fv.shape[0], hip.ptr(sd),
-                                                hip.stream()), "mp_mesh_signed_distance")
+            L.mp_mesh_signed_distance(pts, pts.shape[0], fv, fv.shape[0], sd, hip.stream())
             inside = sd < 0
             pen = sample[0][inside]
             nn_pts = partner[0][_nearest(pen.detach(), partner[0].detach())]

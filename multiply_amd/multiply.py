@@ -279,8 +279,7 @@ class Multiply(nn.Module):
         # rays (rend_util.get_camera_params)
         dirs = torch.empty(R, 3, **f32)
         far = torch.empty(R, **f32)
-        hip.check(L.mp_ray_setup(hip.ptr(uv), hip.ptr(K), hip.ptr(pose), R, C.c_float(self.sdf_bounding_sphere),
-                                 hip.ptr(dirs), hip.ptr(far), st), "mp_ray_setup")
+        L.mp_ray_setup(uv, K, pose, R, self.sdf_bounding_sphere, dirs, far, st)
 
         # SMPL posing, nearest-vertex structures, box cull  (multiply.py:196-214, 256-266)
         per = {}
@@ -304,14 +303,8 @@ class Multiply(nn.Module):
             tfs = torch.empty(NUM_JOINTS, 4, 4, **f32)
             jnts = torch.empty(NUM_JOINTS, 3, **f32)
             server.pose_into(prm, verts, tfs, jnts)
-            d = self.deformer_list[p]
-            vsorted = torch.empty(hip.KNN_NC * hip.KNN_CLUSTER, 4, **f32)
-            cbound = torch.empty(hip.KNN_CB_ROWS, 4, **f32)
-            hip.check(L.mp_knn_build(hip.ptr(verts), hip.ptr(d.knn_perm), hip.ptr(vsorted), hip.ptr(cbound), st),
-                      "mp_knn_build")
-            btab = torch.empty(NUM_VERTS, 12, **f32)        # per-vertex inverse blended transform of this pose
-            hip.check(L.mp_blend_table(hip.ptr(server.tables.lbs_weights), hip.ptr(tfs), NUM_VERTS, hip.ptr(btab), st),
-                      "mp_blend_table")
+            vsorted, cbound = hip.knn_tables(verts, self.deformer_list[p].knn_perm)
+            btab = hip.blend_table(server.tables.lbs_weights, tfs)        # per-vertex inverse blended transform of this pose
             hit_index = torch.empty(R, **i32)
             inv_index = torch.empty(R, **i32)
             cond = (smpl_pose[0, p, 3:] / np.pi).contiguous()          # multiply.py:270
@@ -326,8 +319,7 @@ class Multiply(nn.Module):
             hull_status = zp.take(len(persons), 8, dtype=torch.int32)
             work = torch.empty(len(persons), int(L.mp_obb_hull_device_work_bytes()), dtype=torch.uint8, device=dev)
             obb_all = torch.empty(len(persons), 16, **f32)
-            hip.check(L.mp_obb_hull_device(hip.ptr(verts_all), NUM_VERTS, len(persons), C.c_float(self.obb_inflate), hip.ptr(work),
-                                           hip.ptr(obb_all), hip.ptr(hull_status), st), "mp_obb_hull_device")
+            L.mp_obb_hull_device(verts_all, NUM_VERTS, len(persons), self.obb_inflate, work, obb_all, hull_status, st)
         for n, p in enumerate(persons):
             q = per[p]
             verts, hit_index, inv_index, cbound = q["verts"], q["hit_index"], q["inv_index"], q["cbound"]
@@ -337,8 +329,7 @@ class Multiply(nn.Module):
                 if hi.numel() == 0:      # multiply.py:262-263: no ray meets the box -> ray 0
                     hi = torch.zeros(1, dtype=torch.int32, device=dev)
                 hit_index[:hi.numel()] = hi
-                hip.check(L.mp_ray_hits_from_index(hip.ptr(hit_index), hi.numel(), R, hip.ptr(counts[n:n + 1]),
-                                                   hip.ptr(inv_index), st), "mp_ray_hits_from_index")
+                L.mp_ray_hits_from_index(hit_index, hi.numel(), R, counts[n:n + 1], inv_index, st)
             else:
                 if device_hull:
                     obb = obb_all[n]
@@ -355,23 +346,18 @@ class Multiply(nn.Module):
                         o_n, o_e = 3 * nh, 3 * (nh + nn_)
                         work = torch.empty(2 * nn_, dtype=torch.float64, device=dev)
                         obb = torch.empty(16, **f32)
-                        hip.check(L.mp_obb_hull(hip.ptr(hb), nh, hip.ptr(hb[o_n:]), nn_, hip.ptr(hb[o_e:]), hip.ptr(hb[o_e + 3 * ne:]),
-                                                hip.ptr(hb[o_e + 6 * ne:]), ne, C.c_float(self.obb_inflate), hip.ptr(work),
-                                                hip.ptr(obb), st), "mp_obb_hull")
+                        L.mp_obb_hull(hb, nh, hb[o_n:], nn_, hb[o_e:], hb[o_e + 3 * ne:], hb[o_e + 6 * ne:], ne, self.obb_inflate,
+                                      work, obb, st)
                 else:
                     obb = torch.empty(16, **f32)
-                    hip.check(L.mp_obb(hip.ptr(verts), C.c_float(self.obb_inflate), hip.ptr(obb), st), "mp_obb")
+                    L.mp_obb(verts, self.obb_inflate, obb, st)
                 if self.near_cull and not self.training:
                     # eval: rays of the box that never come within the outlier radius of the body are background, bit for bit
                     # (csrc/geom.hip k_ray_near_body); they are dropped before the sampler
-                    hip.check(L.mp_ray_cull_near(hip.ptr(dirs), hip.ptr(pose), hip.ptr(obb), hip.ptr(cbound), hip.ptr(far),
-                                                 hip.ptr(beta), C.c_float(rs.near), R, group, hip.ptr(hit_index),
-                                                 hip.ptr(counts[n:n + 1]), hip.ptr(inv_index), hip.ptr(scan_tmp), st),
-                              "mp_ray_cull_near")
+                    L.mp_ray_cull_near(dirs, pose, obb, cbound, far, beta, rs.near, R, group, hit_index, counts[n:n + 1],
+                                       inv_index, scan_tmp, st)
                 else:
-                    hip.check(L.mp_ray_cull(hip.ptr(dirs), hip.ptr(pose), hip.ptr(obb), R, group, hip.ptr(hit_index),
-                                            hip.ptr(counts[n:n + 1]), hip.ptr(inv_index), hip.ptr(scan_tmp), st),
-                              "mp_ray_cull")
+                    L.mp_ray_cull(dirs, pose, obb, R, group, hit_index, counts[n:n + 1], inv_index, scan_tmp, st)
             q["obb"] = obb
         if hull_status is not None:      # the one host sync of the call: sizes the per-person workspaces (+ the hulls' status)
             both = torch.cat([counts, hull_status[:, 3]]).tolist()
@@ -436,9 +422,8 @@ class Multiply(nn.Module):
                                    sdfnew.data_ptr(), betar.data_ptr(), active.data_ptr(), gflag.data_ptr(),
                                    zfinal.data_ptr(), iters.data_ptr(), any_active.data_ptr())
         train = draws is not None
-        t_rand = hip.ptr(draws["t_rand"]) if train else None
-        hip.check(L.mp_sampler_init(C.byref(cfg), C.byref(state), hip.ptr(cx["far"]), hip.ptr(pp["hit_index"]),
-                                    hip.ptr(pp["count"]), Rp, group, R, t_rand, st), "mp_sampler_init")
+        t_rand = draws["t_rand"] if train else None
+        L.mp_sampler_init(C.byref(cfg), C.byref(state), cx["far"], pp["hit_index"], pp["count"], Rp, group, R, t_rand, st)
         xc_new = torch.empty(Rp * NE, 3, **f32)
         work = torch.empty(Rp * NE, **i32)
         wcount = zp.take(rs.max_total_iters + 1, dtype=torch.int32)
@@ -454,18 +439,14 @@ class Multiply(nn.Module):
         cx, pp, Rp, NE, train = s["cx"], s["pp"], s["Rp"], s["NE"], s["train"]
         pk_sdf, any_active, wcount = s["pk_sdf"], s["any_active"], s["wcount"]
         with self._ph("sampler_warp"):
-            hip.check(L.mp_warp_inverse(None, hip.ptr(cx["dirs"]), hip.ptr(cx["pose"]), hip.ptr(pp["hit_index"]),
-                                        hip.ptr(pp["count"]), hip.ptr(s["znew"]), NE, NE, Rp, hip.ptr(pp["vsorted"]),
-                                        hip.ptr(pp["cbound"]), hip.ptr(pp["btab"]), 0 if train else 1,
-                                        hip.ptr(s["active"]), hip.ptr(any_active[it:it + 1]), hip.ptr(s["xc_new"]), None,
-                                        hip.ptr(s["sdfnew"]), hip.ptr(s["work"]),
-                                        hip.ptr(wcount[it:it + 1]), hip.ptr(s["bin_work"]) if train else None, st),
-                      "mp_warp_inverse")
+            L.mp_warp_inverse(None, cx["dirs"], cx["pose"], pp["hit_index"], pp["count"], s["znew"], NE, NE, Rp, pp["vsorted"],
+                              pp["cbound"], pp["btab"], 0 if train else 1, s["active"], any_active[it:it + 1], s["xc_new"], None,
+                              s["sdfnew"], s["work"], wcount[it:it + 1], s["bin_work"] if train else None, st)
         with self._ph("sampler_mlp_sdf"):
             self._sampler_sdf(s, it)
         with self._ph("sampler_bound"):
-            hip.check(L.mp_sampler_bound(C.byref(s["cfg"]), C.byref(s["state"]), hip.ptr(cx["beta"]), hip.ptr(pp["hit_index"]),
-                                         hip.ptr(pp["count"]), Rp, cx["group"], cx["R"], it, st), "mp_sampler_bound")
+            L.mp_sampler_bound(C.byref(s["cfg"]), C.byref(s["state"]), cx["beta"], pp["hit_index"], pp["count"], Rp, cx["group"],
+                               cx["R"], it, st)
 
     def resolved_sampler_sdf_mode(self, p=0):
         """`sampler_sdf_mode` with 'auto' resolved for person p's network (see __init__)"""
@@ -498,8 +479,7 @@ class Multiply(nn.Module):
                 # iteration's weights) the shared layers are used, anywhere else the state resolves the weights itself
                 lins = T.train_state(self).lins[id(imp)] if self.__dict__.get("_mp_in_train_graph") else None
                 fs = s["fs"] = T.fused_sdf_state(imp, lins).refresh(s["pp"]["cond"])
-            hip.check(L.mp_tf_sdf_val(hip.ptr(fs.wpack), hip.ptr(fs.bias_all), hip.ptr(s["xc_new"]), hip.ptr(s["work"]),
-                                      hip.ptr(wcount[it:it + 1]), s["Rp"] * s["NE"], hip.ptr(s["sdfnew"]), st), "mp_tf_sdf_val")
+            L.mp_tf_sdf_val(fs.wpack, fs.bias_all, s["xc_new"], s["work"], wcount[it:it + 1], s["Rp"] * s["NE"], s["sdfnew"], st)
             return
         if mode == "bf16x3-layerwise":          # the measurement path of tools/sampler_precision.py (host read per iteration)
             from . import train as T
@@ -517,20 +497,18 @@ class Multiply(nn.Module):
             raise ValueError(f"sampler_sdf_mode {mode!r}: expected 'f16x2', 'f16', 'bf16x3' or 'bf16x3-layerwise'")
         # 'f16x2': split activations on the same packed half-precision weights (csrc/mlp.hip k_mlp_sdf_x2)
         fn = L.mp_mlp_sdf_x2 if mode == "f16x2" else L.mp_mlp_sdf
-        hip.check(fn(C.byref(pk_sdf.net), hip.ptr(pk_sdf.wpack), hip.ptr(pk_sdf.bias),
-                     hip.ptr(s["xc_new"]), hip.ptr(s["work"]), hip.ptr(wcount[it:it + 1]), s["Rp"] * s["NE"],
-                     hip.ptr(s["sdfnew"]), st), "mp_mlp_sdf_x2" if mode == "f16x2" else "mp_mlp_sdf")
+        fn(C.byref(pk_sdf.net), pk_sdf.wpack, pk_sdf.bias, s["xc_new"], s["work"], wcount[it:it + 1], s["Rp"] * s["NE"],
+           s["sdfnew"], st)
 
     def _sampler_resample(self, s, it):
         """iteration `it`, second half: new samples where the bound is not met (or, converged, the final inverse-CDF draw)"""
         L, st = hip.lib(), hip.stream()
         cx, pp, draws = s["cx"], s["pp"], s["draws"]
-        u_final = hip.ptr(draws["u_final"]) if s["train"] else None
-        extra_idx = hip.ptr(draws["extra_idx"]) if s["train"] else None
+        u_final = draws["u_final"] if s["train"] else None
+        extra_idx = draws["extra_idx"] if s["train"] else None
         with self._ph("sampler_resample"):
-            hip.check(L.mp_sampler_resample(C.byref(s["cfg"]), C.byref(s["state"]), hip.ptr(cx["beta"]), hip.ptr(cx["far"]),
-                                            hip.ptr(pp["hit_index"]), hip.ptr(pp["count"]), s["Rp"], cx["group"], cx["R"], it,
-                                            u_final, extra_idx, st), "mp_sampler_resample")
+            L.mp_sampler_resample(C.byref(s["cfg"]), C.byref(s["state"]), cx["beta"], cx["far"], pp["hit_index"], pp["count"],
+                                  s["Rp"], cx["group"], cx["R"], it, u_final, extra_idx, st)
 
     def _sampler_close(self, s):
         s["pp"]["_sampler_keep"] = tuple(s[k] for k in ("zs", "sdfs", "nz", "znew", "sdfnew", "betar", "active", "gflag",
@@ -581,8 +559,6 @@ class Multiply(nn.Module):
         every ray is sampled (no box cull), the convergence vote spans the call.  ray_dirs (R,3) unit vectors, cam_loc (3,)
         or (R,3) with equal rows, cond the pose conditioning (69,) / {'smpl': (1,69)}, smpl_tfs (1,24,4,4), smpl_verts
         (1,6890,3) posed vertices.  -> z_vals (R, N_samples + N_samples_extra + 2) sorted depths."""
-        L = hip.lib()
-        st = hip.stream()
         dev = self.density.beta.device
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -596,13 +572,8 @@ class Multiply(nn.Module):
         far = (-od + torch.sqrt((od * od - (cam @ cam - self.sdf_bounding_sphere ** 2)).clamp_min(0.0))).contiguous()
         verts = smpl_verts.detach().to(dev).float().reshape(-1, 3).contiguous()
         tfs = smpl_tfs.detach().to(dev).float().reshape(24, 16).contiguous()
-        d = self.deformer_list[person_id]
-        vsorted = torch.empty(hip.KNN_NC * hip.KNN_CLUSTER, 4, **f32)
-        cbound = torch.empty(hip.KNN_CB_ROWS, 4, **f32)
-        hip.check(L.mp_knn_build(hip.ptr(verts), hip.ptr(d.knn_perm), hip.ptr(vsorted), hip.ptr(cbound), st), "mp_knn_build")
-        btab = torch.empty(verts.shape[0], 12, **f32)
-        hip.check(L.mp_blend_table(hip.ptr(self.smpl_server_list[person_id].tables.lbs_weights), hip.ptr(tfs), verts.shape[0],
-                                   hip.ptr(btab), st), "mp_blend_table")
+        vsorted, cbound = hip.knn_tables(verts, self.deformer_list[person_id].knn_perm)
+        btab = hip.blend_table(self.smpl_server_list[person_id].tables.lbs_weights, tfs)
         if isinstance(cond, dict):
             cond = cond["smpl"]
         cvec = cond.detach().to(dev).float().reshape(-1).contiguous()
@@ -650,37 +621,28 @@ class Multiply(nn.Module):
             nn_posed = torch.empty(npts, **i32)
             wc2 = wcount[rs.max_total_iters:]
             ph = self._ph("shade_warp"); ph.__enter__()
-            hip.check(L.mp_warp_inverse_shade(hip.ptr(dirs), hip.ptr(pose), hip.ptr(pp["hit_index"]), hip.ptr(pp["count"]),
-                                              hip.ptr(zfinal), NZ, S, Rp, hip.ptr(pp["vsorted"]), hip.ptr(pp["cbound"]),
-                                              hip.ptr(pp["btab"]), 1, hip.ptr(beta), hip.ptr(xc), None,
-                                              hip.ptr(need), hip.ptr(sdf), hip.ptr(work2), hip.ptr(wc2), hip.ptr(nn_posed), None, st),
-                      "mp_warp_inverse_shade")
+            L.mp_warp_inverse_shade(dirs, pose, pp["hit_index"], pp["count"], zfinal, NZ, S, Rp, pp["vsorted"], pp["cbound"],
+                                    pp["btab"], 1, beta, xc, None, need, sdf, work2, wc2, nn_posed, None, st)
             ph.__exit__()
             jinv = torch.empty(npts, 9, **f32)
             ph = self._ph("shade_jacobian"); ph.__enter__()
-            hip.check(L.mp_warp_jacobian(hip.ptr(xc), hip.ptr(need), hip.ptr(pp["count"]), Rp, S, 0,
-                                         hip.ptr(dfm.vsorted_c), hip.ptr(dfm.cbound_c), hip.ptr(pp["btab"]),
-                                         hip.ptr(jinv), None, hip.ptr(nn_posed), hip.ptr(dfm.verts_c_flat), st), "mp_warp_jacobian")
+            L.mp_warp_jacobian(xc, need, pp["count"], Rp, S, 0, dfm.vsorted_c, dfm.cbound_c, pp["btab"], jinv, None, nn_posed,
+                               dfm.verts_c_flat, st)
             ph.__exit__()
             pk_full = hip.packed(imp, "full", 2)
             pk_full.refresh(pp["cond"])
             pk_col = hip.packed(ren, "color", 2)
-            pe = ren.__dict__.get("_mp_pose_embed") or hip.PoseEmbed(ren)
-            ren.__dict__["_mp_pose_embed"] = pe
-            pk_col.refresh(pe(pp["cond"]))
+            pk_col.refresh(hip.pose_embed(ren)(pp["cond"]))
             feat = torch.empty(((npts + 255) // 256) * 4 * 8 * 4 * 1024, dtype=torch.uint8, device=dev)
             if self.shade_mode == "reverse":     # value sweep (parks the sigmoids) + reverse sweep for the normals
                 with self._ph("mlp_shade"):
                     hip.shade_rev_launch(pk_full, hip.grad_net(imp), xc, jinv, work2, wc2, npts, sdf, nrm, feat)
             else:
                 with self._ph("mlp_shade"):
-                    hip.check(L.mp_mlp_shade(C.byref(pk_full.net), hip.ptr(pk_full.wpack), hip.ptr(pk_full.bias), hip.ptr(xc),
-                                             hip.ptr(jinv), hip.ptr(work2), hip.ptr(wc2), npts, hip.ptr(sdf), hip.ptr(nrm),
-                                             hip.ptr(feat), st), "mp_mlp_shade")
+                    L.mp_mlp_shade(C.byref(pk_full.net), pk_full.wpack, pk_full.bias, xc, jinv, work2, wc2, npts, sdf, nrm, feat,
+                                   st)
             with self._ph("mlp_color"):
-                hip.check(L.mp_mlp_color(C.byref(pk_col.net), hip.ptr(pk_col.wpack), hip.ptr(pk_col.bias), hip.ptr(xc),
-                                         hip.ptr(nrm), hip.ptr(feat), hip.ptr(work2), hip.ptr(wc2), npts, hip.ptr(rgb),
-                                         st), "mp_mlp_color")
+                L.mp_mlp_color(C.byref(pk_col.net), pk_col.wpack, pk_col.bias, xc, nrm, feat, work2, wc2, npts, rgb, st)
             stats["iters"].append(iters); stats["n_sdf_evals"].append(wcount)
             per[p].update(zfinal=zfinal, sdf=sdf, rgb=rgb, nrm=nrm, xc=xc, work2=work2, wc2=wc2)
 
@@ -731,10 +693,8 @@ class Multiply(nn.Module):
         normal_values = torch.empty(R, 3, **f32); acc_map = torch.empty(R, **f32)
         acc_person = torch.empty(R, len(persons), **f32); bg_T = torch.empty(R, **f32)
         with self._ph("composite"):
-            hip.check(L.mp_composite(R, len(persons), NZ, hip.ptr(t_inv), hip.ptr(t_z), hip.ptr(t_sdf), hip.ptr(t_rgb),
-                                     hip.ptr(t_nrm), hip.ptr(cx["beta"]), hip.ptr(bg_rgb) if bg_rgb is not None else None,
-                                     hip.ptr(rgb_values), hip.ptr(fg_rgb_values), hip.ptr(normal_values), hip.ptr(acc_map),
-                                     hip.ptr(acc_person), hip.ptr(bg_T), hip.stream()), "mp_composite")
+            L.mp_composite(R, len(persons), NZ, t_inv, t_z, t_sdf, t_rgb, t_nrm, cx["beta"], bg_rgb, rgb_values, fg_rgb_values,
+                           normal_values, acc_map, acc_person, bg_T, hip.stream())
         out = {"acc_map": acc_map, "acc_person_list": acc_person, "rgb_values": rgb_values,
                "fg_rgb_values": fg_rgb_values, "normal_values": normal_values}
         return out, bg_T, (t_inv, t_z, t_sdf, t_rgb, t_nrm)

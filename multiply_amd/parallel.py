@@ -211,7 +211,6 @@ def render_person_sharded(model, input, canonical_pose=False, group=None, exchan
     output dict for ITS ray slice [rank * ceil(R / world), ...) (use gather_rays to assemble the image).  Identical results to
     the single-process call with convergence groups that do not straddle a slice (the sampler's vote is per person and per
     group).  exchange_events (a list): (start, end) timing events around every exchange are appended (bench.py --mode person)."""
-    import ctypes as C
     from . import hip
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     L = hip.lib()
@@ -269,8 +268,7 @@ def render_person_sharded(model, input, canonical_pose=False, group=None, exchan
     K = input["intrinsics"].to(dev).float().reshape(16).contiguous()
     pose = input["pose"].to(dev).float().reshape(16).contiguous()
     dirs = torch.empty(n_my, 3, **f32); far = torch.empty(n_my, **f32)
-    hip.check(L.mp_ray_setup(hip.ptr(uv), hip.ptr(K), hip.ptr(pose), n_my, C.c_float(model.sdf_bounding_sphere),
-                             hip.ptr(dirs), hip.ptr(far), st), "mp_ray_setup")
+    L.mp_ray_setup(uv, K, pose, n_my, model.sdf_bounding_sphere, dirs, far, st)
     bg_rgb = None
     if input.get("idx", None) is not None:
         key = "image_id" if "image_id" in input else "idx"
@@ -281,10 +279,8 @@ def render_person_sharded(model, input, canonical_pose=False, group=None, exchan
                                 pose.reshape(4, 4)[:3, 3].contiguous(), z_bg, code, radius=model.sdf_bounding_sphere)
     out = {k: torch.empty(n_my, 3, **f32) for k in ("rgb_values", "fg_rgb_values", "normal_values")}
     acc_map = torch.empty(n_my, **f32); acc_person = torch.empty(n_my, P, **f32); bg_T = torch.empty(n_my, **f32)
-    hip.check(L.mp_composite(n_my, P, NZ, *[hip.ptr(t) for t in tabs], hip.ptr(beta),
-                             hip.ptr(bg_rgb) if bg_rgb is not None else None, hip.ptr(out["rgb_values"]),
-                             hip.ptr(out["fg_rgb_values"]), hip.ptr(out["normal_values"]), hip.ptr(acc_map),
-                             hip.ptr(acc_person), hip.ptr(bg_T), st), "mp_composite")
+    L.mp_composite(n_my, P, NZ, *tabs, beta, bg_rgb, out["rgb_values"], out["fg_rgb_values"], out["normal_values"], acc_map,
+                   acc_person, bg_T, st)
     torch.cuda.synchronize()                                  # the pointer tables / blocks above must outlive the launch
     out.update(acc_map=acc_map, acc_person_list=acc_person)
     return out, (s0, s0 + n_my)

@@ -183,9 +183,8 @@ class Renderer:
         p2f = torch.empty(H, W, dtype=torch.int32, device=self.device)
         bary = torch.empty(H, W, 3, dtype=torch.float32, device=self.device)
         cam = self._cam16()
-        hip.check(hip.lib().mp_raster_zbuf(hip.ptr(v), v.shape[0], hip.ptr(f), f.shape[0], C.cast(cam, C.c_void_p),
-                                           Z_CLIP, H, W, hip.ptr(self._keys), hip.ptr(self._big), hip.ptr(zbuf),
-                                           hip.ptr(p2f), hip.ptr(bary), hip.stream()), "mp_raster_zbuf")
+        hip.lib().mp_raster_zbuf(v, v.shape[0], f, f.shape[0], C.cast(cam, C.c_void_p), Z_CLIP, H, W, self._keys, self._big, zbuf,
+                                 p2f, bary, hip.stream())
         return Fragments(zbuf[None, :, :, None], p2f.long()[None, :, :, None], bary[None, :, :, None, :])
 
     def _depth_with_grad(self, verts, faces, frag):
@@ -257,8 +256,8 @@ class Renderer:
         offsets = torch.empty(T + 1, dtype=torch.int32, device=self.device)
         cam = self._cam16()
         L = hip.lib()
-        hip.check(L.mp_raster_soft_bins(hip.ptr(v), v.shape[0], hip.ptr(f), f.shape[0], C.cast(cam, C.c_void_p), Z_CLIP, H, W,
-                                        blur, hip.ptr(tile_n), hip.ptr(offsets), hip.stream()), "mp_raster_soft_bins")
+        L.mp_raster_soft_bins(v, v.shape[0], f, f.shape[0], C.cast(cam, C.c_void_p), Z_CLIP, H, W, blur, tile_n, offsets,
+                              hip.stream())
         total = int(offsets[T])
         if total < 0:
             raise RuntimeError("soft render: the tile lists exceed 2^31 entries")
@@ -266,10 +265,8 @@ class Renderer:
         image = torch.empty(H, W, 4, dtype=torch.float32, device=self.device)
         sel = torch.empty(H, W, K, dtype=torch.int32, device=self.device) if want_sel else None
         bg = (C.c_float * 3)(1.0, 1.0, 1.0)                                       # BlendParams' default background
-        hip.check(L.mp_raster_soft(hip.ptr(v), v.shape[0], hip.ptr(f), f.shape[0], hip.ptr(c), C.cast(cam, C.c_void_p), Z_CLIP,
-                                   H, W, sigma, gamma, blur, K, 1.0, 100.0, C.cast(bg, C.c_void_p),
-                                   hip.ptr(tile_n), hip.ptr(offsets), hip.ptr(lst), hip.ptr(image),
-                                   hip.ptr(sel) if want_sel else None, hip.stream()), "mp_raster_soft")
+        L.mp_raster_soft(v, v.shape[0], f, f.shape[0], c, C.cast(cam, C.c_void_p), Z_CLIP, H, W, sigma, gamma, blur, K, 1.0,
+                         100.0, C.cast(bg, C.c_void_p), tile_n, offsets, lst, image, sel if want_sel else None, hip.stream())
         return image, sel
 
     def _soft_with_grad(self, verts, faces, colors, image, sel):

@@ -209,11 +209,9 @@ class SMPLServer(nn.Module):
         """raw launch: params86 (86,) device -> preallocated verts (V,3), tfs (24,4,4), joints (24,3); `work` (3V + 1024
         floats) defaults to the server's own buffer"""
         t = self.tables
-        hip.check(hip.lib().mp_smpl_pose(hip.ptr(t.v_template), hip.ptr(t.shapedirs), hip.ptr(t.posedirs),
-                                         hip.ptr(t.j_regressor), hip.ptr(t.lbs_weights), hip.ptr(t.parents),
-                                         hip.ptr(params86), None if absolute else hip.ptr(self.tfs_c_inv), hip.ptr(verts),
-                                         hip.ptr(tfs), hip.ptr(joints), hip.ptr(self._work if work is None else work),
-                                         hip.stream()), "mp_smpl_pose")
+        hip.lib().mp_smpl_pose(t.v_template, t.shapedirs, t.posedirs, t.j_regressor, t.lbs_weights, t.parents, params86,
+                               None if absolute else self.tfs_c_inv, verts, tfs, joints, self._work if work is None else work,
+                               hip.stream())
 
     def pose_backward(self, params86, work=None, dverts=None, djoints=None, dall_joints=None, dtfs=None):
         """Adjoint of forward(absolute=False) -> d params (86,) = [scale, transl 3, thetas 72, betas 10].  Upstreams (any may
@@ -237,16 +235,12 @@ class SMPLServer(nn.Module):
         if dverts is not None:
             dlbs = torch.empty(hip.SMPL_DLBS, **f32)
             scratch = torch.empty(hip.SMPL_VBWD_SCRATCH, **f32)
-            hip.check(hip.lib().mp_smpl_verts_bwd(hip.ptr(t.posedirs), hip.ptr(t.shapedirs), hip.ptr(t.lbs_weights),
-                                                  hip.ptr(prm), hip.ptr(work), hip.ptr(dverts), hip.ptr(scratch),
-                                                  hip.ptr(dlbs), hip.stream()), "mp_smpl_verts_bwd")
+            hip.lib().mp_smpl_verts_bwd(t.posedirs, t.shapedirs, t.lbs_weights, prm, work, dverts, scratch, dlbs, hip.stream())
             dA, dpf, din = dlbs[:NUM_JOINTS * 16], dlbs[NUM_JOINTS * 16:NUM_JOINTS * 16 + 207], dlbs[NUM_JOINTS * 16 + 207:]
         dprm = torch.empty(86, **f32)
         rest = work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS]          # csrc/geom.hip W_J
-        hip.check(hip.lib().mp_smpl_pose_bwd_lbs(hip.ptr(t.parents), hip.ptr(prm), hip.ptr(self.tfs_c_inv), hip.ptr(rest),
-                                                 hip.ptr(t.j_shapedirs), hip.ptr(dtfs), hip.ptr(dA), hip.ptr(djoints),
-                                                 hip.ptr(dpf), hip.ptr(din), hip.ptr(dprm), hip.stream()),
-                  "mp_smpl_pose_bwd_lbs")
+        hip.lib().mp_smpl_pose_bwd_lbs(t.parents, prm, self.tfs_c_inv, rest, t.j_shapedirs, dtfs, dA, djoints, dpf, din, dprm,
+                                       hip.stream())
         return dprm
 
     def rest_joints(self):

@@ -24,20 +24,7 @@ import torch.distributed as dist
 from . import hip
 
 F32 = torch.float32
-
-
-def _p(t):
-    return hip.ptr(t)
-
-
-_DEBUG_SYNC = bool(int(os.environ.get("MP_DEBUG_SYNC", "0")))
-
-
-def _chk(code, what):
-    hip.check(code, what)
-    if _DEBUG_SYNC:                      # debugging aid: attribute asynchronous faults to the launch that caused them
-        torch.cuda.synchronize()
-        print("[mp sync ok]", what, flush=True)
+_p, _chk = hip.ptr, hip.check      # the binding's helpers under their former names: tests/test_train_gpu.py and tools/ call them; no launch here does
 
 
 # Arithmetic of the training GEMMs (csrc/gemm.hip):
@@ -50,18 +37,18 @@ TRAIN_PRECISION = os.environ.get("MP_TRAIN_PRECISION", "bf16x3")
 
 def gemm_nt(A, lda, B, ldb, Cm, ldc, M, N, K, bias=None, bias_rows=0, accumulate=False, relu=False):
     if TRAIN_PRECISION == "f32":
-        fn, name = hip.lib().mp_gemm_nt, "mp_gemm_nt"
+        fn = hip.lib().mp_gemm_nt
     elif TRAIN_PRECISION == "bf16x3":
-        fn, name = hip.lib().mp_gemm_nt_bf16x3, "mp_gemm_nt_bf16x3"
+        fn = hip.lib().mp_gemm_nt_bf16x3
     else:
         raise ValueError(f"MP_TRAIN_PRECISION {TRAIN_PRECISION!r}: expected 'bf16x3' or 'f32'")
-    _chk(fn(A, lda, B, ldb, Cm, ldc, M, N, K, bias, bias_rows, int(accumulate), int(relu), hip.stream()), name)
+    fn(A, lda, B, ldb, Cm, ldc, M, N, K, bias, bias_rows, int(accumulate), int(relu), hip.stream())
 
 
 def gemm_tn(A, lda, B, ldb, Cm, ldc, M, N, K, colsum=None, colsum_rows=0):
     """Cm[M,N] += A[K,M]^T B[K,N];  colsum[M] += column sums of A's first colsum_rows rows (the bias gradient)"""
     fn = hip.lib().mp_gemm_tn if TRAIN_PRECISION == "f32" else hip.lib().mp_gemm_tn_bf16x3
-    _chk(fn(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows, hip.stream()), "mp_gemm_tn")
+    fn(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows, hip.stream())
 
 
 class MpTnGroup(C.Structure):
@@ -71,7 +58,7 @@ class MpTnGroup(C.Structure):
 
 
 def tn_group(A, lda, B, ldb, Cm, ldc, M, N, K, colsum=None, colsum_rows=0):
-    """one contraction of a grouped launch (mp_gemm_tn_bf16x3_grouped); pointers as returned by _p() / off()"""
+    """one contraction of a grouped launch (mp_gemm_tn_bf16x3_grouped); pointers as returned by hip.ptr() / off()"""
     return MpTnGroup(A.value, B.value, Cm.value, colsum.value if colsum is not None else None, lda, ldb, ldc, M, N, K,
                      colsum_rows, 0)
 
@@ -81,7 +68,7 @@ def gemm_tn_grouped(groups):
     for i in range(0, len(groups), 24):
         chunk = groups[i:i + 24]
         arr = (MpTnGroup * len(chunk))(*chunk)
-        _chk(hip.lib().mp_gemm_tn_bf16x3_grouped(arr, len(chunk), hip.stream()), "mp_gemm_tn_bf16x3_grouped")
+        hip.lib().mp_gemm_tn_bf16x3_grouped(arr, len(chunk), hip.stream())
 
 
 def _big_empty(n_floats, dev, grain=1 << 26, cap=None, cap_bytes=6 << 30):
@@ -126,8 +113,7 @@ class LinW:
         dev = self.v.device
         self.W = torch.empty(self.out_dim, self.in_dim, dtype=F32, device=dev)
         self.WT = torch.empty(self.in_dim, self.out_dim, dtype=F32, device=dev)
-        _chk(hip.lib().mp_tr_wn_fwd(_p(self.v), _p(self.g), self.out_dim, self.in_dim, _p(self.W), _p(self.WT),
-                                    hip.stream()), "mp_tr_wn_fwd")
+        hip.lib().mp_tr_wn_fwd(self.v, self.g, self.out_dim, self.in_dim, self.W, self.WT, hip.stream())
         self.dW = torch.zeros(self.out_dim, self.in_dim, dtype=F32, device=dev)
         self.db = torch.zeros(self.out_dim, dtype=F32, device=dev)
 
@@ -135,8 +121,7 @@ class LinW:
         """gradients in the order of `params()`"""
         dv = torch.empty_like(self.v)
         dg = torch.empty(self.out_dim, 1, dtype=F32, device=self.v.device) if self.wn else None
-        _chk(hip.lib().mp_tr_wn_bwd(_p(self.v), _p(self.g), self.out_dim, self.in_dim, _p(self.dW), _p(dv),
-                                    _p(dg) if self.wn else None, hip.stream()), "mp_tr_wn_bwd")
+        hip.lib().mp_tr_wn_bwd(self.v, self.g, self.out_dim, self.in_dim, self.dW, dv, dg if self.wn else None, hip.stream())
         return [dg, dv, self.db] if self.wn else [dv, self.db]
 
     def params(self):
@@ -162,24 +147,23 @@ def launch_tn_groups(groups):
         gemm_tn_grouped(groups)
     else:                                   # exact-fp32 cross-check: one launch per contraction
         for g in groups:
-            gemm_tn(C.c_void_p(g.A), g.lda, C.c_void_p(g.B), g.ldb, C.c_void_p(g.C), g.ldc, g.M, g.N, g.K,
-                    C.c_void_p(g.colsum) if g.colsum else None, g.colsum_rows)
+            gemm_tn(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.M, g.N, g.K, g.colsum, g.colsum_rows)
 
 
 def _layer0_adjoint(lw0, dZ0, X0, ldx, kx, rows, bias_rows, c0, n_h, hvec):
     """Layer 0 of a network whose conditioning is hoisted into the bias (b0 = b + W0[:, c0:c0+n_h] hvec): the weight gradient
     dW0[:, :kx] += dZ0^T X0 over `rows` rows, the bias gradient over the first `bias_rows`, dW0[:, c0:c0+n_h] += db0 (x) hvec;
-    returns d hvec = W0[:, c0:c0+n_h]^T db0.  dZ0 [rows][out], X0 [rows][ldx]: device pointers."""
+    returns d hvec = W0[:, c0:c0+n_h]^T db0.  dZ0 [rows][out], X0 [rows][ldx]: tensors or device pointers."""
     out, dev = lw0.out_dim, lw0.W.device
     # layer 0's bias gradient of THIS evaluation on its own (db0), then added to the accumulator: the hoisted
     # conditioning's adjoint below must not see what other evaluations of the same network left in lw0.db
     # (the zero-pose regulariser evaluates a network under two conditionings in one sweep)
     db0 = _zeros(out, device=dev)
-    gemm_tn(dZ0, out, X0, ldx, _p(lw0.dW), lw0.in_dim, out, kx, rows, _p(db0), bias_rows)
+    gemm_tn(dZ0, out, X0, ldx, lw0.dW, lw0.in_dim, out, kx, rows, db0, bias_rows)
     lw0.db.add_(db0)
-    _chk(hip.lib().mp_tr_hoist_bwd(_p(db0), out, lw0.in_dim, c0, n_h, _p(hvec), _p(lw0.dW), hip.stream()), "mp_tr_hoist_bwd")
+    hip.lib().mp_tr_hoist_bwd(db0, out, lw0.in_dim, c0, n_h, hvec, lw0.dW, hip.stream())
     dh = _zeros(n_h, device=dev)
-    gemm_tn(_p(db0), 1, off(lw0.W, c0), lw0.in_dim, _p(dh), n_h, 1, n_h, out)
+    gemm_tn(db0, 1, off(lw0.W, c0), lw0.in_dim, dh, n_h, 1, n_h, out)
     return dh
 
 
@@ -224,7 +208,7 @@ class _LayerwiseImplicit(_SdfEvaluator):
         self.E = E = net.embed_dim
         self.lins = lins if lins is not None else [LinW(l) for l in net.layers()]
         self.IN = torch.empty(rows, E, dtype=F32, device=dev)
-        _chk(L.mp_tr_pe(_p(x), net.d_in, P, net.multires, int(fwd), C.c_float(1.0), _p(self.IN), E, 0, st), "mp_tr_pe")
+        L.mp_tr_pe(x, net.d_in, P, net.multires, int(fwd), 1.0, self.IN, E, 0, st)
         self.Z, self.X = [], []          # pre-activations and layer inputs
         r2 = 1.0 / math.sqrt(2.0)
         Pm = P if fwd else 0
@@ -233,25 +217,23 @@ class _LayerwiseImplicit(_SdfEvaluator):
             Z = torch.empty(rows, out, dtype=F32, device=dev)
             if l == 0:
                 self.b0 = torch.empty(out, dtype=F32, device=dev)
-                _chk(L.mp_tr_hoist_fwd(_p(lw.W), out, lw.in_dim, _p(lw.b), E, net.cond_dim, _p(cond_vec), _p(self.b0), st),
-                     "mp_tr_hoist_fwd")
+                L.mp_tr_hoist_fwd(lw.W, out, lw.in_dim, lw.b, E, net.cond_dim, cond_vec, self.b0, st)
                 Xl = self.IN
-                gemm_nt(_p(Xl), E, _p(lw.W), lw.in_dim, _p(Z), out, rows, out, E, _p(self.b0), P)
+                gemm_nt(Xl, E, lw.W, lw.in_dim, Z, out, rows, out, E, self.b0, P)
             else:
                 Zp, po = self.Z[l - 1], self.lins[l - 1].out_dim
                 skip = l in net.skip_in
                 Xl = torch.empty(rows, po + E if skip else po, dtype=F32, device=dev)
-                _chk(L.mp_tr_softplus_fwd(_p(Zp), po, rows, po, Pm, C.c_float(r2 if skip else 1.0), _p(Xl), Xl.shape[1], 0, st),
-                     "mp_tr_softplus_fwd")
+                L.mp_tr_softplus_fwd(Zp, po, rows, po, Pm, r2 if skip else 1.0, Xl, Xl.shape[1], 0, st)
                 if skip:
-                    _chk(L.mp_tr_copy_cols(_p(self.IN), E, 0, _p(Xl), po + E, po, rows, E, C.c_float(r2), 0, st), "mp_tr_copy_cols")
-                gemm_nt(_p(Xl), Xl.shape[1], _p(lw.W), lw.in_dim, _p(Z), out, rows, out, lw.in_dim, _p(lw.b), P)
+                    L.mp_tr_copy_cols(self.IN, E, 0, Xl, po + E, po, rows, E, r2, 0, st)
+                gemm_nt(Xl, Xl.shape[1], lw.W, lw.in_dim, Z, out, rows, out, lw.in_dim, lw.b, P)
             self.Z.append(Z)
             self.X.append(Xl)
         self.out = self.Z[-1]            # [rows][257]
         self.feat_ptr = off(self.out, 1)
         self.sdf = torch.empty(P, dtype=F32, device=dev)
-        _chk(L.mp_tr_copy_cols(_p(self.out), 257, 0, _p(self.sdf), 1, 0, P, 1, C.c_float(1.0), 0, st), "mp_tr_copy_cols")
+        L.mp_tr_copy_cols(self.out, 257, 0, self.sdf, 1, 0, P, 1, 1.0, 0, st)
 
     def new_dfeat(self, n=0):
         return torch.zeros(self.rows, 257, dtype=F32, device=self.x.device)
@@ -274,38 +256,37 @@ class _LayerwiseImplicit(_SdfEvaluator):
             lw, Xl = self.lins[l], self.X[l]
             out, po = lw.out_dim, self.lins[l - 1].out_dim
             if grouped and TRAIN_PRECISION == "bf16x3" and out == 256 and lw.in_dim == 256:
-                groups.append(tn_group(_p(dZ), out, _p(Xl), 256, _p(lw.dW), lw.in_dim, out, 256, rows, _p(lw.db), P))
+                groups.append(tn_group(hip.ptr(dZ), out, hip.ptr(Xl), 256, hip.ptr(lw.dW), lw.in_dim, out, 256, rows,
+                                       hip.ptr(lw.db), P))
                 held.append(dZ)
             else:
-                gemm_tn(_p(dZ), out, _p(Xl), lw.in_dim, _p(lw.dW), lw.in_dim, out, lw.in_dim, rows, _p(lw.db), P)
+                gemm_tn(dZ, out, Xl, lw.in_dim, lw.dW, lw.in_dim, out, lw.in_dim, rows, lw.db, P)
             dX = torch.empty(rows, lw.in_dim, dtype=F32, device=dev)
-            gemm_nt(_p(dZ), out, _p(lw.WT), out, _p(dX), lw.in_dim, rows, lw.in_dim, out)
+            gemm_nt(dZ, out, lw.WT, out, dX, lw.in_dim, rows, lw.in_dim, out)
             skip = l in net.skip_in
             if want_dx and skip:      # the skip connection's copy of the encoded input
-                _chk(L.mp_tr_copy_cols(_p(dX), lw.in_dim, po, _p(dIN), E, 0, rows, E, C.c_float(r2), 1, st), "mp_tr_copy_cols")
+                L.mp_tr_copy_cols(dX, lw.in_dim, po, dIN, E, 0, rows, E, r2, 1, st)
             dZp = torch.empty(rows, po, dtype=F32, device=dev)
-            scale = C.c_float(r2 if skip else 1.0)
+            scale = r2 if skip else 1.0
             if dS is None:
-                _chk(L.mp_tr_softplus_bwd(_p(self.Z[l - 1]), po, rows, po, Pm, scale, _p(dX), lw.in_dim, 0, _p(dZp), po, st),
-                     "mp_tr_softplus_bwd")
+                L.mp_tr_softplus_bwd(self.Z[l - 1], po, rows, po, Pm, scale, dX, lw.in_dim, 0, dZp, po, st)
             else:
-                _chk(L.mp_tr_dz(_p(self.Z[l - 1]), po, P, po, _p(dX), lw.in_dim, scale, _p(dS[l - 1]), po, _p(dZp), po, st),
-                     "mp_tr_dz")
+                L.mp_tr_dz(self.Z[l - 1], po, P, po, dX, lw.in_dim, scale, dS[l - 1], po, dZp, po, st)
             dZ = dZp
         lw0 = self.lins[0]
-        dcond = _layer0_adjoint(lw0, _p(dZ), _p(self.IN), E, E, rows, P, E, net.cond_dim, self.cond)
+        dcond = _layer0_adjoint(lw0, dZ, self.IN, E, E, rows, P, E, net.cond_dim, self.cond)
         if want_dx:
-            gemm_nt(_p(dZ), lw0.out_dim, _p(lw0.WT), lw0.out_dim, _p(dIN), E, rows, E, lw0.out_dim, accumulate=True)
+            gemm_nt(dZ, lw0.out_dim, lw0.WT, lw0.out_dim, dIN, E, rows, E, lw0.out_dim, accumulate=True)
             if self.dx is None:
                 self.dx = torch.zeros(P, net.d_in, dtype=F32, device=dev)
-            _chk(L.mp_tr_pe_bwd(_p(self.x), net.d_in, P, net.multires, int(self.fwd), _p(dIN), E, _p(self.dx), st), "mp_tr_pe_bwd")
+            L.mp_tr_pe_bwd(self.x, net.d_in, P, net.multires, int(self.fwd), dIN, E, self.dx, st)
         if groups:
             gemm_tn_grouped(groups)
         return dcond
 
     def _dsdf_into(self, dZ, dsdf):
         """d sdf -> column 0 of the value rows of dZ [rows][257]"""
-        _chk(hip.lib().mp_tr_copy_cols(_p(dsdf), 1, 0, _p(dZ), 257, 0, self.P, 1, C.c_float(1.0), 0, hip.stream()), "mp_tr_copy_cols")
+        hip.lib().mp_tr_copy_cols(dsdf, 1, 0, dZ, 257, 0, self.P, 1, 1.0, 0, hip.stream())
 
 
 class ImplicitTrain(_LayerwiseImplicit):
@@ -319,8 +300,7 @@ class ImplicitTrain(_LayerwiseImplicit):
             L, P = hip.lib(), self.P
             self.grad = torch.empty(P, 3, dtype=F32, device=x.device)
             for k in range(3):           # column 0 of tangent block k
-                _chk(L.mp_tr_copy_cols(off(self.out, (k + 1) * P * 257), 257, 0, _p(self.grad), 3, k, P, 1, C.c_float(1.0), 0,
-                                       hip.stream()), "mp_tr_copy_cols")
+                L.mp_tr_copy_cols(off(self.out, (k + 1) * P * 257), 257, 0, self.grad, 3, k, P, 1, 1.0, 0, hip.stream())
 
     def backward(self, dfeat, dsdf=None, dgrad=None, want_dx=False, tn_groups=None):
         L, P, dZ = hip.lib(), self.P, dfeat
@@ -329,8 +309,7 @@ class ImplicitTrain(_LayerwiseImplicit):
             self._dsdf_into(dZ, dsdf)
         if dgrad is not None:
             for k in range(3):
-                _chk(L.mp_tr_copy_cols(_p(dgrad), 3, k, off(dZ, (k + 1) * P * 257), 257, 0, P, 1, C.c_float(1.0), 0, hip.stream()),
-                     "mp_tr_copy_cols")
+                L.mp_tr_copy_cols(dgrad, 3, k, off(dZ, (k + 1) * P * 257), 257, 0, P, 1, 1.0, 0, hip.stream())
         self.dx = None
         return self._value_adjoint(dZ, want_dx=want_dx, grouped=True)
 
@@ -362,24 +341,23 @@ class ImplicitTrainRev(_LayerwiseImplicit):
         self.V = [None] * nh
         self.T = [None] * nh                          # T[l] = V_l W_l  (U_{l-1} = scale_l * T[l][:, :out_{l-1}])
         self.V[nh - 1] = torch.empty(P, lins[nh - 1].out_dim, **f32)
-        _chk(L.mp_tr_sigmul(_p(self.Z[nh - 1]), lins[nh - 1].out_dim, P, lins[nh - 1].out_dim, None, 0, _p(self.w8),
-                            C.c_float(1.0), _p(self.V[nh - 1]), lins[nh - 1].out_dim, st), "mp_tr_sigmul")
+        L.mp_tr_sigmul(self.Z[nh - 1], lins[nh - 1].out_dim, P, lins[nh - 1].out_dim, None, 0, self.w8, 1.0, self.V[nh - 1],
+                       lins[nh - 1].out_dim, st)
         self.Gpe = torch.zeros(P, E, **f32)
         for l in range(nh - 1, 0, -1):
             lw, po = lins[l], lins[l - 1].out_dim
             T = torch.empty(P, lw.in_dim, **f32)
-            gemm_nt(_p(self.V[l]), lw.out_dim, _p(lw.WT), lw.out_dim, _p(T), lw.in_dim, P, lw.in_dim, lw.out_dim)
+            gemm_nt(self.V[l], lw.out_dim, lw.WT, lw.out_dim, T, lw.in_dim, P, lw.in_dim, lw.out_dim)
             sc = r2 if l in net.skip_in else 1.0
             if l in net.skip_in:
-                _chk(L.mp_tr_copy_cols(_p(T), lw.in_dim, po, _p(self.Gpe), E, 0, P, E, C.c_float(r2), 1, st), "copy_cols")
+                L.mp_tr_copy_cols(T, lw.in_dim, po, self.Gpe, E, 0, P, E, r2, 1, st)
             self.T[l] = T
             self.V[l - 1] = torch.empty(P, po, **f32)
-            _chk(L.mp_tr_sigmul(_p(self.Z[l - 1]), po, P, po, _p(T), lw.in_dim, None, C.c_float(sc), _p(self.V[l - 1]), po, st),
-                 "mp_tr_sigmul")
+            L.mp_tr_sigmul(self.Z[l - 1], po, P, po, T, lw.in_dim, None, sc, self.V[l - 1], po, st)
         lw0 = lins[0]
-        gemm_nt(_p(self.V[0]), lw0.out_dim, _p(lw0.WT), lw0.out_dim, _p(self.Gpe), E, P, E, lw0.out_dim, accumulate=True)
+        gemm_nt(self.V[0], lw0.out_dim, lw0.WT, lw0.out_dim, self.Gpe, E, P, E, lw0.out_dim, accumulate=True)
         self.grad = torch.empty(P, 3, **f32)
-        _chk(L.mp_tr_pe_grad_fwd(_p(x), P, net.multires, _p(self.Gpe), E, _p(self.grad), st), "mp_tr_pe_grad_fwd")
+        L.mp_tr_pe_grad_fwd(x, P, net.multires, self.Gpe, E, self.grad, st)
 
     def backward(self, dfeat, dsdf, dgrad, want_dx=False, tn_groups=None):
         L = hip.lib()
@@ -395,12 +373,11 @@ class ImplicitTrainRev(_LayerwiseImplicit):
         # ---- adjoint of the reverse sweep (ascending l)
         dGpe = torch.empty(P, E, **f32)
         self.dx = torch.zeros(P, 3, **f32) if want_dx else None
-        _chk(L.mp_tr_pe_grad_bwd(_p(self.x), P, net.multires, _p(dgrad), _p(self.Gpe), E, _p(dGpe), E, _p(self.dx), st),
-             "mp_tr_pe_grad_bwd")
+        L.mp_tr_pe_grad_bwd(self.x, P, net.multires, dgrad, self.Gpe, E, dGpe, E, self.dx, st)
         lw0 = lins[0]
         dV = torch.empty(P, lw0.out_dim, **f32)
-        gemm_nt(_p(dGpe), E, _p(lw0.W), lw0.in_dim, _p(dV), lw0.out_dim, P, lw0.out_dim, E)
-        gemm_tn(_p(self.V[0]), lw0.out_dim, _p(dGpe), E, _p(lw0.dW), lw0.in_dim, lw0.out_dim, E, P)
+        gemm_nt(dGpe, E, lw0.W, lw0.in_dim, dV, lw0.out_dim, P, lw0.out_dim, E)
+        gemm_tn(self.V[0], lw0.out_dim, dGpe, E, lw0.dW, lw0.in_dim, lw0.out_dim, E, P)
         dS = [None] * nh
         for l in range(0, nh - 1):
             lw1 = lins[l + 1]
@@ -408,25 +385,24 @@ class ImplicitTrainRev(_LayerwiseImplicit):
             sc = r2 if (l + 1) in net.skip_in else 1.0
             dU = torch.empty(P, out_l, **f32)
             dS[l] = torch.empty(P, out_l, **f32)
-            _chk(L.mp_tr_rev_adj(_p(self.Z[l]), out_l, P, out_l, _p(self.T[l + 1]), lw1.in_dim, None, C.c_float(sc), _p(dV), out_l,
-                                 _p(dU), out_l, _p(dS[l]), out_l, st), "mp_tr_rev_adj")
+            L.mp_tr_rev_adj(self.Z[l], out_l, P, out_l, self.T[l + 1], lw1.in_dim, None, sc, dV, out_l, dU, out_l, dS[l], out_l,
+                            st)
             if (l + 1) in net.skip_in:
                 dT = torch.empty(P, lw1.in_dim, **f32)
-                _chk(L.mp_tr_copy_cols(_p(dU), out_l, 0, _p(dT), lw1.in_dim, 0, P, out_l, C.c_float(r2), 0, st), "copy_cols")
-                _chk(L.mp_tr_copy_cols(_p(dGpe), E, 0, _p(dT), lw1.in_dim, out_l, P, E, C.c_float(r2), 0, st), "copy_cols")
+                L.mp_tr_copy_cols(dU, out_l, 0, dT, lw1.in_dim, 0, P, out_l, r2, 0, st)
+                L.mp_tr_copy_cols(dGpe, E, 0, dT, lw1.in_dim, out_l, P, E, r2, 0, st)
             else:
                 dT = dU
             dV = torch.empty(P, lw1.out_dim, **f32)
-            gemm_nt(_p(dT), lw1.in_dim, _p(lw1.W), lw1.in_dim, _p(dV), lw1.out_dim, P, lw1.out_dim, lw1.in_dim)
-            gemm_tn(_p(self.V[l + 1]), lw1.out_dim, _p(dT), lw1.in_dim, _p(lw1.dW), lw1.in_dim, lw1.out_dim, lw1.in_dim, P)
+            gemm_nt(dT, lw1.in_dim, lw1.W, lw1.in_dim, dV, lw1.out_dim, P, lw1.out_dim, lw1.in_dim)
+            gemm_tn(self.V[l + 1], lw1.out_dim, dT, lw1.in_dim, lw1.dW, lw1.in_dim, lw1.out_dim, lw1.in_dim, P)
         # top of the sweep: V_7 = s_7 (.) W_8[sdf row]
         top = lins[nh - 1].out_dim
         dU = torch.empty(P, top, **f32)
         dS[nh - 1] = torch.empty(P, top, **f32)
-        _chk(L.mp_tr_rev_adj(_p(self.Z[nh - 1]), top, P, top, None, 0, _p(self.w8), C.c_float(1.0), _p(dV), top, _p(dU), top,
-                             _p(dS[nh - 1]), top, st), "mp_tr_rev_adj")
+        L.mp_tr_rev_adj(self.Z[nh - 1], top, P, top, None, 0, self.w8, 1.0, dV, top, dU, top, dS[nh - 1], top, st)
         dw8 = torch.empty(top, **f32)
-        _chk(L.mp_tr_colsum(_p(dU), top, P, top, _p(dw8), st), "mp_tr_colsum")
+        L.mp_tr_colsum(dU, top, P, top, dw8, st)
         lins[nh].dW[0] += dw8
         # ---- adjoint of the value sweep (descending l)
         return self._value_adjoint(dZ, dS, want_dx=want_dx)
@@ -472,8 +448,7 @@ class LinP(LinW):
 
     def refresh(self):
         self.read_params()
-        _chk(hip.lib().mp_tr_wn_fwd(_p(self.v), _p(self.g), self.out_dim, self.in_dim, _p(self.W), _p(self.WT), hip.stream()),
-             "mp_tr_wn_fwd")
+        hip.lib().mp_tr_wn_fwd(self.v, self.g, self.out_dim, self.in_dim, self.W, self.WT, hip.stream())
         self.dW_full.zero_()
         self.db_full.zero_()
 
@@ -565,7 +540,7 @@ class TrainState:
         for k, _ in self.groups:
             if keys is None or k in keys:
                 tab, n, rows, _ = self.tables[k]
-                _chk(L.mp_tr_wn_fwd_multi(_p(tab), n, rows, st), "mp_tr_wn_fwd_multi")
+                L.mp_tr_wn_fwd_multi(tab, n, rows, st)
         self.acc = self.gbuf = None
         return self
 
@@ -587,7 +562,7 @@ class TrainState:
             raise RuntimeError(f"TrainState.finish_group({key!r}) twice in one backward sweep")
         self._finished.add(key)
         tab, n, rows, lps = self.tables[key]
-        _chk(hip.lib().mp_tr_wn_bwd_multi(_p(tab), n, rows, _p(self.acc), _p(self.gbuf), hip.stream()), "mp_tr_wn_bwd_multi")
+        hip.lib().mp_tr_wn_bwd_multi(tab, n, rows, self.acc, self.gbuf, hip.stream())
 
 
 def _implicit_net_type():
@@ -638,7 +613,7 @@ class FusedState:
         self.lins = lins if self.shared else [LinP(l, pad_rows=256 if i == pad else 0) for i, l in enumerate(net.layers())]
         dev = self.lins[0].W.device
         per_point, pack = C.c_longlong(0), C.c_longlong(0)
-        _chk(getattr(hip.lib(), sizes)(1, C.byref(per_point), C.byref(pack)), sizes)
+        getattr(hip.lib(), sizes)(1, C.byref(per_point), C.byref(pack))
         self.arena_per_point = int(per_point.value)
         self.wpack = torch.empty(int(pack.value), dtype=torch.uint8, device=dev)
         self.bias_all = torch.empty(n_layers * 288, dtype=F32, device=dev)
@@ -657,17 +632,17 @@ class FusedState:
         if self.kind == "col":          # the colour net hoists lin_pose(cond) (8), columns 6..13 of its input
             lp = net.lin_pose
             self.lp_w, self.lp_b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
-            _chk(L.mp_tr_hoist_fwd(_p(self.lp_w), 8, 69, _p(self.lp_b), 0, 69, _p(cond_vec), _p(self.pose8), st), "mp_tr_hoist_fwd")
+            L.mp_tr_hoist_fwd(self.lp_w, 8, 69, self.lp_b, 0, 69, cond_vec, self.pose8, st)
             c0, n_h, hvec = 6, 8, self.pose8
         else:
             c0, n_h, hvec = net.embed_dim, net.cond_dim, cond_vec
         lw0 = lins[0]
-        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), 256, lw0.in_dim, _p(lw0.b), c0, n_h, _p(hvec), _p(self.b0), st), "mp_tr_hoist_fwd")
+        L.mp_tr_hoist_fwd(lw0.W, 256, lw0.in_dim, lw0.b, c0, n_h, hvec, self.b0, st)
         bs = [self.b0] + [lw.b for lw in lins[1:]]
         key = tuple(b.data_ptr() for b in bs)
         if key != self._btab_key:
             self._btab_key, self.btab = key, _table(bs, self.b0.device)
-        _chk(getattr(L, self._pack)(_p(self.wtab), _p(self.btab), _p(self.wpack), _p(self.bias_all), st), self._pack)
+        getattr(L, self._pack)(self.wtab, self.btab, self.wpack, self.bias_all, st)
         return self
 
 
@@ -698,11 +673,11 @@ class _FusedImplicit(_SdfEvaluator):
         self.lins = fs.lins
         sizes = getattr(L, _FUSED_KINDS[kind][0])
         arena = C.c_longlong(0)
-        _chk(sizes(P, C.byref(arena), None), "mp_tf_sizes")
+        sizes(P, C.byref(arena), None)
         cap = None
         if p_cap is not None and p_cap >= P:
             capv = C.c_longlong(0)
-            _chk(sizes(int(p_cap), C.byref(capv), None), "mp_tf_sizes")
+            sizes(int(p_cap), C.byref(capv), None)
             cap = int(capv.value)
         self.arena = _big_empty(int(arena.value), x.device, grain=grain, cap=cap, cap_bytes=cap_bytes)
         # the arena's layout (floats): [P+1][256] tensors dZ_l, (V_l,) X_l, (dT_l), then the [P][E] Fourier features (and the
@@ -710,10 +685,10 @@ class _FusedImplicit(_SdfEvaluator):
         self.R1 = R1 = 256 * (P + 1)
         self.t_dZ, self.t_V, self.t_X, self.t_dT, n_t = (0, 8, 15, 23, 46) if kind == "sdf" else (0, None, 7, None, 16)
         self.o_IN, self.o_dG, self.o_G = n_t * R1, n_t * R1 + E * P, n_t * R1 + 2 * E * P
-        _chk(L.mp_tr_pe(_p(x), net.d_in, P, net.multires, 0, C.c_float(1.0), off(self.arena, self.o_IN), E, 0, hip.stream()), "mp_tr_pe")
+        L.mp_tr_pe(x, net.d_in, P, net.multires, 0, 1.0, off(self.arena, self.o_IN), E, 0, hip.stream())
         self.feat = torch.empty(P + 1, 256, dtype=F32, device=x.device)  # columns 1.. of the reference's output (+ the pad row)
         self.sdf = torch.empty(P + 1, dtype=F32, device=x.device)        # column 0
-        self.feat_ptr = _p(self.feat)
+        self.feat_ptr = hip.ptr(self.feat)
 
     def _at(self, t0, l):
         """device pointer to stash tensor l of the family starting at tensor t0 (t_dZ, t_V, t_X, t_dT)"""
@@ -722,8 +697,8 @@ class _FusedImplicit(_SdfEvaluator):
     def _skip_features(self):
         # the skip connection re-injects the Fourier features into layer 4's input (times 1/sqrt 2): the last E columns of X_4
         E = self.E
-        _chk(hip.lib().mp_tr_copy_cols(off(self.arena, self.o_IN), E, 0, self._at(self.t_X, 4), 256, 256 - E, self.P, E,
-                                       C.c_float(1.0 / math.sqrt(2.0)), 0, hip.stream()), "mp_tr_copy_cols")
+        hip.lib().mp_tr_copy_cols(off(self.arena, self.o_IN), E, 0, self._at(self.t_X, 4), 256, 256 - E, self.P, E,
+                                  1.0 / math.sqrt(2.0), 0, hip.stream())
 
     @property
     def out(self):
@@ -742,17 +717,18 @@ class _FusedImplicit(_SdfEvaluator):
         lw0, lw8 = lins[0], lins[8]
         dcond = _layer0_adjoint(lw0, self._at(self.t_dZ, 0), off(self.arena, self.o_IN), E, E, P, P, E, self.net.cond_dim, self.cond)
         if gradient_sweep:
-            gemm_tn(self._at(self.t_V, 0), 256, off(self.arena, self.o_dG), E, _p(lw0.dW), lw0.in_dim, 256, E, P)
+            gemm_tn(self._at(self.t_V, 0), 256, off(self.arena, self.o_dG), E, lw0.dW, lw0.in_dim, 256, E, P)
         groups = tn_groups if tn_groups is not None else []
         for l in range(1, 8):
             lw = lins[l]                                # (layer 3: its 217 / 172 rows contracted as 256, see LinP)
             rows = lw.dW_full.shape[0]
-            groups.append(tn_group(self._at(self.t_dZ, l), 256, self._at(self.t_X, l), 256, _p(lw.dW_full), lw.in_dim, rows, lw.in_dim,
-                                   P, _p(lw.db_full), P))
+            groups.append(tn_group(self._at(self.t_dZ, l), 256, self._at(self.t_X, l), 256, hip.ptr(lw.dW_full), lw.in_dim, rows,
+                                   lw.in_dim, P, hip.ptr(lw.db_full), P))
             if gradient_sweep:
-                groups.append(tn_group(self._at(self.t_V, l), 256, self._at(self.t_dT, l), 256, _p(lw.dW_full), lw.in_dim, rows,
-                                       lw.in_dim, P))
-        groups.append(tn_group(_p(dfeat), 256, self._at(self.t_X, 8), 256, off(lw8.dW, 256), 256, 256, 256, P, off(lw8.db, 1), P))
+                groups.append(tn_group(self._at(self.t_V, l), 256, self._at(self.t_dT, l), 256, hip.ptr(lw.dW_full), lw.in_dim,
+                                       rows, lw.in_dim, P))
+        groups.append(tn_group(hip.ptr(dfeat), 256, self._at(self.t_X, 8), 256, off(lw8.dW, 256), 256, 256, 256, P,
+                               off(lw8.db, 1), P))
         if tn_groups is None:
             launch_tn_groups(groups)
         return dcond
@@ -775,11 +751,10 @@ class ImplicitTrainFused(_FusedImplicit):
         fs, P, E = self.fs, self.P, self.E
         self.nl = len(fs.lins)
         self.w8 = fs.lins[8].W                          # row 0 = the sdf row of the last layer
-        _chk(L.mp_tf_sdf_fwd(_p(fs.wpack), _p(fs.bias_all), _p(self.w8), _p(self.arena), P, _p(self.feat), _p(self.sdf), st),
-             "mp_tf_sdf_fwd")
+        L.mp_tf_sdf_fwd(fs.wpack, fs.bias_all, self.w8, self.arena, P, self.feat, self.sdf, st)
         self._skip_features()
         self.grad = torch.empty(P, 3, dtype=F32, device=x.device)
-        _chk(L.mp_tr_pe_grad_fwd(_p(x), P, net.multires, off(self.arena, self.o_G), E, _p(self.grad), st), "mp_tr_pe_grad_fwd")
+        L.mp_tr_pe_grad_fwd(x, P, net.multires, off(self.arena, self.o_G), E, self.grad, st)
 
     def backward(self, dfeat, dsdf, dgrad, want_dx=False, tn_groups=None):
         assert not want_dx, "the fused SDF kernels do not produce the adjoint of the input points"
@@ -787,11 +762,10 @@ class ImplicitTrainFused(_FusedImplicit):
         L, st = hip.lib(), hip.stream()
         net, P, E, fs, A = self.net, self.P, self.E, self.fs, self.arena
         dG = off(A, self.o_dG)
-        _chk(L.mp_tr_pe_grad_bwd(_p(self.x), P, net.multires, _p(dgrad), off(A, self.o_G), E, dG, E, None, st), "mp_tr_pe_grad_bwd")
+        L.mp_tr_pe_grad_bwd(self.x, P, net.multires, dgrad, off(A, self.o_G), E, dG, E, None, st)
         lw8 = self.lins[8]                              # the sdf row's gradient goes straight into row 0 of dW_8 / db_8
-        _chk(L.mp_tf_sdf_bwd(_p(fs.wpack), _p(self.w8), _p(A), P, _p(dfeat), _p(dsdf), _p(lw8.dW), _p(lw8.db), st), "mp_tf_sdf_bwd")
-        _chk(L.mp_tr_copy_cols(dG, E, 0, self._at(self.t_dT, 4), 256, 256 - E, P, E, C.c_float(1.0 / math.sqrt(2.0)), 0, st),
-             "mp_tr_copy_cols")
+        L.mp_tf_sdf_bwd(fs.wpack, self.w8, A, P, dfeat, dsdf, lw8.dW, lw8.db, st)
+        L.mp_tr_copy_cols(dG, E, 0, self._at(self.t_dT, 4), 256, 256 - E, P, E, 1.0 / math.sqrt(2.0), 0, st)
         self.dx = None
         return self._weight_grads(dfeat, tn_groups, gradient_sweep=True)
 
@@ -806,15 +780,13 @@ class ImplicitTrainFusedBG(_FusedImplicit):
         assert fused_bg_supported(net)
         self._begin("bg", net, x, code, lins, 1 << 22)
         fs = self.fs
-        _chk(hip.lib().mp_tf_bg_fwd(_p(fs.wpack), _p(fs.bias_all), _p(self.arena), self.P, _p(self.feat), _p(self.sdf), hip.stream()),
-             "mp_tf_bg_fwd")
+        hip.lib().mp_tf_bg_fwd(fs.wpack, fs.bias_all, self.arena, self.P, self.feat, self.sdf, hip.stream())
         self._skip_features()
 
     def backward(self, dfeat, dsdf, dgrad=None, want_dx=False, tn_groups=None):
         assert dgrad is None and not want_dx and dfeat.shape[1] == 256
         lw8 = self.lins[8]
-        _chk(hip.lib().mp_tf_bg_bwd(_p(self.fs.wpack), _p(lw8.W), _p(self.arena), self.P, _p(dfeat), _p(dsdf), _p(lw8.dW), _p(lw8.db),
-                                    hip.stream()), "mp_tf_bg_bwd")
+        hip.lib().mp_tf_bg_bwd(self.fs.wpack, lw8.W, self.arena, self.P, dfeat, dsdf, lw8.dW, lw8.db, hip.stream())
         return self._weight_grads(dfeat, tn_groups, gradient_sweep=False)
 
 
@@ -832,7 +804,7 @@ class _ColourNet(_NetParams):
     def _lin_pose_adjoint(self, dh, lp_w):
         """lin_pose's own gradients from d pose8: dW = dh (x) cond, db = dh"""
         dlp_w = _zeros(8, 69, device=dh.device)
-        _chk(hip.lib().mp_tr_hoist_bwd(_p(dh), 8, 69, 0, 69, _p(self.cond), _p(dlp_w), hip.stream()), "mp_tr_hoist_bwd")
+        hip.lib().mp_tr_hoist_bwd(dh, 8, 69, 0, 69, self.cond, dlp_w, hip.stream())
         self.extra_grads = [dlp_w, dh]
         self._dcond = (lp_w, dh)
 
@@ -861,54 +833,52 @@ class RenderTrain(_ColourNet):
             self.extra_params = [lp.weight, lp.bias]
             self.lp_w, self.lp_b = lp.weight.detach().contiguous(), lp.bias.detach().contiguous()
             self.pose8 = torch.empty(8, dtype=F32, device=dev)
-            _chk(L.mp_tr_hoist_fwd(_p(self.lp_w), 8, 69, _p(self.lp_b), 0, 69, _p(cond_vec), _p(self.pose8), hip.stream()),
-                 "mp_tr_hoist_fwd")
+            L.mp_tr_hoist_fwd(self.lp_w, 8, 69, self.lp_b, 0, 69, cond_vec, self.pose8, hip.stream())
             self.hvec = self.pose8
         else:
             self.hvec = cond_vec
         self.b0 = torch.empty(lw0.out_dim, dtype=F32, device=dev)
-        _chk(L.mp_tr_hoist_fwd(_p(lw0.W), lw0.out_dim, lw0.in_dim, _p(lw0.b), self.c_h0, self.n_h, _p(self.hvec),
-                               _p(self.b0), hip.stream()), "mp_tr_hoist_fwd")
+        L.mp_tr_hoist_fwd(lw0.W, lw0.out_dim, lw0.in_dim, lw0.b, self.c_h0, self.n_h, self.hvec, self.b0, hip.stream())
         self.XA, self.feat_ptr, self.feat_ld = XA, feat_ptr, feat_ld
         self.H = []
         nl = len(self.lins)
         H0 = torch.empty(n, lw0.out_dim, dtype=F32, device=dev)
         last0 = nl == 1
-        gemm_nt(_p(XA), self.na, _p(lw0.W), lw0.in_dim, _p(H0), lw0.out_dim, n, lw0.out_dim, self.na, _p(self.b0), n)
-        gemm_nt(feat_ptr, feat_ld, off(lw0.W, self.c_feat), lw0.in_dim, _p(H0), lw0.out_dim, n, lw0.out_dim, 256, None, 0,
+        gemm_nt(XA, self.na, lw0.W, lw0.in_dim, H0, lw0.out_dim, n, lw0.out_dim, self.na, self.b0, n)
+        gemm_nt(feat_ptr, feat_ld, off(lw0.W, self.c_feat), lw0.in_dim, H0, lw0.out_dim, n, lw0.out_dim, 256, None, 0,
                 accumulate=True, relu=not last0)
         self.H.append(H0)
         for l in range(1, nl):
             lw = self.lins[l]
             Hl = torch.empty(n, lw.out_dim, dtype=F32, device=dev)
-            gemm_nt(_p(self.H[l - 1]), self.lins[l - 1].out_dim, _p(lw.W), lw.in_dim, _p(Hl), lw.out_dim, n, lw.out_dim,
-                    lw.in_dim, _p(lw.b), n, relu=l < nl - 1)
+            gemm_nt(self.H[l - 1], self.lins[l - 1].out_dim, lw.W, lw.in_dim, Hl, lw.out_dim, n, lw.out_dim, lw.in_dim, lw.b, n,
+                    relu=l < nl - 1)
             self.H.append(Hl)
         self.rgb = torch.empty(n, 3, dtype=F32, device=dev)
-        _chk(L.mp_tr_sigmoid_fwd(_p(self.H[-1]), n * 3, _p(self.rgb), hip.stream()), "mp_tr_sigmoid_fwd")
+        L.mp_tr_sigmoid_fwd(self.H[-1], n * 3, self.rgb, hip.stream())
 
     def backward(self, drgb, dXA, dfeat_ptr, dfeat_ld, feat_accumulate=True, tn_groups=None):
         L = hip.lib()
         n, dev = self.n, drgb.device
         nl = len(self.lins)
         dZ = torch.empty(n, 3, dtype=F32, device=dev)
-        _chk(L.mp_tr_sigmoid_bwd(_p(self.rgb), _p(drgb), n * 3, _p(dZ), hip.stream()), "mp_tr_sigmoid_bwd")
+        L.mp_tr_sigmoid_bwd(self.rgb, drgb, n * 3, dZ, hip.stream())
         for l in range(nl - 1, 0, -1):
             lw, Hp = self.lins[l], self.H[l - 1]
             pout = self.lins[l - 1].out_dim
-            gemm_tn(_p(dZ), lw.out_dim, _p(Hp), pout, _p(lw.dW), lw.in_dim, lw.out_dim, lw.in_dim, n, _p(lw.db), n)
+            gemm_tn(dZ, lw.out_dim, Hp, pout, lw.dW, lw.in_dim, lw.out_dim, lw.in_dim, n, lw.db, n)
             dH = torch.empty(n, pout, dtype=F32, device=dev)
-            gemm_nt(_p(dZ), lw.out_dim, _p(lw.WT), lw.out_dim, _p(dH), pout, n, pout, lw.out_dim)
+            gemm_nt(dZ, lw.out_dim, lw.WT, lw.out_dim, dH, pout, n, pout, lw.out_dim)
             dZp = torch.empty(n, pout, dtype=F32, device=dev)
-            _chk(L.mp_tr_relu_bwd(_p(Hp), pout, n, pout, _p(dH), pout, _p(dZp), pout, hip.stream()), "mp_tr_relu_bwd")
+            L.mp_tr_relu_bwd(Hp, pout, n, pout, dH, pout, dZp, pout, hip.stream())
             dZ = dZp
         lw0 = self.lins[0]
         o0 = lw0.out_dim
-        dh = _layer0_adjoint(lw0, _p(dZ), _p(self.XA), self.na, self.na, n, n, self.c_h0, self.n_h, self.hvec)
-        gemm_tn(_p(dZ), o0, self.feat_ptr, self.feat_ld, off(lw0.dW, self.c_feat), lw0.in_dim, o0, 256, n)
+        dh = _layer0_adjoint(lw0, dZ, self.XA, self.na, self.na, n, n, self.c_h0, self.n_h, self.hvec)
+        gemm_tn(dZ, o0, self.feat_ptr, self.feat_ld, off(lw0.dW, self.c_feat), lw0.in_dim, o0, 256, n)
         # data gradients
-        gemm_nt(_p(dZ), o0, _p(lw0.WT), o0, _p(dXA), self.na, n, self.na, o0)
-        gemm_nt(_p(dZ), o0, off(lw0.WT, self.c_feat * o0), o0, dfeat_ptr, dfeat_ld, n, 256, o0, None, 0, accumulate=feat_accumulate)
+        gemm_nt(dZ, o0, lw0.WT, o0, dXA, self.na, n, self.na, o0)
+        gemm_nt(dZ, o0, off(lw0.WT, self.c_feat * o0), o0, dfeat_ptr, dfeat_ld, n, 256, o0, None, 0, accumulate=feat_accumulate)
         if self.pose_mode:
             self._lin_pose_adjoint(dh, self.lp_w)
         return dh
@@ -927,10 +897,10 @@ class RenderTrainFused(_ColourNet):
         self.lins = cs.lins
         self.extra_params = [net.lin_pose.weight, net.lin_pose.bias]
         stash = C.c_longlong(0)
-        _chk(L.mp_tf_col_sizes(n, C.byref(stash), None), "mp_tf_col_sizes")
+        L.mp_tf_col_sizes(n, C.byref(stash), None)
         self.stash = _big_empty(int(stash.value), XA.device)
         self.rgb = torch.empty(n, 3, dtype=F32, device=XA.device)
-        _chk(L.mp_tf_col_fwd(_p(cs.wpack), _p(cs.bias_all), _p(self.stash), feat_ptr, _p(XA), n, _p(self.rgb), st), "mp_tf_col_fwd")
+        L.mp_tf_col_fwd(cs.wpack, cs.bias_all, self.stash, feat_ptr, XA, n, self.rgb, st)
 
     def backward(self, drgb, dXA, dfeat_ptr, dfeat_ld, feat_accumulate=False, tn_groups=None):
         assert not feat_accumulate and dfeat_ld == 256       # rows [0, n) of dfeat are written; see ImplicitTrainFused for tn_groups
@@ -938,22 +908,21 @@ class RenderTrainFused(_ColourNet):
         n, lins, cs, S = self.n, self.lins, self.cs, self.stash
         NL = 256 * (n + 1)                               # one pad row per stash tensor
         dz4 = torch.empty(n, 3, dtype=F32, device=drgb.device)
-        _chk(L.mp_tf_col_bwd(_p(cs.wpack), _p(S), _p(lins[4].W), _p(self.rgb), _p(drgb), n, dfeat_ptr, _p(dXA), _p(dz4), st),
-             "mp_tf_col_bwd")
+        L.mp_tf_col_bwd(cs.wpack, S, lins[4].W, self.rgb, drgb, n, dfeat_ptr, dXA, dz4, st)
         H = lambda l: off(S, l * NL)
         dZ = lambda l: off(S, (4 + l) * NL)
         lw0 = lins[0]
         # the hoisted pose embedding: dW_0[:, 6:14] += db_0 (x) pose8 ; d pose8 = W_0[:, 6:14]^T db_0
-        dh = _layer0_adjoint(lw0, dZ(0), _p(self.XA), 6, 6, n, n, 6, 8, cs.pose8)
+        dh = _layer0_adjoint(lw0, dZ(0), self.XA, 6, 6, n, n, 6, 8, cs.pose8)
         groups = tn_groups if tn_groups is not None else []
         groups.append(tn_group(dZ(0), 256, self.feat_ptr, 256, off(lw0.dW, 14), lw0.in_dim, 256, 256, n))
         for l in range(1, 4):
             lw = lins[l]
-            groups.append(tn_group(dZ(l), 256, H(l - 1), 256, _p(lw.dW), 256, 256, 256, n, _p(lw.db), n))
+            groups.append(tn_group(dZ(l), 256, H(l - 1), 256, hip.ptr(lw.dW), 256, 256, 256, n, hip.ptr(lw.db), n))
         if tn_groups is None:
             launch_tn_groups(groups)
         lw4 = lins[4]
-        gemm_tn(_p(dz4), 3, H(3), 256, _p(lw4.dW), 256, 3, 256, n, _p(lw4.db), n)
+        gemm_tn(dz4, 3, H(3), 256, lw4.dW, 256, 3, 256, n, lw4.db, n)
         self._lin_pose_adjoint(dh, cs.lp_w)
         return dh
 
@@ -1135,19 +1104,18 @@ class TrainGraph:
         nn_cano = torch.empty(npts, dtype=torch.int32, device=dev) if self.pose_grad else None
         # (a training batch's rays are random pixels: the warp first groups the samples by their nearest vertex cluster)
         bin_work = torch.empty(int(L.mp_warp_bin_work_bytes(npts)), dtype=torch.uint8, device=dev)
-        _chk(L.mp_warp_inverse_shade(_p(cx["dirs"]), _p(cx["pose"]), _p(pp["hit_index"]), _p(pp["count"]), _p(zfinal), NZ, S, Rp,
-                                     _p(pp["vsorted"]), _p(pp["cbound"]), _p(pp["btab"]), 0, _p(cx["beta"]),
-                                     _p(X), None, None, None, None, None, _p(nn_posed), _p(bin_work), st), "mp_warp_inverse_shade")
+        L.mp_warp_inverse_shade(cx["dirs"], cx["pose"], pp["hit_index"], pp["count"], zfinal, NZ, S, Rp, pp["vsorted"],
+                                pp["cbound"], pp["btab"], 0, cx["beta"], X, None, None, None, None, None, nn_posed, bin_work, st)
         jinv = torch.empty(npts, 9, **f32)
-        _chk(L.mp_warp_jacobian(_p(X), None, None, 0, 0, npts, _p(dfm.vsorted_c), _p(dfm.cbound_c), _p(pp["btab"]),
-                                _p(jinv), _p(nn_cano), _p(nn_posed), _p(dfm.verts_c_flat), st), "mp_warp_jacobian")
+        L.mp_warp_jacobian(X, None, None, 0, 0, npts, dfm.vsorted_c, dfm.cbound_c, pp["btab"], jinv, nn_cano, nn_posed,
+                           dfm.verts_c_flat, st)
         flags = None
         if self.surface_flags:        # multiply.py:311-315: in / off-surface rays w.r.t. the current canonical mesh
             fv = m.mesh_face_vertices_list[p].detach().reshape(-1, 9).to(dev).float().contiguous()
             sd = torch.empty(npts, **f32)
-            _chk(L.mp_mesh_signed_distance(_p(X), npts, _p(fv), fv.shape[0], _p(sd), st), "mp_mesh_signed_distance")
+            L.mp_mesh_signed_distance(X, npts, fv, fv.shape[0], sd, st)
             off_p = torch.empty(Rp, dtype=torch.uint8, device=dev); in_p = torch.empty(Rp, dtype=torch.uint8, device=dev)
-            _chk(L.mp_mesh_ray_flags(_p(sd), Rp, S, C.c_float(m.threshold), _p(off_p), _p(in_p), st), "mp_mesh_ray_flags")
+            L.mp_mesh_ray_flags(sd, Rp, S, m.threshold, off_p, in_p, st)
             flags = (off_p.bool(), in_p.bool(), sd)
         # eikonal points near the canonical surface (multiply.py:322-327, sampler.py:84-108 with global_ratio 0)
         vc = server.verts_c.reshape(-1, 3)
@@ -1158,9 +1126,9 @@ class TrainGraph:
         XA = torch.empty(npts, 6, **f32); nrm = torch.empty(npts, 3, **f32)
         sdf = it.sdf[:npts]
         # (sdf and d sdf / d x come from the evaluator as arrays of their own: the kernels' "no Z8" form)
-        _chk(L.mp_tr_shade_in_fwd(None, Pt, npts, _p(X), _p(jinv), _p(XA), _p(nrm), None, _p(it.grad), st), "mp_tr_shade_in_fwd")
+        L.mp_tr_shade_in_fwd(None, Pt, npts, X, jinv, XA, nrm, None, it.grad, st)
         gth = torch.empty(E, 3, **f32)
-        _chk(L.mp_tr_eik_fwd(None, Pt, npts, E, _p(gth), _p(it.grad), st), "mp_tr_eik_fwd")
+        L.mp_tr_eik_fwd(None, Pt, npts, E, gth, it.grad, st)
         rt = colour_evaluator(ren, XA, it, npts, pp["cond"], self.ts.lins[id(ren)])
         self.fg[p] = dict(it=it, rt=rt, X=X, jinv=jinv, XA=XA, sdf=sdf, nrm=nrm, gth=gth, zfinal=zfinal, iters=iters,
                           wcount=wcount, npts=npts, Pt=Pt, Rp=Rp, flags=flags, nn_posed=nn_posed, nn_cano=nn_cano)
@@ -1254,16 +1222,15 @@ class TrainGraph:
             rows = Rb * NB
             pts = torch.empty(rows, 4, **f32)
             cam = cx["pose"].reshape(4, 4)[:3, 3].contiguous()
-            _chk(L.mp_tr_bg_points(_p(bdirs), _p(cam), _p(zbg), Rb, NB, C.c_float(m.sdf_bounding_sphere), _p(pts), st),
-                 "mp_tr_bg_points")
+            L.mp_tr_bg_points(bdirs, cam, zbg, Rb, NB, m.sdf_bounding_sphere, pts, st)
             bit = bg_evaluator(m.bg_implicit_network, pts, code, self.ts.lins[id(m.bg_implicit_network)])
             drep = bdirs[:, None, :].expand(Rb, NB, 3).reshape(-1, 3).contiguous()
             XAb = torch.empty(rows, 27, **f32)
-            _chk(L.mp_tr_pe(_p(drep), 3, rows, 4, 0, C.c_float(1.0), _p(XAb), 27, 0, st), "mp_tr_pe")
+            L.mp_tr_pe(drep, 3, rows, 4, 0, 1.0, XAb, 27, 0, st)
             brt = colour_evaluator(m.bg_rendering_network, XAb, bit, rows, code, self.ts.lins[id(m.bg_rendering_network)])
             sdfb = bit.sdf[:rows]
             bg_slice = torch.empty(Rb, 3, **f32)
-            _chk(L.mp_tr_bg_comp_fwd(_p(sdfb), _p(brt.rgb), _p(zbg), Rb, NB, _p(bg_slice), st), "mp_tr_bg_comp_fwd")
+            L.mp_tr_bg_comp_fwd(sdfb, brt.rgb, zbg, Rb, NB, bg_slice, st)
             if bg_rgb is None:
                 bg_rgb = bg_slice                                 # the whole call's rays: no scatter into a zero image
             else:
@@ -1288,9 +1255,8 @@ class TrainGraph:
         rgb_values = torch.empty(R, 3, **f32); fg_rgb_values = torch.empty(R, 3, **f32)
         normal_values = torch.empty(R, 3, **f32); acc_map = torch.empty(R, **f32)
         acc_person = torch.empty(R, P, **f32); bg_T = torch.empty(R, **f32)
-        _chk(L.mp_composite(R, P, self.NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(t_nrm), _p(cx["beta"]),
-                            _p(bg_rgb) if bg_rgb is not None else None, _p(rgb_values), _p(fg_rgb_values),
-                            _p(normal_values), _p(acc_map), _p(acc_person), _p(bg_T), hip.stream()), "mp_composite")
+        L.mp_composite(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, t_nrm, cx["beta"], bg_rgb, rgb_values, fg_rgb_values,
+                       normal_values, acc_map, acc_person, bg_T, hip.stream())
         grad_theta = torch.cat([rec["gth"] for rec in self.composited], 0)[None]               # multiply.py:565
         self.bg_T = bg_T
         if self.reg_items:
@@ -1323,16 +1289,15 @@ class TrainGraph:
                 pts = pp["verts"].index_select(0, idx).contiguous()
                 n = pts.shape[0]
                 xc = torch.empty(n, 3, dtype=F32, device=dev)
-                _chk(L.mp_warp_inverse(_p(pts), None, None, None, None, None, 0, 1, n, _p(pp["vsorted"]), _p(pp["cbound"]),
-                                       _p(pp["btab"]), 0, None, None, _p(xc), None, None, None, None, None, st), "mp_warp_inverse")
+                L.mp_warp_inverse(pts, None, None, None, None, None, 0, 1, n, pp["vsorted"], pp["cbound"], pp["btab"], 0, None,
+                                  None, xc, None, None, None, None, None, st)
                 warp = None
                 if self.pose_grad:
                     # the backward needs the nearest posed vertex of every sample (ties: lowest id) and its inverse blended
                     # transform I_nn: the same exact search over the posed vertex structure (the weights are constants, deformer.py:47)
                     jv = torch.empty(n, 9, dtype=F32, device=dev)
                     nn = torch.empty(n, dtype=torch.int32, device=dev)
-                    _chk(L.mp_warp_jacobian(_p(pts), None, None, 0, 0, n, _p(pp["vsorted"]), _p(pp["cbound"]), _p(pp["btab"]),
-                                            _p(jv), _p(nn), None, None, st), "mp_warp_jacobian")
+                    L.mp_warp_jacobian(pts, None, None, 0, 0, n, pp["vsorted"], pp["cbound"], pp["btab"], jv, nn, None, None, st)
                     warp = (xc, jv, nn, idx.to(torch.int32).contiguous())
                 it = ImplicitTrain(imp, xc, cond, fwd=False, lins=self.ts.lins[id(imp)])
                 sdf = it.out[:, 0]
@@ -1372,10 +1337,9 @@ class TrainGraph:
                     pp, server = self.cx["per"][q], self.model.smpl_server_list[q]
                     dxc = it.dx.contiguous()
                     dtfs = torch.zeros(24, 16, dtype=F32, device=dev)
-                    _chk(L.mp_tr_warp_bwd(_p(xc), _p(dxc), None, None, _p(nn), None, n, _p(server.tables.lbs_weights), _p(pp["tfs"]),
-                                          _p(dtfs), st), "mp_tr_warp_bwd")
+                    L.mp_tr_warp_bwd(xc, dxc, None, None, nn, None, n, server.tables.lbs_weights, pp["tfs"], dtfs, st)
                     dverts = torch.zeros(server.verts_c.reshape(-1, 3).shape[0], 3, dtype=F32, device=dev)
-                    _chk(L.mp_tr_gather_bwd(_p(idx), n, _p(jv), _p(dxc), dverts.shape[0], _p(dverts), st), "mp_tr_gather_bwd")
+                    L.mp_tr_gather_bwd(idx, n, jv, dxc, dverts.shape[0], dverts, st)
                     prev = self.reg_surf.get(q)
                     self.reg_surf[q] = (dtfs, dverts) if prev is None else (prev[0] + dtfs, prev[1] + dverts)
                     if not self.cond_zero:
@@ -1456,10 +1420,8 @@ class TrainGraph:
         d_bg_rgb = zp.take(R, 3)
         d_beta = zp.take(1)
         t_dsdf, t_drgb = _table(dsdf_l, dev), _table(drgb_l, dev)
-        _chk(hip.lib().mp_tr_composite_bwd(R, P, self.NZ, _p(t_inv), _p(t_z), _p(t_sdf), _p(t_rgb), _p(cx["beta"]),
-                                           _p(self.bg_rgb) if self.bg_rgb is not None else None, _p(d_rgb_values), _p(d_acc_map),
-                                           _p(d_acc_person), _p(t_dsdf), _p(t_drgb), _p(d_bg_rgb), _p(d_beta), hip.stream()),
-             "mp_tr_composite_bwd")
+        hip.lib().mp_tr_composite_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, cx["beta"], self.bg_rgb, d_rgb_values, d_acc_map,
+                                      d_acc_person, t_dsdf, t_drgb, d_bg_rgb, d_beta, hip.stream())
         return dsdf_l, drgb_l, d_bg_rgb, d_beta
 
     def _person_backward(self, p, dsdf, drgb, dgth):
@@ -1475,10 +1437,9 @@ class TrainGraph:
         tn_groups = []                 # the person's aligned weight-gradient contractions: ONE grouped launch below
         rt.backward(drgb, dXA, *it.dfeat_target(dfeat), tn_groups=tn_groups)
         djinv = torch.empty(npts, 9, **f32) if self.pose_grad else None
-        _chk(L.mp_tr_shade_in_bwd(None, Pt, npts, _p(f["jinv"]), _p(dXA), _p(dsdf), None, None, _p(djinv), _p(it.grad), _p(dgrad), st),
-             "mp_tr_shade_in_bwd")
+        L.mp_tr_shade_in_bwd(None, Pt, npts, f["jinv"], dXA, dsdf, None, None, djinv, it.grad, dgrad, st)
         if dgth is not None:
-            _chk(L.mp_tr_eik_bwd(Pt, npts, N_EIKONAL, _p(dgth), None, _p(dgrad), st), "mp_tr_eik_bwd")
+            L.mp_tr_eik_bwd(Pt, npts, N_EIKONAL, dgth, None, dgrad, st)
         dcond = it.backward(dfeat, dsdf, dgrad, want_dx=self.pose_grad, tn_groups=tn_groups)
         launch_tn_groups(tn_groups)
         self.ts.finish_group(p)                                   # one batched weight-norm adjoint for the person's two nets
@@ -1494,14 +1455,13 @@ class TrainGraph:
         npts = f["npts"]
         dxc = (f["it"].dx[:npts] + dXA[:, :3]).contiguous()
         dtfs = torch.zeros(24, 16, **f32)
-        _chk(L.mp_tr_warp_bwd(_p(f["X"]), _p(dxc), _p(f["jinv"]), _p(djinv), _p(f["nn_posed"]), _p(f["nn_cano"]),
-                              npts, _p(server.tables.lbs_weights), _p(pp["tfs"]), _p(dtfs), st), "mp_tr_warp_bwd")
+        L.mp_tr_warp_bwd(f["X"], dxc, f["jinv"], djinv, f["nn_posed"], f["nn_cano"], npts, server.tables.lbs_weights, pp["tfs"],
+                         dtfs, st)
         surf = self.reg_surf.get(p)
         if surf is None:
             dprm = torch.empty(86, **f32)
-            _chk(L.mp_smpl_pose_bwd(_p(server.tables.parents), _p(pp["prm"]), _p(server.tfs_c_inv),
-                                    _p(pp["rest_joints"]), _p(server.tables.j_shapedirs), _p(dtfs), _p(dprm), st),
-                 "mp_smpl_pose_bwd")
+            L.mp_smpl_pose_bwd(server.tables.parents, pp["prm"], server.tfs_c_inv, pp["rest_joints"], server.tables.j_shapedirs,
+                               dtfs, dprm, st)
         else:                                                    # + the surface term's posed vertices and transforms
             dprm = server.pose_backward(pp["prm"], dverts=surf[1], dtfs=dtfs + surf[0])
         if not self.cond_zero:                                   # cond = smpl_pose[3:] / pi  (multiply.py:270)
@@ -1521,8 +1481,7 @@ class TrainGraph:
         s0, s1 = self.ray_slice
         d_bg_slice = d_bg_rgb[s0:s1].contiguous()
         dsdfb = torch.empty(rows, **f32); drgbb = torch.empty(rows, 3, **f32)
-        _chk(L.mp_tr_bg_comp_bwd(_p(b["sdfb"]), _p(brt.rgb), _p(b["zbg"]), Rb, NB, _p(d_bg_slice), _p(dsdfb), _p(drgbb),
-                                 st), "mp_tr_bg_comp_bwd")
+        L.mp_tr_bg_comp_bwd(b["sdfb"], brt.rgb, b["zbg"], Rb, NB, d_bg_slice, dsdfb, drgbb, st)
         dXAb = torch.empty(rows, 27, **f32)
         dfeatb = bit.new_dfeat(rows)
         dcode = brt.backward(drgbb, dXAb, *bit.dfeat_target(dfeatb))
