@@ -638,6 +638,12 @@ def shade_rev_launch(pki, gn, x_c, jinv, worklist, count, n, sdf, nrm, feat):
                            count, n, sdf, nrm, feat, buf, seg, stream())
 
 
+def feat_frag_bytes(n):
+    """size of the shade -> colour feature hand-off for n work items: f16 B-fragments, 8 K steps x 4 blocks x 1 KiB per tile of
+    64 items, in whole launches of 4 tiles (csrc/mlp.hip feat_frag)"""
+    return (int(n) + 255) // 256 * 4 * 8 * 4 * 1024
+
+
 def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
     """sdf, normals, rgb at canonical points (ImplicitNet value + input gradient, RenderingNet 'pose_no_view').
     mode 'reverse': mp_mlp_shade_rev (two sweeps); 'forward': the forward-mode kernel mp_mlp_shade."""
@@ -654,8 +660,7 @@ def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
     nrm = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    tiles = (n + 255) // 256 * 4
-    feat = torch.empty(tiles * 8 * 4 * 1024, dtype=torch.uint8, device=dev)
+    feat = torch.empty(feat_frag_bytes(n), dtype=torch.uint8, device=dev)
     if (mode or SHADE_MODE) == "reverse":
         shade_rev_launch(pki, grad_net(imp), x_c, jinv, None, None, n, sdf, nrm, feat)
     else:

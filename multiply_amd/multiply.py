@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import hip
 from .density import AbsDensity, LaplaceDensity
 from .networks import ImplicitNet, RenderingNet
-from .ray_sampler import ErrorBoundSampler
+from .ray_sampler import ErrorBoundSampler, sample_persons
 from .smpl import NUM_JOINTS, NUM_VERTS, SMPLDeviceTables, SMPLServer, knn_cluster_perm, load_smpl_tables
 from .deformer import SMPLDeformer
 from .sampler import PointInSpace
@@ -132,9 +132,9 @@ class Multiply(nn.Module):
         # eval-mode refinement of the box cull that provably leaves every pixel unchanged (mp_ray_cull_near); 0 = box only
         self.near_cull = os.environ.get("MP_NEAR_CULL", "1") != "0"
         # ray-sharded data-parallel training: a torch.distributed process group (or True = the default group) over which the
-        # sampler's per-iteration convergence vote is all-reduced (MAX) -- see _sample_person; None: the vote is per process
+        # sampler's per-iteration convergence vote is all-reduced (MAX) -- see ray_sampler.sample_persons; None: the vote is per process
         self.sampler_vote_group = None
-        # arithmetic of the sampler's network queries (_sampler_sdf): 'auto' (default, round 6) = 'bf16x3' -- near-fp32: the depths
+        # arithmetic of the sampler's network queries (ray_sampler.SamplerRun.sdf): 'auto' (default, round 6) = 'bf16x3' -- near-fp32: the depths
         # then agree with the fp32 reference to 1e-3 instead of 2e-2 and the grazing-ray tail of the render disappears -- for the
         # network shape csrc/tfuse.hip is specialised for (the shipped configs), 'f16x2' (split activations, any shape) otherwise;
         # 'f16': the fused half-precision kernel (the round 1-5 default), a third of the query time
@@ -182,11 +182,6 @@ class Multiply(nn.Module):
             raise ValueError(f"obb_mode {self.obb_mode!r}: expected 'auto', 'hull' or 'pca'")
         return ("hull" if self.training else "pca") if self.obb_mode == "auto" else self.obb_mode
 
-    def _sampler_cfg(self):
-        rs = self.ray_sampler
-        return hip.MpSamplerCfg(rs.N_samples, rs.N_samples_eval, rs.N_samples_extra, rs.beta_iters, rs.max_total_iters,
-                                rs.eps, rs.add_tiny, rs.near)
-
     def forward(self, input, id=-1, cond_zero_shit=False, canonical_pose=False):
         if self.training:
             from . import train
@@ -194,11 +189,20 @@ class Multiply(nn.Module):
         with torch.no_grad():
             return self._forward_eval(input, id, canonical_pose)
 
-    def _setup(self, input, id, canonical_pose, side_stream=False, _beta=None, host_hull=False):
+    def _beta_value(self):
+        """the density's beta as the kernels read it (abs + beta_min, multiply.py's density call), on the current stream"""
+        return (self.density.beta.detach().abs() + self.density.beta_min).reshape(1).float().contiguous()
+
+    def _setup(self, input, id, canonical_pose, side_stream=False, host_hull=False):
         """Rays, SMPL posing, nearest-vertex structures and the box cull for every person of the call
         (multiply.py:177-266).  Ends with the one host sync of the call (hit counts size the workspaces).
+        side_stream: run it on a stream of its own (_setup_side_stream); host_hull: the convex hulls on the host."""
+        if side_stream:
+            return self._setup_side_stream(input, id, canonical_pose, host_hull)
+        return self._setup_body(input, id, canonical_pose, self._beta_value(), host_hull)
 
-        side_stream: the setup kernels read only the call's inputs, so they run on a stream of their own and the host waits
+    def _setup_side_stream(self, input, id, canonical_pose, host_hull):
+        """The setup kernels read only the call's inputs, so they run on a stream of their own and the host waits
         for THAT stream only: it does not wait for the previous iteration's backward pass (or the previous frame) still
         running on the caller's stream, and keeps enqueueing.  The inputs must be resident and complete (produced by work
         the host has already waited for, e.g. a data loader's copies); everything allocated here is handed to the caller's
@@ -209,72 +213,62 @@ class Multiply(nn.Module):
             computed on the caller's stream once per parameter version and the side stream waits for that event;
           * body-model inputs that are being optimised (requires_grad / produced by BodyModelParams in this iteration on
             the caller's stream): the side stream is refused, the setup runs in order."""
-        if side_stream and any(torch.is_tensor(input.get(k)) and (input[k].requires_grad or input[k].grad_fn is not None)
-                               for k in ("smpl_params", "smpl_pose", "smpl_shape", "smpl_trans")):
-            side_stream = False
-        if side_stream:
-            main = torch.cuda.current_stream()
-            side = self.__dict__.get("_setup_stream")
-            if side is None:
-                side = self.__dict__["_setup_stream"] = torch.cuda.Stream()
-            beta_in = None
-            if not self.training:
-                b = self.density.beta
-                cache = self.__dict__.get("_eval_beta")
-                # keyed on the parameter OBJECT, its storage and its version: writes through .data and a replaced Parameter with the
-                # same version number must not leave a stale value behind (a load_state_dict bumps the version: copy_ in place)
-                # (`id` is this method's person-id argument: the parameter is identified by its storage)
-                key = (b.data_ptr(), b._version, str(b.device), hip._GENERATION[0])
-                if cache is None or cache[0] != key:
-                    val = (b.detach().abs() + self.density.beta_min).reshape(1).float().contiguous()   # caller's stream
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    side.wait_event(ev)          # once per parameter version: later side-stream work is ordered behind it
-                    val.record_stream(side)
-                    cache = self.__dict__["_eval_beta"] = (key, val)
-                beta_in = cache[1]
-            with torch.cuda.stream(side):
-                cx = self._setup(input, id, canonical_pose, _beta=beta_in if beta_in is not None else "defer", host_hull=host_hull)
+        if any(torch.is_tensor(input.get(k)) and (input[k].requires_grad or input[k].grad_fn is not None)
+               for k in ("smpl_params", "smpl_pose", "smpl_shape", "smpl_trans")):
+            return self._setup_body(input, id, canonical_pose, self._beta_value(), host_hull)
+        main = torch.cuda.current_stream()
+        side = self.__dict__.get("_setup_stream")
+        if side is None:
+            side = self.__dict__["_setup_stream"] = torch.cuda.Stream()
+        beta = None               # training: no setup kernel reads it
+        if not self.training:
+            b = self.density.beta
+            cache = self.__dict__.get("_eval_beta")
+            # keyed on the parameter's storage and its version: writes through .data and a replaced Parameter with the
+            # same version number must not leave a stale value behind (a load_state_dict bumps the version: copy_ in place)
+            key = (b.data_ptr(), b._version, str(b.device), hip._GENERATION[0])
+            if cache is None or cache[0] != key:
+                val = self._beta_value()                                                                 # caller's stream
+                ev = torch.cuda.Event()
+                ev.record(main)
+                side.wait_event(ev)          # once per parameter version: later side-stream work is ordered behind it
+                val.record_stream(side)
+                cache = self.__dict__["_eval_beta"] = (key, val)
+            beta = cache[1]
+        with torch.cuda.stream(side):
+            cx = self._setup_body(input, id, canonical_pose, beta, host_hull)
 
-            def hand_over(o):
-                if torch.is_tensor(o):
-                    if o.is_cuda:
-                        o.record_stream(main)
-                elif isinstance(o, dict):
-                    for v in o.values():
-                        hand_over(v)
-                elif isinstance(o, (list, tuple)):
-                    for v in o:
-                        hand_over(v)
-            hand_over(cx)
-            main.wait_stream(side)
-            if beta_in is None:       # training: the parameter as the caller's stream sees it (behind the last optimizer step)
-                cx["beta"] = (self.density.beta.detach().abs() + self.density.beta_min).reshape(1).float().contiguous()
-            return cx
-        L = hip.lib()
+        def hand_over(o):
+            if torch.is_tensor(o):
+                if o.is_cuda:
+                    o.record_stream(main)
+            elif isinstance(o, dict):
+                for v in o.values():
+                    hand_over(v)
+            elif isinstance(o, (list, tuple)):
+                for v in o:
+                    hand_over(v)
+        hand_over(cx)
+        main.wait_stream(side)
+        if beta is None:          # training: the parameter as the caller's stream sees it (behind the last optimizer step)
+            cx["beta"] = self._beta_value()
+        return cx
+
+    def _setup_body(self, input, id, canonical_pose, beta, host_hull=False):
+        """One run of the setup on the current stream -> cx.  beta: the density's beta [1], or None where the caller fills
+        cx['beta'] in afterwards (side-stream training setup: no setup kernel reads it)."""
+        assert beta is not None or self.training, "a deferred beta is only valid where the near cull (eval) does not run"
+        L, st = hip.lib(), hip.stream()
         dev = self.density.beta.device
         f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        st = hip.stream()
         uv = input["uv"].to(dev).float().reshape(-1, 2).contiguous()
         R = uv.shape[0]
         K = input["intrinsics"].to(dev).float().reshape(16).contiguous()
         pose = input["pose"].to(dev).float().reshape(16).contiguous()
-        smpl_params = input["smpl_params"].detach().to(dev).float()
-        smpl_pose = input["smpl_pose"].detach().to(dev).float()
-        smpl_shape = input["smpl_shape"].detach().to(dev).float()
-        smpl_trans = input["smpl_trans"].detach().to(dev).float()
-        P = smpl_trans.shape[1]
+        smpl = {k: input["smpl_" + k].detach().to(dev).float() for k in ("params", "pose", "shape", "trans")}
+        P = smpl["trans"].shape[1]
         persons = list(id) if isinstance(id, (list, tuple)) else (list(range(P)) if id == -1 else [id])
-        rs = self.ray_sampler
         group = int(self.convergence_group or R)
-        if torch.is_tensor(_beta):
-            beta = _beta
-        elif _beta == "defer":     # side-stream training setup: filled in on the caller's stream; no setup kernel reads it
-            assert self.training, "a deferred beta is only valid where the near cull (eval) does not run"
-            beta = None
-        else:
-            beta = (self.density.beta.detach().abs() + self.density.beta_min).reshape(1).float().contiguous()
 
         # rays (rend_util.get_camera_params)
         dirs = torch.empty(R, 3, **f32)
@@ -282,84 +276,36 @@ class Multiply(nn.Module):
         L.mp_ray_setup(uv, K, pose, R, self.sdf_bounding_sphere, dirs, far, st)
 
         # SMPL posing, nearest-vertex structures, box cull  (multiply.py:196-214, 256-266)
-        per = {}
         zp = hip.ZeroPool(dev, 1 << 16)             # the setup's device counters: one fill (on the setup's stream)
         counts = zp.take(len(persons), dtype=torch.int32)
-        hull_status = None
-        scan_tmp = torch.empty(R + (R + 1023) // 1024 + 8, **i32)
+        scan_tmp = torch.empty(R + (R + 1023) // 1024 + 8, dtype=torch.int32, device=dev)
         verts_all = torch.empty(len(persons), NUM_VERTS, 3, **f32)
-        given_hits = "hit_index" in input and input["hit_index"] is not None
+        per = {p: self._setup_pose(p, smpl, canonical_pose, verts_all[n], counts[n:n + 1], R) for n, p in enumerate(persons)}
+        given_hits = input.get("hit_index") is not None
         device_hull = not given_hits and self._obb_mode_now() == "hull" and not host_hull
-        for n, p in enumerate(persons):
-            server = self.smpl_server_list[p]
-            prm = torch.cat([smpl_params[0, p, 0:1], smpl_trans[0, p], smpl_pose[0, p], smpl_shape[0, p]]).contiguous()
-            if canonical_pose:   # multiply.py:197-202
-                prm = prm.clone()
-                prm[1:4] = 0
-                prm[4:76] = 0
-                prm[4 + 5] = np.pi / 6
-                prm[4 + 8] = -np.pi / 6
-            verts = verts_all[n]
-            tfs = torch.empty(NUM_JOINTS, 4, 4, **f32)
-            jnts = torch.empty(NUM_JOINTS, 3, **f32)
-            server.pose_into(prm, verts, tfs, jnts)
-            vsorted, cbound = hip.knn_tables(verts, self.deformer_list[p].knn_perm)
-            btab = hip.blend_table(server.tables.lbs_weights, tfs)        # per-vertex inverse blended transform of this pose
-            hit_index = torch.empty(R, **i32)
-            inv_index = torch.empty(R, **i32)
-            cond = (smpl_pose[0, p, 3:] / np.pi).contiguous()          # multiply.py:270
-            per[p] = dict(verts=verts, tfs=tfs, btab=btab, vsorted=vsorted, cbound=cbound, hit_index=hit_index, obb=None,
-                          inv_index=inv_index, count=counts[n:n + 1], cond=cond, prm=prm,
-                          rest_joints=server.rest_joints() if self.training else None)
-        obb_all = None
-        if device_hull:
-            # the convex hulls (gift wrapping), the candidate searches and the boxes of ALL bodies in one batch on the device: no
-            # host round trip; the status words are read with the hit counts below (a failure -- exactly coplanar vertices
-            # tying into a non-manifold patch -- repeats the setup with the host-side hull)
-            hull_status = zp.take(len(persons), 8, dtype=torch.int32)
-            work = torch.empty(len(persons), int(L.mp_obb_hull_device_work_bytes()), dtype=torch.uint8, device=dev)
-            obb_all = torch.empty(len(persons), 16, **f32)
-            L.mp_obb_hull_device(verts_all, NUM_VERTS, len(persons), self.obb_inflate, work, obb_all, hull_status, st)
+        obb_all, hull_status = self._setup_device_hull(verts_all, zp) if device_hull else (None, None)
         for n, p in enumerate(persons):
             q = per[p]
-            verts, hit_index, inv_index, cbound = q["verts"], q["hit_index"], q["inv_index"], q["cbound"]
-            obb = None
             if given_hits:
                 hi = input["hit_index"][p].to(dev).to(torch.int32).contiguous()
                 if hi.numel() == 0:      # multiply.py:262-263: no ray meets the box -> ray 0
                     hi = torch.zeros(1, dtype=torch.int32, device=dev)
-                hit_index[:hi.numel()] = hi
-                L.mp_ray_hits_from_index(hit_index, hi.numel(), R, counts[n:n + 1], inv_index, st)
+                q["hit_index"][:hi.numel()] = hi
+                L.mp_ray_hits_from_index(q["hit_index"], hi.numel(), R, q["count"], q["inv_index"], st)
+                continue
+            obb = q["obb"] = obb_all[n] if device_hull else self._setup_box(q["verts"])
+            if self.near_cull and not self.training:
+                # eval: rays of the box that never come within the outlier radius of the body are background, bit for bit
+                # (csrc/geom.hip k_ray_near_body); they are dropped before the sampler
+                L.mp_ray_cull_near(dirs, pose, obb, q["cbound"], far, beta, self.ray_sampler.near, R, group, q["hit_index"],
+                                   q["count"], q["inv_index"], scan_tmp, st)
             else:
-                if device_hull:
-                    obb = obb_all[n]
-                elif self._obb_mode_now() == "hull":
-                    # hull on the host (Qhull, ~3 ms; one extra device sync), search + box on the device
-                    from .obb import hull_search_inputs, obb_record
-                    vhost = verts.cpu().numpy()
-                    buf, nh, nn_, ne = hull_search_inputs(vhost)
-                    if nh > 4096:      # beyond the kernel's LDS tile (a body's hull has a few hundred vertices): the host statement
-                        obb = torch.from_numpy(obb_record(vhost, self.obb_inflate)).to(dev)
-                        buf = None
-                    hb = torch.from_numpy(buf).to(dev) if buf is not None else None
-                    if hb is not None:
-                        o_n, o_e = 3 * nh, 3 * (nh + nn_)
-                        work = torch.empty(2 * nn_, dtype=torch.float64, device=dev)
-                        obb = torch.empty(16, **f32)
-                        L.mp_obb_hull(hb, nh, hb[o_n:], nn_, hb[o_e:], hb[o_e + 3 * ne:], hb[o_e + 6 * ne:], ne, self.obb_inflate,
-                                      work, obb, st)
-                else:
-                    obb = torch.empty(16, **f32)
-                    L.mp_obb(verts, self.obb_inflate, obb, st)
-                if self.near_cull and not self.training:
-                    # eval: rays of the box that never come within the outlier radius of the body are background, bit for bit
-                    # (csrc/geom.hip k_ray_near_body); they are dropped before the sampler
-                    L.mp_ray_cull_near(dirs, pose, obb, cbound, far, beta, rs.near, R, group, hit_index, counts[n:n + 1],
-                                       inv_index, scan_tmp, st)
-                else:
-                    L.mp_ray_cull(dirs, pose, obb, R, group, hit_index, counts[n:n + 1], inv_index, scan_tmp, st)
-            q["obb"] = obb
-        if hull_status is not None:      # the one host sync of the call: sizes the per-person workspaces (+ the hulls' status)
+                L.mp_ray_cull(dirs, pose, obb, R, group, q["hit_index"], q["count"], q["inv_index"], scan_tmp, st)
+
+        # the one host sync of the call: sizes the per-person workspaces (+ the hulls' status)
+        if hull_status is None:
+            n_hit = counts.tolist()
+        else:
             both = torch.cat([counts, hull_status[:, 3]]).tolist()
             n_hit = both[:len(persons)]
             if any(both[len(persons):]):
@@ -368,86 +314,64 @@ class Multiply(nn.Module):
                 # shows as a growing `hull_host_fallbacks` in `last_stats` / the bench line, not only as a warning
                 self.hull_host_fallbacks = getattr(self, "hull_host_fallbacks", 0) + 1
                 warnings.warn("device convex hull failed (degenerate vertex configuration): falling back to the host-side hull")
-                return self._setup(input, id, canonical_pose, _beta=_beta, host_hull=True)
-        else:
-            n_hit = counts.tolist()
+                return self._setup_body(input, id, canonical_pose, beta, host_hull=True)
         return dict(dev=dev, R=R, uv=uv, K=K, pose=pose, dirs=dirs, far=far, per=per, persons=persons, n_hit=n_hit,
                     group=group, beta=beta, counts=counts, hull_status=hull_status)
 
-    def _vote_groups_check(self, n_groups, grp):
-        """Every rank of the vote's process group must contribute the same number of convergence-group flags (uneven ray shards
-        with convergence_group set would mismatch the collective's sizes -- undefined behaviour on RCCL).  A FIXED-size collective,
-        issued by every rank on every call in which the flag count is not 1 by construction (convergence_group set), whatever
-        its own n_groups: a rank that skipped it would desynchronise the collective sequence it is meant to protect."""
-        import torch.distributed as dist
-        t = torch.tensor([n_groups, -n_groups], device=self.density.beta.device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=grp)
-        hi, lo = int(t[0]), int(-t[1])
-        if hi != n_groups or lo != n_groups:
-            raise RuntimeError(f"sampler vote: the ranks hold different numbers of convergence groups (this rank {n_groups}, "
-                               f"range {lo}..{hi}); shard the rays at multiples of convergence_group, equally many per rank")
+    def _setup_pose(self, p, smpl, canonical_pose, verts, count, R):
+        """person p's record: the posed body (into `verts`), its nearest-vertex tables and the ray-index workspaces"""
+        dev = verts.device
+        server = self.smpl_server_list[p]
+        prm = torch.cat([smpl["params"][0, p, 0:1], smpl["trans"][0, p], smpl["pose"][0, p], smpl["shape"][0, p]]).contiguous()
+        if canonical_pose:   # multiply.py:197-202
+            prm = prm.clone()
+            prm[1:4] = 0
+            prm[4:76] = 0
+            prm[4 + 5] = np.pi / 6
+            prm[4 + 8] = -np.pi / 6
+        tfs = torch.empty(NUM_JOINTS, 4, 4, dtype=torch.float32, device=dev)
+        jnts = torch.empty(NUM_JOINTS, 3, dtype=torch.float32, device=dev)
+        server.pose_into(prm, verts, tfs, jnts)
+        vsorted, cbound = hip.knn_tables(verts, self.deformer_list[p].knn_perm)
+        btab = hip.blend_table(server.tables.lbs_weights, tfs)        # per-vertex inverse blended transform of this pose
+        hit_index = torch.empty(R, dtype=torch.int32, device=dev)
+        inv_index = torch.empty(R, dtype=torch.int32, device=dev)
+        cond = (smpl["pose"][0, p, 3:] / np.pi).contiguous()          # multiply.py:270
+        return dict(verts=verts, tfs=tfs, btab=btab, vsorted=vsorted, cbound=cbound, hit_index=hit_index, obb=None,
+                    inv_index=inv_index, count=count, cond=cond, prm=prm,
+                    rest_joints=server.rest_joints() if self.training else None)
 
-    # ---- ErrorBoundSampler.get_z_vals (ray_sampler.py:66-220) in four steps, so that the persons of a call can advance
-    #      iteration by iteration together (one convergence-vote collective per iteration for ALL persons, _sample_persons)
-    def _sampler_open(self, cx, n, p, draws=None):
-        """workspaces of person p's sampler + mp_sampler_init.  draws = None: eval-mode determinism; else the training
-        randomness {t_rand [R_p,NE], u_final [R_p,N], extra_idx [max_iters,N_extra] int32}."""
-        L = hip.lib()
-        dev = cx["dev"]
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        st = hip.stream()
-        rs = self.ray_sampler
-        cfg = self._sampler_cfg()
-        NE, NS, NX = rs.N_samples_eval, rs.N_samples, rs.N_samples_extra
-        NZ = NS + NX + 2
-        ZM = NE * rs.max_total_iters
-        R, group = cx["R"], cx["group"]
-        n_groups = (R + group - 1) // group
-        pp = cx["per"][p]
-        Rp = max(int(cx["n_hit"][n]), 1)
-        imp = self.foreground_implicit_network_list[p]
-        pk_sdf = hip.packed(imp, "sdf", 2)
-        pk_sdf.refresh(pp["cond"], force=self.training)
-        zs = torch.empty(Rp, ZM, **f32); sdfs = torch.empty(Rp, ZM, **f32)
-        nz = torch.empty(Rp, **i32); znew = torch.empty(Rp, NE, **f32); sdfnew = torch.empty(Rp, NE, **f32)
-        betar = torch.empty(Rp, **f32); active = torch.empty(Rp, **i32)
-        gflag = torch.empty((rs.max_total_iters + 1) * n_groups, **i32)
-        zp = cx.get("_zp_sampler")                   # the samplers' device counters of ALL persons of the call: one fill
-        if zp is None:
-            zp = cx["_zp_sampler"] = hip.ZeroPool(dev, 1 << 16)
-        zfinal = torch.empty(Rp, NZ, **f32); iters = zp.take(n_groups, dtype=torch.int32)
-        any_active = zp.take(rs.max_total_iters + 1, dtype=torch.int32)
-        state = hip.MpSamplerState(zs.data_ptr(), sdfs.data_ptr(), nz.data_ptr(), znew.data_ptr(),
-                                   sdfnew.data_ptr(), betar.data_ptr(), active.data_ptr(), gflag.data_ptr(),
-                                   zfinal.data_ptr(), iters.data_ptr(), any_active.data_ptr())
-        train = draws is not None
-        t_rand = draws["t_rand"] if train else None
-        L.mp_sampler_init(C.byref(cfg), C.byref(state), cx["far"], pp["hit_index"], pp["count"], Rp, group, R, t_rand, st)
-        xc_new = torch.empty(Rp * NE, 3, **f32)
-        work = torch.empty(Rp * NE, **i32)
-        wcount = zp.take(rs.max_total_iters + 1, dtype=torch.int32)
-        # training: the rays are random pixels -- the warp first groups a call's samples by their nearest vertex cluster
-        bin_work = torch.empty(int(L.mp_warp_bin_work_bytes(Rp * NE)), dtype=torch.uint8, device=dev) if train else None
-        return dict(cx=cx, p=p, pp=pp, Rp=Rp, NE=NE, cfg=cfg, state=state, train=train, draws=draws, pk_sdf=pk_sdf, n_groups=n_groups,
-                    zs=zs, sdfs=sdfs, nz=nz, znew=znew, sdfnew=sdfnew, betar=betar, active=active, gflag=gflag, zfinal=zfinal,
-                    iters=iters, any_active=any_active, xc_new=xc_new, work=work, wcount=wcount, bin_work=bin_work)
+    def _setup_device_hull(self, verts_all, zp):
+        """the convex hulls (gift wrapping), the candidate searches and the boxes of ALL bodies in one batch on the device: no
+        host round trip; the status words are read with the hit counts (a failure -- exactly coplanar vertices tying into a
+        non-manifold patch -- repeats the setup with the host-side hull) -> (boxes [P][16], status [P][8])"""
+        L, dev, n = hip.lib(), verts_all.device, verts_all.shape[0]
+        hull_status = zp.take(n, 8, dtype=torch.int32)
+        work = torch.empty(n, int(L.mp_obb_hull_device_work_bytes()), dtype=torch.uint8, device=dev)
+        obb_all = torch.empty(n, 16, dtype=torch.float32, device=dev)
+        L.mp_obb_hull_device(verts_all, NUM_VERTS, n, self.obb_inflate, work, obb_all, hull_status, hip.stream())
+        return obb_all, hull_status
 
-    def _sampler_query(self, s, it):
-        """iteration `it`, first half: warp the new samples, query the SDF net, evaluate the error bound (sets the group flags)"""
-        L, st = hip.lib(), hip.stream()
-        cx, pp, Rp, NE, train = s["cx"], s["pp"], s["Rp"], s["NE"], s["train"]
-        pk_sdf, any_active, wcount = s["pk_sdf"], s["any_active"], s["wcount"]
-        with self._ph("sampler_warp"):
-            L.mp_warp_inverse(None, cx["dirs"], cx["pose"], pp["hit_index"], pp["count"], s["znew"], NE, NE, Rp, pp["vsorted"],
-                              pp["cbound"], pp["btab"], 0 if train else 1, s["active"], any_active[it:it + 1], s["xc_new"], None,
-                              s["sdfnew"], s["work"], wcount[it:it + 1], s["bin_work"] if train else None, st)
-        with self._ph("sampler_mlp_sdf"):
-            self._sampler_sdf(s, it)
-        with self._ph("sampler_bound"):
-            L.mp_sampler_bound(C.byref(s["cfg"]), C.byref(s["state"]), cx["beta"], pp["hit_index"], pp["count"], Rp, cx["group"],
-                               cx["R"], it, st)
+    def _setup_box(self, verts):
+        """one body's cull box [16] without the batched device hull: the hull on the host, or the principal-axes box"""
+        L, st, dev = hip.lib(), hip.stream(), verts.device
+        obb = torch.empty(16, dtype=torch.float32, device=dev)
+        if self._obb_mode_now() != "hull":
+            L.mp_obb(verts, self.obb_inflate, obb, st)
+            return obb
+        # hull on the host (Qhull, ~3 ms; one extra device sync), search + box on the device
+        from .obb import hull_search_inputs, obb_record
+        vhost = verts.cpu().numpy()
+        buf, nh, nn_, ne = hull_search_inputs(vhost)
+        if nh > 4096:      # beyond the kernel's LDS tile (a body's hull has a few hundred vertices): the host statement
+            return torch.from_numpy(obb_record(vhost, self.obb_inflate)).to(dev)
+        hb = torch.from_numpy(buf).to(dev)
+        o_n, o_e = 3 * nh, 3 * (nh + nn_)
+        work = torch.empty(2 * nn_, dtype=torch.float64, device=dev)
+        L.mp_obb_hull(hb, nh, hb[o_n:], nn_, hb[o_e:], hb[o_e + 3 * ne:], hb[o_e + 6 * ne:], ne, self.obb_inflate, work, obb, st)
+        return obb
 
+    # ---- the error-bound sampler: the driver lives in ray_sampler.py (SamplerRun, sample_persons); these delegate
     def resolved_sampler_sdf_mode(self, p=0):
         """`sampler_sdf_mode` with 'auto' resolved for person p's network (see __init__)"""
         mode = getattr(self, "sampler_sdf_mode", "auto")
@@ -456,97 +380,9 @@ class Multiply(nn.Module):
         from . import train as T
         return "bf16x3" if T.fused_sdf_supported(self.foreground_implicit_network_list[p]) else "f16x2"
 
-    def _sampler_sdf(self, s, it):
-        """the sampler's network queries of iteration `it` (`self.sampler_sdf_mode`, MP_SAMPLER_SDF):
-        'bf16x3' (what 'auto' resolves to for the shipped network shape): the value sweep of the training path's layer-fused
-        kernel (mp_tf_sdf_val: split-bfloat16 products, fp32 activations, ~2^-16 per product) -- near-fp32 queries, 3x the time
-        of the half-precision kernel; 'f16x2': split activations on the half-precision weights (mp_mlp_sdf_x2, 2x the time, a
-        quarter of the mean depth error, any network shape); 'f16': the fused half-precision kernel (csrc/mlp.hip k_mlp_sdf);
-        'bf16x3-layerwise': the bf16x3 arithmetic layer by layer (the independent implementation tools/sampler_precision.py
-        first measured with; reads the worklist count on the host)."""
-        L, st = hip.lib(), hip.stream()
-        pk_sdf, wcount = s["pk_sdf"], s["wcount"]
-        mode = self.resolved_sampler_sdf_mode(s["p"])
-        if mode == "bf16x3":
-            # the value sweep of the training path's layer-fused kernel (csrc/tfuse.hip k_tf_sdf_val): same worklist, device-side count
-            fs = s.get("fs")
-            if fs is None:
-                from . import train as T
-                imp = self.foreground_implicit_network_list[s["p"]]
-                if not T.fused_sdf_supported(imp):
-                    raise NotImplementedError("sampler_sdf_mode 'bf16x3' needs the network shape csrc/tfuse.hip is specialised for")
-                # once per call and person; inside a training forward (TrainGraph.run: TrainState.begin has just resolved the
-                # iteration's weights) the shared layers are used, anywhere else the state resolves the weights itself
-                lins = T.train_state(self).lins[id(imp)] if self.__dict__.get("_mp_in_train_graph") else None
-                fs = s["fs"] = T.fused_sdf_state(imp, lins).refresh(s["pp"]["cond"])
-            L.mp_tf_sdf_val(fs.wpack, fs.bias_all, s["xc_new"], s["work"], wcount[it:it + 1], s["Rp"] * s["NE"], s["sdfnew"], st)
-            return
-        if mode == "bf16x3-layerwise":          # the measurement path of tools/sampler_precision.py (host read per iteration)
-            from . import train as T
-            n = int(wcount[it])
-            if n > 0:
-                idx = s["work"][:n].long()
-                x = s["xc_new"][idx].contiguous()
-                imp = self.foreground_implicit_network_list[s["p"]]
-                lins = [T.LinW(l) for l in imp.layers()]
-                parts = [T.ImplicitTrain(imp, x[c0:c0 + (1 << 18)], s["pp"]["cond"], fwd=False, lins=lins).out[:, 0].clone()
-                         for c0 in range(0, n, 1 << 18)]
-                s["sdfnew"].view(-1)[idx] = torch.cat(parts)
-            return
-        if mode not in ("f16", "f16x2"):
-            raise ValueError(f"sampler_sdf_mode {mode!r}: expected 'f16x2', 'f16', 'bf16x3' or 'bf16x3-layerwise'")
-        # 'f16x2': split activations on the same packed half-precision weights (csrc/mlp.hip k_mlp_sdf_x2)
-        fn = L.mp_mlp_sdf_x2 if mode == "f16x2" else L.mp_mlp_sdf
-        fn(C.byref(pk_sdf.net), pk_sdf.wpack, pk_sdf.bias, s["xc_new"], s["work"], wcount[it:it + 1], s["Rp"] * s["NE"],
-           s["sdfnew"], st)
-
-    def _sampler_resample(self, s, it):
-        """iteration `it`, second half: new samples where the bound is not met (or, converged, the final inverse-CDF draw)"""
-        L, st = hip.lib(), hip.stream()
-        cx, pp, draws = s["cx"], s["pp"], s["draws"]
-        u_final = draws["u_final"] if s["train"] else None
-        extra_idx = draws["extra_idx"] if s["train"] else None
-        with self._ph("sampler_resample"):
-            L.mp_sampler_resample(C.byref(s["cfg"]), C.byref(s["state"]), cx["beta"], cx["far"], pp["hit_index"], pp["count"],
-                                  s["Rp"], cx["group"], cx["R"], it, u_final, extra_idx, st)
-
-    def _sampler_close(self, s):
-        s["pp"]["_sampler_keep"] = tuple(s[k] for k in ("zs", "sdfs", "nz", "znew", "sdfnew", "betar", "active", "gflag",
-                                                       "any_active", "xc_new", "work", "draws"))
-        return s["zfinal"], s["iters"], s["wcount"]
-
-    def _sample_persons(self, cx, draws_by_person=None, persons=None):
-        """The sampler of EVERY person of the call, advancing iteration by iteration together -> {p: (zfinal, iters, wcount)}.
-        The persons' samplers are independent (same launches as one after the other, other order); what the interleaving buys
-        is the data-parallel convergence vote: the reference's `not_converge = beta.max() > beta0` (ray_sampler.py:137) spans
-        ALL rays of the call -- here the rays of every rank -- and with `sampler_vote_group` set ONE MAX all-reduce per sampler
-        iteration carries the flags of all persons (P x n_groups ints; P x max_total_iters collectives before), between the
-        bound and the resampling kernels: the N-rank step samples exactly like the single-process step."""
-        persons = list(cx["persons"]) if persons is None else list(persons)
-        order = {p: n for n, p in enumerate(cx["persons"])}
-        states = [self._sampler_open(cx, order[p], p, None if draws_by_person is None else draws_by_person[p]) for p in persons]
-        vote = self.sampler_vote_group is not None
-        if vote and states:
-            import torch.distributed as dist
-            grp = None if self.sampler_vote_group is True else self.sampler_vote_group
-            ng = states[0]["n_groups"]
-            if self.convergence_group is not None:      # (None: one flag per person and call on every rank, by construction)
-                self._vote_groups_check(ng, grp)
-        for it in range(self.ray_sampler.max_total_iters):
-            for s in states:
-                self._sampler_query(s, it)
-            if vote and states:
-                flags = [s["gflag"][it * ng:(it + 1) * ng] for s in states]
-                if len(flags) == 1:
-                    dist.all_reduce(flags[0], op=dist.ReduceOp.MAX, group=grp)
-                else:
-                    packed = torch.cat(flags)
-                    dist.all_reduce(packed, op=dist.ReduceOp.MAX, group=grp)
-                    torch._foreach_copy_(flags, list(packed.split(ng)))
-                self.vote_collectives = getattr(self, "vote_collectives", 0) + 1
-            for s in states:
-                self._sampler_resample(s, it)
-        return {s["p"]: self._sampler_close(s) for s in states}
+    def _sample_persons(self, cx, draws_by_person=None, persons=None, shared_lins=None):
+        """The sampler of every person of the call, advancing together -> {p: (zfinal, iters, wcount)} (ray_sampler.sample_persons)"""
+        return sample_persons(self, cx, draws_by_person, persons, shared_lins)
 
     def _sample_person(self, cx, n, p, draws=None):
         """ErrorBoundSampler.get_z_vals for person p's rays (ray_sampler.py:66-220): returns zfinal [R_p][N+N_extra+2],
@@ -577,7 +413,7 @@ class Multiply(nn.Module):
         if isinstance(cond, dict):
             cond = cond["smpl"]
         cvec = cond.detach().to(dev).float().reshape(-1).contiguous()
-        beta = (self.density.beta.detach().abs() + self.density.beta_min).reshape(1).float().contiguous()
+        beta = self._beta_value()
         per = {person_id: dict(verts=verts, tfs=tfs, btab=btab, vsorted=vsorted, cbound=cbound,
                                hit_index=torch.arange(R, **i32), count=torch.full((1,), R, **i32), cond=cvec)}
         cx = dict(dev=dev, R=R, pose=pose.reshape(16).contiguous(), dirs=dirs, far=far, per=per, persons=[person_id], n_hit=[R],
@@ -589,77 +425,72 @@ class Multiply(nn.Module):
     def _forward_eval(self, input, id, canonical_pose, composite=True):
         """composite=False: stop after the per-person sampling + shading and return the per-person sample arrays (in hit
         order) -- the person-sharded multi-GPU mode composites them elsewhere (parallel.render_person_sharded)."""
-        L = hip.lib()
         # async_setup (inputs resident and complete, e.g. a render loop over preloaded frames): the setup's host sync waits
         # for the setup kernels only, not for the previous frame still in flight on this stream
         cx = self._setup(input, id, canonical_pose, side_stream=bool(getattr(self, "async_setup", False)))
-        dev, R, dirs, far, pose, beta = cx["dev"], cx["R"], cx["dirs"], cx["far"], cx["pose"], cx["beta"]
-        per, persons, n_hit = cx["per"], cx["persons"], cx["n_hit"]
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        st = hip.stream()
-        rs = self.ray_sampler
-        NZ = rs.N_samples + rs.N_samples_extra + 2
-        S = NZ - 1
+        dirs, far, per, persons, n_hit = cx["dirs"], cx["far"], cx["per"], cx["persons"], cx["n_hit"]
         stats = {"n_hit": n_hit, "iters": [], "n_sdf_evals": [], "n_shaded": [], "hull_host_fallbacks": getattr(self, "hull_host_fallbacks", 0)}
 
         for n, p in enumerate(persons):
-            pp = per[p]
-            Rp = max(int(n_hit[n]), 1)
-            imp, ren, dfm = self.foreground_implicit_network_list[p], self.foreground_rendering_network_list[p], \
-                self.deformer_list[p]
-            skin_w = self.smpl_server_list[p].tables.lbs_weights
             zfinal, iters, wcount = self._sample_person(cx, n, p)
-            # ---- shading of the final samples (multiply.py:294-308, 403-405)
-            npts = Rp * S
-            xc = torch.empty(npts, 3, **f32)
-            sdf = torch.empty(npts, **f32)
-            nrm = torch.zeros(npts, 3, **f32)
-            rgb = torch.zeros(npts, 3, **f32)
-            work2 = torch.empty(npts, **i32)
-            need = torch.empty(npts, dtype=torch.uint8, device=dev)
-            nn_posed = torch.empty(npts, **i32)
-            wc2 = wcount[rs.max_total_iters:]
-            ph = self._ph("shade_warp"); ph.__enter__()
-            L.mp_warp_inverse_shade(dirs, pose, pp["hit_index"], pp["count"], zfinal, NZ, S, Rp, pp["vsorted"], pp["cbound"],
-                                    pp["btab"], 1, beta, xc, None, need, sdf, work2, wc2, nn_posed, None, st)
-            ph.__exit__()
-            jinv = torch.empty(npts, 9, **f32)
-            ph = self._ph("shade_jacobian"); ph.__enter__()
-            L.mp_warp_jacobian(xc, need, pp["count"], Rp, S, 0, dfm.vsorted_c, dfm.cbound_c, pp["btab"], jinv, None, nn_posed,
-                               dfm.verts_c_flat, st)
-            ph.__exit__()
-            pk_full = hip.packed(imp, "full", 2)
-            pk_full.refresh(pp["cond"])
-            pk_col = hip.packed(ren, "color", 2)
-            pk_col.refresh(hip.pose_embed(ren)(pp["cond"]))
-            feat = torch.empty(((npts + 255) // 256) * 4 * 8 * 4 * 1024, dtype=torch.uint8, device=dev)
-            if self.shade_mode == "reverse":     # value sweep (parks the sigmoids) + reverse sweep for the normals
-                with self._ph("mlp_shade"):
-                    hip.shade_rev_launch(pk_full, hip.grad_net(imp), xc, jinv, work2, wc2, npts, sdf, nrm, feat)
-            else:
-                with self._ph("mlp_shade"):
-                    L.mp_mlp_shade(C.byref(pk_full.net), pk_full.wpack, pk_full.bias, xc, jinv, work2, wc2, npts, sdf, nrm, feat,
-                                   st)
-            with self._ph("mlp_color"):
-                L.mp_mlp_color(C.byref(pk_col.net), pk_col.wpack, pk_col.bias, xc, nrm, feat, work2, wc2, npts, rgb, st)
+            shaded = self._shade_person(cx, n, p, zfinal, wcount)
             stats["iters"].append(iters); stats["n_sdf_evals"].append(wcount)
-            per[p].update(zfinal=zfinal, sdf=sdf, rgb=rgb, nrm=nrm, xc=xc, work2=work2, wc2=wc2)
+            per[p].update(zfinal=zfinal, **shaded)
 
+        stats["n_shaded"] = [per[p]["wc2"] for p in persons]
+        self.last_stats = stats
         if not composite:
-            stats["n_shaded"] = [per[p]["wc2"] for p in persons]
-            self.last_stats = stats
             self._last = dict(per=per, dirs=dirs, far=far, persons=persons, cx=cx)
             return {p: dict(z=per[p]["zfinal"], sdf=per[p]["sdf"], rgb=per[p]["rgb"], nrm=per[p]["nrm"],
                             hit_index=per[p]["hit_index"][:max(int(n_hit[n]), 1)], n_hit=int(n_hit[n]))
                     for n, p in enumerate(persons)}
-
-        stats["n_shaded"] = [per[p]["wc2"] for p in persons]
-        self.last_stats = stats
         bg_rgb = self._background(input, cx)
         out, bg_T, keep = self._composite(cx, persons, bg_rgb)
         self._last = dict(per=per, dirs=dirs, far=far, bg_T=bg_T, bg_rgb=bg_rgb, persons=persons, keep=keep)
         return out
+
+    def _shade_person(self, cx, n, p, zfinal, wcount):
+        """shading of person p's final samples (multiply.py:294-308, 403-405): warp to canonical space, Jacobian, weight
+        packing, SDF + normals, colour -> the arrays the compositing reads, in hit order"""
+        L, st = hip.lib(), hip.stream()
+        dev, pp = cx["dev"], cx["per"][p]
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        rs = self.ray_sampler
+        NZ = rs.N_samples + rs.N_samples_extra + 2
+        S = NZ - 1
+        Rp = max(int(cx["n_hit"][n]), 1)
+        imp, ren, dfm = self.foreground_implicit_network_list[p], self.foreground_rendering_network_list[p], \
+            self.deformer_list[p]
+        npts = Rp * S
+        xc = torch.empty(npts, 3, **f32)
+        sdf = torch.empty(npts, **f32)
+        nrm = torch.zeros(npts, 3, **f32)
+        rgb = torch.zeros(npts, 3, **f32)
+        work2 = torch.empty(npts, **i32)
+        need = torch.empty(npts, dtype=torch.uint8, device=dev)
+        nn_posed = torch.empty(npts, **i32)
+        wc2 = wcount[rs.max_total_iters:]
+        with self._ph("shade_warp"):
+            L.mp_warp_inverse_shade(cx["dirs"], cx["pose"], pp["hit_index"], pp["count"], zfinal, NZ, S, Rp, pp["vsorted"],
+                                    pp["cbound"], pp["btab"], 1, cx["beta"], xc, None, need, sdf, work2, wc2, nn_posed, None, st)
+        jinv = torch.empty(npts, 9, **f32)
+        with self._ph("shade_jacobian"):
+            L.mp_warp_jacobian(xc, need, pp["count"], Rp, S, 0, dfm.vsorted_c, dfm.cbound_c, pp["btab"], jinv, None, nn_posed,
+                               dfm.verts_c_flat, st)
+        pk_full = hip.packed(imp, "full", 2)
+        pk_full.refresh(pp["cond"])
+        pk_col = hip.packed(ren, "color", 2)
+        pk_col.refresh(hip.pose_embed(ren)(pp["cond"]))
+        feat = torch.empty(hip.feat_frag_bytes(npts), dtype=torch.uint8, device=dev)
+        with self._ph("mlp_shade"):
+            if self.shade_mode == "reverse":     # value sweep (parks the sigmoids) + reverse sweep for the normals
+                hip.shade_rev_launch(pk_full, hip.grad_net(imp), xc, jinv, work2, wc2, npts, sdf, nrm, feat)
+            else:
+                L.mp_mlp_shade(C.byref(pk_full.net), pk_full.wpack, pk_full.bias, xc, jinv, work2, wc2, npts, sdf, nrm, feat, st)
+        with self._ph("mlp_color"):
+            L.mp_mlp_color(C.byref(pk_col.net), pk_col.wpack, pk_col.bias, xc, nrm, feat, work2, wc2, npts, rgb, st)
+        return dict(sdf=sdf, rgb=rgb, nrm=nrm, xc=xc, work2=work2, wc2=wc2)
 
     def _background(self, input, cx):
         """NeRF++ background colour of every ray of the call, or None without a frame index (multiply.py:482-484,

@@ -1059,11 +1059,9 @@ class TrainGraph:
         # the samplers of all persons advance together (Multiply._sample_persons): in ray-sharded data-parallel training the
         # convergence vote is then ONE collective per sampler iteration for all persons
         todo = [p for p in persons if self.draws["person"][p].get("z_given") is None]
-        m.__dict__["_mp_in_train_graph"] = True       # (the near-fp32 sampler mode may share this iteration's resolved weights)
-        try:
-            sampled = m._sample_persons(cx, {p: self.draws["person"][p] for p in todo}, persons=todo) if todo else {}
-        finally:
-            m.__dict__["_mp_in_train_graph"] = False
+        # (the near-fp32 sampler mode queries on this iteration's resolved weights: the shared layers are handed in)
+        sampled = m._sample_persons(cx, {p: self.draws["person"][p] for p in todo}, persons=todo,
+                                    shared_lins={p: self.ts.lins[id(m.foreground_implicit_network_list[p])] for p in todo}) if todo else {}
         self.fg = {}
         local = [self._person_forward(n, p, sampled.get(p)) for n, p in enumerate(persons)]
         if m.smpl_surface_weight > 0 or m.zero_pose_weight > 0:

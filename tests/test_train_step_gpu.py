@@ -23,11 +23,11 @@ def _cpu(d):
     return d
 
 
-def _train_setup(H=11, W=11, epoch=301):      # odd size: no ray through the sphere centre (NaN, see test_render_gpu.report)
+def _train_setup(H=11, W=11, epoch=301, P=2):      # odd size: no ray through the sphere centre (NaN, see test_render_gpu.report)
     from multiply_amd.loss import Loss
     from multiply_amd.config import load_config
     from multiply_amd import train
-    model, oracle, inp = build(H=H, W=W)
+    model, oracle, inp = build(P=P, H=H, W=W)
     model.train()
     R = inp["uv"].shape[1]
     gin = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in inp.items()}
@@ -289,6 +289,36 @@ def test_training_step_with_the_near_fp32_sampler_mode():
     model.sampler_sdf_mode = "auto"
     for p in range(2):
         assert TOL.within(report(f"train z_vals person {p}: bf16x3 vs f16 sampler", zs["bf16x3"][p], zs["f16"][p].cpu()), TOL.TRAIN_Z_VALS_F16)
+
+
+def test_training_forward_samples_on_the_weights_of_its_own_iteration():
+    """A weight changed in place WITHOUT a version bump (what torch's fused Adam does, hip._GENERATION) between two training
+    forwards with the same draws: the second forward's sampler queries the new weights (the iteration's resolved layers are handed
+    to it, TrainGraph.run), and a standalone sampler call outside any training forward, which resolves the weights itself, gives
+    the same depths bit for bit."""
+    model, oracle, inp, gin, gt, loss_fn, train = _train_setup(H=8, W=8, P=1)
+    R = inp["uv"].shape[1]
+    assert R == 64 and model.resolved_sampler_sdf_mode(0) == "bf16x3"
+    gin = {**gin, "hit_index": [torch.arange(R)]}
+    draws = train.make_draws(model, model._setup(gin, -1, False), None)
+
+    def training_forward_depths():
+        train.forward_train(model, gin, draws=draws)
+        torch.cuda.synchronize()
+        return model._last_train.fg[0]["zfinal"].clone()
+    z_before = training_forward_depths()
+    g = model.foreground_implicit_network_list[0].layers()[-1].weight_g      # [257, 1]: row 0 scales the sdf output
+    version = g._version
+    g.data[0] *= 1.25
+    assert g._version == version
+    z_after = training_forward_depths()
+    changed = int((z_after != z_before).sum())
+    print(f"[info] depths that moved with the weight: {changed} of {z_after.numel()}")
+    assert changed > 0
+    z_alone, _, _ = model._sample_person(model._setup(gin, -1, False), 0, 0, draws["person"][0])
+    torch.cuda.synchronize()
+    print(f"[info] standalone sampler vs training forward: {int((z_alone != z_after).sum())} depths differ")
+    assert torch.equal(z_alone, z_after)
 
 
 def test_training_step_reduces_loss():
