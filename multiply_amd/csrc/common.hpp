@@ -1,4 +1,4 @@
-// Small device helpers shared by the sampler, warp and compositing kernels.
+// Small device helpers shared by the kernels: density, the wave / workgroup reductions, the per-device LDS attribute.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +26,19 @@ __device__ __forceinline__ float wmax(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
+}
+__device__ __forceinline__ float wmin(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+// block-wide sum for blockDim.x = 256 (4 waves)
+__device__ __forceinline__ float block_sum256(float v, float* sh) {
+    v = wsum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
 }
 // exclusive prefix sum across the 64 lanes of a wave; `total` receives the wave sum
 __device__ __forceinline__ float wave_excl_scan(float v, float& total) {

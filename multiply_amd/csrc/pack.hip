@@ -4,15 +4,10 @@
 // constant conditioning (networks.py:164-165) into the bias.  See include/multiply_hip.h: mp_pack_layer.
 #include <hip/hip_runtime.h>
 #include "../../include/multiply_hip.h"
+#include "common.hpp"
 #include "mlp_core.hpp"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void k_pack_layer(const float* __restrict__ v, const float* __restrict__ g,
                                                    const float* __restrict__ b, int out_dim, int in_dim,
@@ -31,7 +26,7 @@ __global__ __launch_bounds__(64) void k_pack_layer(const float* __restrict__ v, 
         if (g) {
             float ss = 0.0f;
             for (int c = lane; c < in_dim; c += 64) ss += row[c] * row[c];
-            ss = wave_sum(ss);
+            ss = mp::wsum(ss);
             scale = g[src] / sqrtf(ss);
         }
     }
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(64) void k_pack_layer(const float* __restrict__ v, 
         float h = 0.0f;
         if (src >= 0 && hoist_n > 0) {
             for (int c = lane; c < hoist_n; c += 64) h += (row[hoist_col0 + c] * scale) * hoist_vec[c];
-            h = wave_sum(h);
+            h = mp::wsum(h);
         }
         if (lane == 0) bias_out[r] = src >= 0 ? (b[src] + h) * bias_scale : 0.0f;
     }
@@ -84,7 +79,7 @@ __global__ __launch_bounds__(64) void k_pack_layers(const MpPackLayer* __restric
         if (g) {
             float ss = 0.0f;
             for (int c = lane; c < L.in_dim; c += 64) ss += row[c] * row[c];
-            ss = wave_sum(ss);
+            ss = mp::wsum(ss);
             scale = g[src] / sqrtf(ss);
         }
     }
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(64) void k_pack_layers(const MpPackLayer* __restric
         float h = 0.0f;
         if (src >= 0 && L.hoist_n > 0 && hoist_vec) {
             for (int c = lane; c < L.hoist_n; c += 64) h += (row[L.hoist_col0 + c] * scale) * hoist_vec[c];
-            h = wave_sum(h);
+            h = mp::wsum(h);
         }
         if (lane == 0) bias_out[r] = src >= 0 ? (b[src] + h) * L.bias_scale : 0.0f;
     }

@@ -676,170 +676,6 @@ __global__ __launch_bounds__(256) void k_warp_bwd(const float* __restrict__ xc, 
         if (acc[e] != 0.f) atomicAdd(&dtfs[16 * (e / 12) + (e % 12)], acc[e]);
 }
 
-// ---- adjoint of SMPLServer.forward's bone transforms (smpl.py:50-94, lbs.py:276-377) w.r.t. the 86 SMPL parameters
-//   [scale, transl(3), thetas(72), betas(10)];  one thread: 24 joints, a few hundred flops each.
-//   Upstreams (each optional): dtfs (smpl_tfs), dA_ext (the rest-relative transforms A, from the posed vertices'
-//   adjoint), djoints (smpl_jnts), dpf (the pose feature R_j - I, j >= 1), dparams_in (added at the end).
-//   With only dtfs this is mp_smpl_pose_bwd: the hot path's samples reach the pose through the transforms alone.
-__global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __restrict__ params,
-                                const float* __restrict__ tfs_c_inv, const float* __restrict__ rest_joints,
-                                const float* __restrict__ j_shapedirs, const float* __restrict__ dtfs,
-                                const float* __restrict__ dA_ext, const float* __restrict__ djoints,
-                                const float* __restrict__ dpf, const float* __restrict__ dparams_in,
-                                float* __restrict__ dparams) {
-    constexpr int NJ = 24;
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const float scale = params[0];
-    const float* transl = params + 1;
-    const float* th = params + 4;
-    const float* J = rest_joints;
-    float R[NJ][9], G[NJ][12], dG[NJ][12], dJ[NJ][3], dR[NJ][9];
-    for (int j = 0; j < NJ; ++j) {
-        const float ax = th[3 * j] + 1e-8f, ay = th[3 * j + 1] + 1e-8f, az = th[3 * j + 2] + 1e-8f;
-        const float ang = sqrtf(ax * ax + ay * ay + az * az);
-        const float n[3] = {th[3 * j] / ang, th[3 * j + 1] / ang, th[3 * j + 2] / ang};
-        float s, c;
-        sincosf(ang, &s, &c);
-        const float K[9] = {0.f, -n[2], n[1], n[2], 0.f, -n[0], -n[1], n[0], 0.f};
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                float kk = 0.f;
-                for (int k = 0; k < 3; ++k) kk += K[3 * a + k] * K[3 * k + b];
-                R[j][3 * a + b] = (a == b ? 1.f : 0.f) + s * K[3 * a + b] + (1.f - c) * kk;
-            }
-        const int p = parents[j];
-        float rel[3];
-        for (int a = 0; a < 3; ++a) rel[a] = J[3 * j + a] - (j > 0 ? J[3 * p + a] : 0.f);
-        if (j == 0) {
-            for (int a = 0; a < 3; ++a) { for (int b = 0; b < 3; ++b) G[0][4 * a + b] = R[0][3 * a + b]; G[0][4 * a + 3] = rel[a]; }
-        } else {
-            for (int a = 0; a < 3; ++a) {
-                for (int b = 0; b < 3; ++b) {
-                    float v = 0.f;
-                    for (int k = 0; k < 3; ++k) v += G[p][4 * a + k] * R[j][3 * k + b];
-                    G[j][4 * a + b] = v;
-                }
-                float v = G[p][4 * a + 3];
-                for (int k = 0; k < 3; ++k) v += G[p][4 * a + k] * rel[k];
-                G[j][4 * a + 3] = v;
-            }
-        }
-        for (int a = 0; a < 3; ++a) dJ[j][a] = 0.f;
-    }
-    float dscale = 0.f, dtr[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < NJ; ++j) {
-        // tfs_j = tf_j C_j  ->  d tf = dtfs C^T  (rows 0..2; C's last row is [0,0,0,1] for the absolute case C = I)
-        float dtf[12];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 4; ++b) {
-                float v = 0.f;
-                if (dtfs && tfs_c_inv) for (int k = 0; k < 4; ++k) v += dtfs[16 * j + 4 * a + k] * tfs_c_inv[16 * j + 4 * b + k];
-                else if (dtfs) v = dtfs[16 * j + 4 * a + b];
-                dtf[4 * a + b] = v;
-            }
-        // A = G with translation column  A[a][3] = G[a][3] - sum_k G[a][k] J_j[k];  tf = scale A, tf[a][3] += scale transl[a]
-        float dA[12];
-        for (int a = 0; a < 3; ++a) {
-            float A3 = G[j][4 * a + 3];
-            for (int k = 0; k < 3; ++k) A3 -= G[j][4 * a + k] * J[3 * j + k];
-            for (int b = 0; b < 3; ++b) dscale += dtf[4 * a + b] * G[j][4 * a + b];
-            dscale += dtf[4 * a + 3] * (A3 + transl[a]);
-            dtr[a] += scale * dtf[4 * a + 3];
-            for (int b = 0; b < 4; ++b) dA[4 * a + b] = scale * dtf[4 * a + b];
-            if (dA_ext)
-                for (int b = 0; b < 4; ++b) dA[4 * a + b] += dA_ext[16 * j + 4 * a + b];
-        }
-        for (int a = 0; a < 3; ++a) {
-            for (int k = 0; k < 3; ++k) {
-                dG[j][4 * a + k] = dA[4 * a + k] - dA[4 * a + 3] * J[3 * j + k];
-                dJ[j][k] -= dA[4 * a + 3] * G[j][4 * a + k];
-            }
-            dG[j][4 * a + 3] = dA[4 * a + 3];
-        }
-        if (djoints)      // joints_j = scale G_j[:3,3] + scale transl  (smpl.py:79-84)
-            for (int a = 0; a < 3; ++a) {
-                const float dj = djoints[3 * j + a];
-                dscale += dj * (G[j][4 * a + 3] + transl[a]);
-                dtr[a] += scale * dj;
-                dG[j][4 * a + 3] += scale * dj;
-            }
-    }
-    for (int j = NJ - 1; j >= 1; --j) {   // G_j = G_p [R_j | rel_j]
-        const int p = parents[j];
-        float rel[3];
-        for (int a = 0; a < 3; ++a) rel[a] = J[3 * j + a] - J[3 * p + a];
-        float drel[3] = {0.f, 0.f, 0.f};
-        for (int b = 0; b < 3; ++b)
-            for (int c2 = 0; c2 < 3; ++c2) {
-                float v = 0.f;
-                for (int a = 0; a < 3; ++a) v += G[p][4 * a + b] * dG[j][4 * a + c2];
-                dR[j][3 * b + c2] = v;
-            }
-        for (int b = 0; b < 3; ++b)
-            for (int a = 0; a < 3; ++a) drel[b] += G[p][4 * a + b] * dG[j][4 * a + 3];
-        for (int a = 0; a < 3; ++a) {
-            for (int b = 0; b < 3; ++b) {
-                float v = dG[j][4 * a + 3] * rel[b];
-                for (int c2 = 0; c2 < 3; ++c2) v += dG[j][4 * a + c2] * R[j][3 * b + c2];
-                dG[p][4 * a + b] += v;
-            }
-            dG[p][4 * a + 3] += dG[j][4 * a + 3];
-        }
-        for (int a = 0; a < 3; ++a) { dJ[j][a] += drel[a]; dJ[p][a] -= drel[a]; }
-    }
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 3; ++b) dR[0][3 * a + b] = dG[0][4 * a + b];
-        dJ[0][a] += dG[0][4 * a + 3];
-    }
-    if (dpf)              // pose_feature = (R_j - I).flatten, j >= 1 (lbs.py:199)
-        for (int j = 1; j < NJ; ++j)
-            for (int e = 0; e < 9; ++e) dR[j][e] += dpf[9 * (j - 1) + e];
-    for (int i = 0; i < 86; ++i) dparams[i] = 0.f;
-    dparams[0] = dscale;
-    for (int a = 0; a < 3; ++a) dparams[1 + a] = dtr[a];
-    for (int j = 0; j < NJ; ++j) {   // Rodrigues with angle = |theta + 1e-8|, axis = theta / angle (lbs.py:290-296)
-        const float t3[3] = {th[3 * j], th[3 * j + 1], th[3 * j + 2]};
-        const float e3[3] = {t3[0] + 1e-8f, t3[1] + 1e-8f, t3[2] + 1e-8f};
-        const float ang = sqrtf(e3[0] * e3[0] + e3[1] * e3[1] + e3[2] * e3[2]);
-        const float n[3] = {t3[0] / ang, t3[1] / ang, t3[2] / ang};
-        float s, c;
-        sincosf(ang, &s, &c);
-        const float K[9] = {0.f, -n[2], n[1], n[2], 0.f, -n[0], -n[1], n[0], 0.f};
-        float KK[9];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                float kk = 0.f;
-                for (int k = 0; k < 3; ++k) kk += K[3 * a + k] * K[3 * k + b];
-                KK[3 * a + b] = kk;
-            }
-        float dang = 0.f;
-        for (int e = 0; e < 9; ++e) dang += dR[j][e] * (c * K[e] + s * KK[e]);
-        // dK (adjoint of K): from s K and (1-c) K K  ->  dK = s dR + (1-c) (dR K^T + K^T dR)
-        float dK[9];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                float v = s * dR[j][3 * a + b];
-                for (int k = 0; k < 3; ++k) v += (1.f - c) * (dR[j][3 * a + k] * K[3 * b + k] + K[3 * k + a] * dR[j][3 * k + b]);
-                dK[3 * a + b] = v;
-            }
-        const float dn[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
-        float ndot = 0.f;
-        for (int k = 0; k < 3; ++k) ndot += dn[k] * t3[k];
-        for (int i = 0; i < 3; ++i)
-            dparams[4 + 3 * j + i] = dang * e3[i] / ang + dn[i] / ang - ndot * e3[i] / (ang * ang * ang);
-    }
-    if (j_shapedirs)
-        for (int l = 0; l < 10; ++l) {
-            float v = 0.f;
-            for (int j = 0; j < NJ; ++j)
-                for (int k = 0; k < 3; ++k) v += dJ[j][k] * j_shapedirs[(3 * j + k) * 10 + l];
-            dparams[76 + l] = v;
-        }
-    if (dparams_in)
-        for (int i = 0; i < 86; ++i) dparams[i] += dparams_in[i];
-}
-
-
 // ---- adjoint of x_c = I_nn (x - c_nn) w.r.t. explicit points x = verts[idx[s]] (the smpl_surface regulariser under pose
 // optimisation): dverts[v] += sum_{s : idx[s] == v} I_s^T dxc_s, samples in ascending order (idx is drawn with replacement)
 __global__ void k_gather_bwd(const int* __restrict__ idx, int n, const float* __restrict__ jinv, const float* __restrict__ dxc,
@@ -1155,19 +991,6 @@ int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const f
                    const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_warp_bwd, grid1(n), dim3(TB), 0, ST, xc, dxc, jinv, djinv, nn_posed, nn_cano, n, skin_w, tfs, dtfs);
-    return (int)hipGetLastError();
-}
-int mp_smpl_pose_bwd(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
-                     const float* j_shapedirs, const float* dtfs, float* dparams, void* stream) {
-    hipLaunchKernelGGL(k_smpl_pose_bwd, dim3(1), dim3(64), 0, ST, parents, params, tfs_c_inv, rest_joints, j_shapedirs, dtfs,
-                       nullptr, nullptr, nullptr, nullptr, dparams);
-    return (int)hipGetLastError();
-}
-int mp_smpl_pose_bwd_lbs(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
-                         const float* j_shapedirs, const float* dtfs, const float* dA, const float* djoints,
-                         const float* dpf, const float* dparams_in, float* dparams, void* stream) {
-    hipLaunchKernelGGL(k_smpl_pose_bwd, dim3(1), dim3(64), 0, ST, parents, params, tfs_c_inv, rest_joints, j_shapedirs, dtfs,
-                       dA, djoints, dpf, dparams_in, dparams);
     return (int)hipGetLastError();
 }
 int mp_tr_gather_bwd(const int* idx, int n, const float* jinv, const float* dxc, int n_verts, float* dverts, void* stream) {

@@ -296,7 +296,7 @@ class Multiply(nn.Module):
             obb = q["obb"] = obb_all[n] if device_hull else self._setup_box(q["verts"])
             if self.near_cull and not self.training:
                 # eval: rays of the box that never come within the outlier radius of the body are background, bit for bit
-                # (csrc/geom.hip k_ray_near_body); they are dropped before the sampler
+                # (csrc/rays.hip k_ray_near_body); they are dropped before the sampler
                 L.mp_ray_cull_near(dirs, pose, obb, q["cbound"], far, beta, self.ray_sampler.near, R, group, q["hit_index"],
                                    q["count"], q["inv_index"], scan_tmp, st)
             else:

@@ -14,9 +14,9 @@ beat the optimum, which the theorem places ON a hull edge.
 
 `Multiply.obb_mode = "hull"` (the default in training mode, where the hit set decides which samples exist): the HULL is built
 on the host (Qhull, ~3 ms for a posed body; needs the posed vertices there: one device sync per person and call, like the
-reference's own trimesh call), the candidate search and the box run on the device in fp64 (csrc/geom.hip mp_obb_hull; the
+reference's own trimesh call), the candidate search and the box run on the device in fp64 (csrc/obb.hip mp_obb_hull; the
 numpy statement below, `min_volume_obb`, takes 50 ms and stays as the host-side cross-check of that kernel).  `"pca"`
-(csrc/geom.hip k_obb) never leaves the device; it is proven conservative for eval renders (identical pixels)."""
+(csrc/obb.hip k_obb) never leaves the device; it is proven conservative for eval renders (identical pixels)."""
 import numpy as np
 
 

@@ -5,8 +5,8 @@ of the SMPL class it wraps (code/lib/smpl/body_models.py:60-365) for what the ho
 `verts_c`, `joints_c`, `tfs_c_inv`, `faces`, `smpl.faces`, `bone_parents`, `param_canonical`, and
 forward(scale, transl, thetas, betas, absolute=False) -> {'smpl_verts','smpl_tfs','smpl_jnts','smpl_all_jnts',
 'smpl_weights'}; the SMPL sub-module's parameters / buffers keep the reference's state-dict names.
-The arithmetic (blend shapes, Rodrigues, kinematic chain, LBS) runs in csrc/geom.hip (mp_smpl_pose), its adjoint in
-csrc/geom.hip (mp_smpl_verts_bwd) and csrc/train.hip (mp_smpl_pose_bwd_lbs).
+The arithmetic (blend shapes, Rodrigues, kinematic chain, LBS) and its adjoint (mp_smpl_pose, mp_smpl_verts_bwd,
+mp_smpl_pose_bwd_lbs) run in csrc/smpl.hip.
 """
 import os
 import pickle
@@ -154,7 +154,7 @@ class _SMPLModule(nn.Module):
 class _PoseLBS(torch.autograd.Function):
     """smpl_verts (V,3), smpl_jnts (24,3), smpl_all_jnts (29,3) and smpl_tfs (24,4,4) of the 86 parameters: ONE node over the
     forward launches of mp_smpl_pose, whose backward takes any subset of the four upstream gradients (SMPLServer.pose_backward:
-    csrc/geom.hip mp_smpl_verts_bwd, csrc/train.hip mp_smpl_pose_bwd_lbs).  smpl_all_jnts = the joints + the face-keypoint
+    csrc/smpl.hip mp_smpl_verts_bwd, mp_smpl_pose_bwd_lbs).  smpl_all_jnts = the joints + the face-keypoint
     vertices, so its gradient folds into d joints and d verts."""
 
     @staticmethod
@@ -238,13 +238,13 @@ class SMPLServer(nn.Module):
             hip.lib().mp_smpl_verts_bwd(t.posedirs, t.shapedirs, t.lbs_weights, prm, work, dverts, scratch, dlbs, hip.stream())
             dA, dpf, din = dlbs[:NUM_JOINTS * 16], dlbs[NUM_JOINTS * 16:NUM_JOINTS * 16 + 207], dlbs[NUM_JOINTS * 16 + 207:]
         dprm = torch.empty(86, **f32)
-        rest = work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS]          # csrc/geom.hip W_J
+        rest = work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS]          # csrc/smpl.hip W_J
         hip.lib().mp_smpl_pose_bwd_lbs(t.parents, prm, self.tfs_c_inv, rest, t.j_shapedirs, dtfs, dA, djoints, dpf, din, dprm,
                                        hip.stream())
         return dprm
 
     def rest_joints(self):
-        """J (24,3) of the most recent pose_into() call (kernel work buffer, csrc/geom.hip W_J)"""
+        """J (24,3) of the most recent pose_into() call (kernel work buffer, csrc/smpl.hip W_J)"""
         return self._work[3 * NUM_VERTS:3 * NUM_VERTS + 3 * NUM_JOINTS].clone()
 
     def forward(self, scale, transl, thetas, betas, absolute=False):

@@ -192,7 +192,7 @@ def test_hull_box_cull_hit_sets_match_the_published_algorithm():
         gin = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in cur.items()}
         cx = model._setup(gin, -1, False)
         torch.cuda.synchronize()
-        # round 4: the hull itself is built on the device (gift wrapping, csrc/geom.hip k_hull_wrap) -- no host copy of the vertices;
+        # round 4: the hull itself is built on the device (gift wrapping, csrc/obb.hip k_hull_wrap) -- no host copy of the vertices;
         # the host-side hull (Qhull) stays as the fall-back and as the cross-check here: same box volume, same hit sets
         hs = cx["hull_status"].cpu().numpy()
         assert hs.shape == (len(cx["persons"]), 8) and (hs[:, 3] == 0).all(), hs

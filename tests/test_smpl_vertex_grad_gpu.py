@@ -1,6 +1,6 @@
 """SMPLServer.forward under autograd: smpl_verts / smpl_jnts / smpl_all_jnts / smpl_tfs carry gradients to scale, transl,
 thetas and betas (lib/model/smpl.py:50-94 returns them as ordinary autograd tensors), through the posed vertices' adjoint
-(csrc/geom.hip mp_smpl_verts_bwd) and the chain adjoint (csrc/train.hip mp_smpl_pose_bwd_lbs).  Reference: torch autograd on
+(csrc/smpl.hip mp_smpl_verts_bwd) and the chain adjoint (csrc/smpl.hip mp_smpl_pose_bwd_lbs).  Reference: torch autograd on
 the oracle's plain-torch restatement (oracle.multiply_oracle.smpl_server_forward), evaluated in float64 on the fp32 tables and
 on the device's own canonical inverse transforms, so that the comparison measures the device's error alone."""
 import copy
