@@ -78,6 +78,10 @@ __device__ __forceinline__ void stage_pe_tangent(op_t* row, const float (&x)[3],
     }
 }
 
+__device__ __forceinline__ float lane_value(float v, int lane_uniform) {   // lane `lane_uniform`'s v (the index is wave-uniform), in a scalar register
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane_uniform));
+}
+
 template <int NB>
 __device__ __forceinline__ void zero_b(opx8 (&B)[KS_REG][NB]) {
 #pragma unroll
@@ -85,6 +89,42 @@ __device__ __forceinline__ void zero_b(opx8 (&B)[KS_REG][NB]) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) B[k][nb] = (opx8)(op_t)0.0f;
 }
+
+// Work-item ids and positions of a persistent workgroup's tiles, fetched AHEAD of the tile that uses them: the id of the tile after
+// next and -- through the id fetched a tile ago -- the position of the next tile are requested at the head of the current tile and
+// arrive under its network, so that the dependent pair of memory latencies (worklist -> xc) leaves the tile boundary.
+// `slot`: the work index of this lane's point within a tile is base + t * TILE + slot.
+template <int TILE>
+struct TileInputs {
+    const float* __restrict__ xc;
+    const int* __restrict__ worklist;
+    int base, count, slot, stride;   // stride: tiles between two tiles of this workgroup
+    int id_next, id_after;           // ids of the point in the next tile / the tile after next (-1: none)
+    float x_next[3];
+    __device__ __forceinline__ int fetch_id(int t) const {
+        const long long w = (long long)base + (long long)t * TILE + slot;
+        return (slot >= 0 && w < count) ? (worklist ? worklist[w] : (int)w) : -1;
+    }
+    __device__ __forceinline__ void fetch_x(int id, float (&x)[3]) const {
+        x[0] = x[1] = x[2] = 0.0f;
+        if (id >= 0) { x[0] = xc[3 * (size_t)id]; x[1] = xc[3 * (size_t)id + 1]; x[2] = xc[3 * (size_t)id + 2]; }
+    }
+    __device__ __forceinline__ TileInputs(const float* xc_, const int* wl, int base_, int count_, int slot_, int t0, int stride_)
+        : xc(xc_), worklist(wl), base(base_), count(count_), slot(slot_), stride(stride_) {
+        id_next = fetch_id(t0);
+        id_after = fetch_id(t0 + stride);
+        fetch_x(id_next, x_next);
+    }
+    // the inputs of tile t (call once per tile, in order); requests those of the tiles behind it
+    __device__ __forceinline__ int take(int t, float (&x)[3]) {
+        const int id = id_next;
+        x[0] = x_next[0]; x[1] = x_next[1]; x[2] = x_next[2];
+        id_next = id_after;
+        fetch_x(id_next, x_next);
+        id_after = fetch_id(t + 2 * stride);
+        return id;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------ sdf only
 template <int NB, int WAVES>
@@ -101,30 +141,32 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_sdf(const NetDesc net, const
     float* bias_lds = (float*)(smem + L::bias0);
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * in_stride(KS_IN);
     load_bias(net, bias, bias_lds);
+    const ChunkMasks cm = chunk_masks(net);
+    const bool wraps = ring_stream_path<HID_SOFTPLUS>() && ring_can_wrap(net);
+    RingStream rs = {0, false};
+    TileInputs<L::TILE> in(xc, worklist, 0, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
     for (int t = blockIdx.x; t * L::TILE < count; t += gridDim.x) {
-        MP_STAMP_AT(HID_SOFTPLUS, 120, 0);
-        prologue_issue<KS_IN, WAVES>(net, wpack, smem + L::ring, wave, lane);
-        const int w = t * L::TILE + wave * L::PTS + lane;
-        const int id = (lane < L::PTS && w < count) ? (worklist ? worklist[w] : w) : -1;
-        if (lane < L::PTS) {
-            float x[3] = {0.f, 0.f, 0.f};
-            if (id >= 0) { x[0] = xc[3 * (size_t)id]; x[1] = xc[3 * (size_t)id + 1]; x[2] = xc[3 * (size_t)id + 2]; }
-            stage_pe<3, 6, KS_IN>(stage + lane * in_stride(KS_IN), x);
-        }
-        MP_STAMP_AT(HID_SOFTPLUS, 120, 1);
+        MP_STAMP_AT(HID_SOFTPLUS, 120 + MP_TILE_SLOT(t), 0);
+        const bool more = wraps && (long long)(t + gridDim.x) * L::TILE < count;   // this workgroup runs another tile
+        stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem + L::ring, wave, lane);
+        float x[3];
+        const int id = in.take(t, x);
+        if (lane < L::PTS) stage_pe<3, 6, KS_IN>(stage + lane * in_stride(KS_IN), x);
+        MP_STAMP_AT(HID_SOFTPLUS, 120 + MP_TILE_SLOT(t), 1);
         opx8 Bcur[KS_REG][NB];
         f32x4 out[NB];
         zero_b<NB>(Bcur);
-        prologue_wait();  // barrier inside: staging rows visible
-        MP_STAMP_AT(HID_SOFTPLUS, 120, 2);
-        run_net<NB, false, KS_IN, HID_SOFTPLUS, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane);
-        MP_STAMP_AT(HID_SOFTPLUS, 120, 3);
+        stream_prologue_wait(rs);  // first tile; the staging rows are this wave's own
+        MP_STAMP_AT(HID_SOFTPLUS, 120 + MP_TILE_SLOT(t), 2);
+        run_net<NB, false, KS_IN, HID_SOFTPLUS, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
+                                                       SigIO{nullptr, 0}, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
+        MP_STAMP_AT(HID_SOFTPLUS, 120 + MP_TILE_SLOT(t), 3);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int pid = __shfl(id, nb * 16 + (lane & 15));
             if (lane < 16 && pid >= 0) sdf_out[pid] = out[nb][0];
         }
-        MP_STAMP_AT(HID_SOFTPLUS, 121, 0);
+        MP_STAMP_AT(HID_SOFTPLUS, 121 + MP_TILE_SLOT(t), 0);
     }
 }
 
@@ -148,8 +190,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_sdf_x2(const NetDesc net, co
     float* bias_lds = (float*)(smem + L::bias0);
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * STR;
     load_bias(net, bias, bias_lds);
+    const ChunkMasks cm = chunk_masks(net);
+    const bool wraps = ring_stream_path<HID_SOFTPLUS_X2>() && ring_can_wrap(net);
+    RingStream rs = {0, false};
     for (int t = blockIdx.x; t * TILE < count; t += gridDim.x) {
-        prologue_issue<KS_IN, WAVES>(net, wpack, smem + L::ring, wave, lane);
+        const bool more = wraps && (long long)(t + gridDim.x) * TILE < count;
+        stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem + L::ring, wave, lane);
         const int w = t * TILE + wave * WPTS + j;
         const int id = w < count ? (worklist ? worklist[w] : w) : -1;    // every lane knows the id of point lane & 15
         {
@@ -178,8 +224,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_sdf_x2(const NetDesc net, co
         opx8 Bcur[KS_REG][NB];
         f32x4 out[NB];
         zero_b<NB>(Bcur);
-        prologue_wait();  // barrier inside: staging rows visible
-        run_net<NB, false, KS_IN, HID_SOFTPLUS_X2, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane);
+        stream_prologue_wait(rs);  // first tile; the staging rows are this wave's own
+        run_net<NB, false, KS_IN, HID_SOFTPLUS_X2, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
+                                                          SigIO{nullptr, 0}, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
         if (lane < 16 && id >= 0) sdf_out[id] = out[0][0] + out[1][0];
     }
 }
@@ -361,28 +408,31 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, c
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * in_stride(KS_IN);
     load_bias(net, bias, bias_lds);
     constexpr int SIG_LAYER = KS_REG * SIG_CHUNK_BYTES;   // one wave's sigmoids of one layer: 8 (UNORM8) or 16 KiB
+    const ChunkMasks cm = chunk_masks(net);
+    const bool wraps = ring_stream_path<HID_SOFTPLUS_SAVE>() && ring_can_wrap(net);
+    RingStream rs = {0, false};
+    TileInputs<L::TILE> in(xc, worklist, offset, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
     for (int t = blockIdx.x; offset + t * L::TILE < count; t += gridDim.x) {
-        prologue_issue<KS_IN, WAVES>(net, wpack, smem + L::ring, wave, lane);
-        const int w = offset + t * L::TILE + wave * L::PTS + lane;
-        const int id = (lane < L::PTS && w < count) ? (worklist ? worklist[w] : w) : -1;
-        if (lane < L::PTS) {
-            float x[3] = {0.f, 0.f, 0.f};
-            if (id >= 0) { x[0] = xc[3 * (size_t)id]; x[1] = xc[3 * (size_t)id + 1]; x[2] = xc[3 * (size_t)id + 2]; }
-            stage_pe<3, 6, KS_IN>(stage + lane * in_stride(KS_IN), x);
-        }
+        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 0);
+        const bool more = wraps && (long long)offset + (long long)(t + gridDim.x) * L::TILE < count;
+        stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem + L::ring, wave, lane);
+        float x[3];
+        const int id = in.take(t, x);
+        if (lane < L::PTS) stage_pe<3, 6, KS_IN>(stage + lane * in_stride(KS_IN), x);
+        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 1);
         opx8 Bcur[KS_REG][NB];
         f32x4 out[NB];
         zero_b<NB>(Bcur);
-        prologue_wait();
-        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120, 2);
+        stream_prologue_wait(rs);
+        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 2);
         #ifdef MP_EXP_SIGCACHED   // ablation: every tile uses the first workgroup-slots of the buffer (cache resident)
         const SigIO sio = {sigbuf + ((size_t)(blockIdx.x) * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
 #else
         const SigIO sio = {sigbuf + ((size_t)t * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
 #endif
         run_net<NB, false, KS_IN, HID_SOFTPLUS_SAVE, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
-                                                            sio);
-        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120, 3);
+                                                            sio, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
+        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 3);
         // features in the colour kernel's layout: tiles of 64 work items (offset is a multiple of 256), 4 blocks of 16 columns
         const size_t tile = (size_t)(offset / 64) + (size_t)t * 4 + (wave >> 1);
 #pragma unroll
@@ -393,6 +443,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, c
             const int pid = __shfl(id, nb * 16 + (lane & 15));
             if (lane < 16 && pid >= 0) sdf_out[pid] = out[nb][0];
         }
+        MP_STAMP_AT(HID_SOFTPLUS_SAVE, 121 + MP_TILE_SLOT(t), 0);
     }
 }
 
@@ -415,12 +466,22 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
     op_t* tabs = w8 + 256 + wave * (2 * PTS * 48);
     for (int i = threadIdx.x; i < 256; i += blockDim.x) w8[i] = w8_slots[i];
     constexpr int SIG_LAYER = KS_REG * SIG_CHUNK_BYTES;   // one wave's sigmoids of one layer: 8 (UNORM8) or 16 KiB
+    const ChunkMasks cm = chunk_masks(net);
+    const bool wraps = ring_stream_path<HID_SIGMUL>() && ring_can_wrap(net);
+    RingStream rs = {0, false};
+    TileInputs<TILE> in(xc, worklist, offset, count, wave * PTS + (lane & (PTS - 1)), blockIdx.x, gridDim.x);
+    __syncthreads();   // w8 visible
     for (int t = blockIdx.x; offset + t * TILE < count; t += gridDim.x) {
-        const int w = offset + t * TILE + wave * PTS + (lane & (PTS - 1));
-        const int id = w < count ? (worklist ? worklist[w] : w) : -1;     // lanes l and l+32 both know point l's id
+        MP_STAMP_AT(HID_SIGMUL, 120 + MP_TILE_SLOT(t), 0);
+        const bool more = wraps && (long long)offset + (long long)(t + gridDim.x) * TILE < count;
+#ifdef MP_EXP_GRAD_OLD   // ablation: the reverse sweep on the interleaved stream, two chunks in the ring
+        stream_prologue_issue<KS_IN, WAVES, false>(rs, net, wpack, smem, wave, lane);
+#else
+        stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem, wave, lane);
+#endif
+        float x[3];
+        const int id = in.take(t, x);     // lanes l and l+32 both know point l's id
         if (lane < PTS) {   // d PE_f / d x_axis(f), f = 0..38 (embedders.py layout: x, then per octave sin(3), cos(3))
-            float x[3] = {0.f, 0.f, 0.f};
-            if (id >= 0) { x[0] = xc[3 * (size_t)id]; x[1] = xc[3 * (size_t)id + 1]; x[2] = xc[3 * (size_t)id + 2]; }
             op_t* ta = tabs + lane * 48;
             op_t* tb = tabs + PTS * 48 + lane * 48;
 #pragma unroll
@@ -448,7 +509,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
 #endif
         // V_7 = sigma'_7 (.) W_8[sdf row]
         opx8 Bcur[KS_REG][NB];
-        __syncthreads();   // w8 visible
 #pragma unroll
         for (int ks = 0; ks < KS_REG; ++ks) {
             const opx8 wv = *(const opx8*)(w8 + ks * 32 + 8 * gq);
@@ -474,15 +534,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
         }
         float g[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
         f32x4 out[NB];
-#ifdef MP_EXP_GRAD_OLD
-        prologue<KS_IN, WAVES, false>(net, wpack, smem, wave, lane);
-#else
-        prologue<KS_IN, WAVES>(net, wpack, smem, wave, lane);   // barrier inside: tables visible
-#endif
-        MP_STAMP_AT(HID_SIGMUL, 120, 2);
+        MP_STAMP_AT(HID_SIGMUL, 120 + MP_TILE_SLOT(t), 1);
+        stream_prologue_wait(rs);   // first tile; the tables are this wave's own
+        MP_STAMP_AT(HID_SIGMUL, 120 + MP_TILE_SLOT(t), 2);
         run_net<NB, false, KS_IN, HID_SIGMUL, WAVES, GradCapture>(net, wpack, nullptr, smem, Bcur, nullptr, out, wave, lane, sio,
-                                                                   GradCapture{tabs, tabs + PTS * 48, g});
-        MP_STAMP_AT(HID_SIGMUL, 120, 3);
+                                                                   GradCapture{tabs, tabs + PTS * 48, g}, rs, cm,
+                                                                   more ? wpack : nullptr, cm);
+        MP_STAMP_AT(HID_SIGMUL, 120 + MP_TILE_SLOT(t), 3);
         GradCapture::unrotate(g);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -512,7 +570,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
                 normal_out[3 * (size_t)pid + 2] = n2 * inv + poison;
             }
         }
-        __syncthreads();   // the tables are rebuilt by the next tile
+        MP_STAMP_AT(HID_SIGMUL, 121 + MP_TILE_SLOT(t), 0);
+        // no barrier: the tables are per wave, and the wave that rebuilds them for the next tile has read them for this one
     }
 }
 
@@ -534,16 +593,19 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
     float* bias_lds = (float*)(smem + L::bias0);
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * in_stride(KS_IN);
     load_bias(net, bias, bias_lds);
+    const ChunkMasks cm = chunk_masks(net);
+    const bool wraps = ring_stream_path<HID_RELU>() && ring_can_wrap(net);
+    RingStream rs = {0, false};
+    // the id and the position come a tile ahead (TileInputs); the normal is read behind the feature fragments as before
+    TileInputs<L::TILE> in(xc, worklist, 0, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
     for (int t = blockIdx.x; t * L::TILE < count; t += gridDim.x) {
-        MP_STAMP_AT(HID_RELU, 120, 0);
+        MP_STAMP_AT(HID_RELU, 120 + MP_TILE_SLOT(t), 0);
+        const bool more = wraps && (long long)(t + gridDim.x) * L::TILE < count;
         const int w0 = t * L::TILE + wave * L::PTS;   // first work item of this wave
         const int tile = w0 / 64, nb0 = (w0 % 64) / 16;
-        const int w = w0 + lane;
-        // Order of the tile's memory requests (round 6): the work item's id first (one small load), then the first weight chunks
-        // and the 16 KiB of feature fragments of this wave -- none of them depends on the id -- and only then the id -> position /
-        // normal chain, whose two dependent latencies now run beside the big transfers instead of in front of them.
-        const int id = (lane < L::PTS && w < count) ? (worklist ? worklist[w] : w) : -1;
-        prologue_issue<KS_IN, WAVES>(net, wpack, smem + L::ring, wave, lane);
+        float x[3];
+        const int id = in.take(t, x);
+        stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem + L::ring, wave, lane);
         opx8 Bcur[KS_REG][NB];
         const bool live = w0 < count;
 #pragma unroll
@@ -559,17 +621,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
             if (id >= 0) {
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
-                    row[a] = (op_t)xc[3 * (size_t)id + a];
+                    row[a] = (op_t)x[a];
                     row[3 + a] = (op_t)normal[3 * (size_t)id + a];
                 }
             }
         }
-        MP_STAMP_AT(HID_RELU, 120, 1);
+        MP_STAMP_AT(HID_RELU, 120 + MP_TILE_SLOT(t), 1);
         f32x4 out[NB];
-        prologue_wait();
-        MP_STAMP_AT(HID_RELU, 120, 2);
-        run_net<NB, false, KS_IN, HID_RELU, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane);
-        MP_STAMP_AT(HID_RELU, 120, 3);
+        stream_prologue_wait(rs);
+        MP_STAMP_AT(HID_RELU, 120 + MP_TILE_SLOT(t), 2);
+        run_net<NB, false, KS_IN, HID_RELU, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
+                                                   SigIO{nullptr, 0}, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
+        MP_STAMP_AT(HID_RELU, 120 + MP_TILE_SLOT(t), 3);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int pid = __shfl(id, nb * 16 + (lane & 15));
@@ -582,7 +645,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
                 for (int c = 0; c < 3; ++c) rgb_out[3 * (size_t)pid + c] = 1.0f / (1.0f + __expf(-out[nb][c])) + poison;
             }
         }
-        MP_STAMP_AT(HID_RELU, 121, 0);
+        MP_STAMP_AT(HID_RELU, 121 + MP_TILE_SLOT(t), 0);
     }
 }
 
@@ -598,7 +661,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
                                                            float radius, float* __restrict__ bg_rgb) {
     constexpr int KS_IN = 3, NBG = 32;
     using L = Lds<KS_IN, NB, WAVES>;
-    static_assert(L::PTS % NBG == 0, "whole rays per wave");
+    static_assert(L::PTS == NBG, "one ray per wave");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* bias_lds0 = (float*)(smem + L::bias0);
@@ -609,8 +672,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
     load_bias(net_ren, bias_ren, bias_lds1);
     const int n_pts = n_rays * NBG;
     const float ox = cam[0], oy = cam[1], oz = cam[2];
+    // one stream through both packs: density net -> colour net -> density net of the next tile ...
+    const ChunkMasks cm_imp = chunk_masks(net_imp), cm_ren = chunk_masks(net_ren);
+    const bool wraps = ring_stream_path<HID_SOFTPLUS>() && ring_can_wrap(net_imp) && ring_can_wrap(net_ren);
+    RingStream rs = {0, false};
     for (int t = blockIdx.x; t * L::TILE < n_pts; t += gridDim.x) {
-        prologue_issue<KS_IN, WAVES>(net_imp, wp_imp, smem + L::ring, wave, lane);
+        const bool more = wraps && (long long)(t + gridDim.x) * L::TILE < n_pts;
+        stream_prologue_issue<KS_IN, WAVES>(rs, net_imp, wp_imp, smem + L::ring, wave, lane);
         const int q = t * L::TILE + wave * L::PTS + lane;
         const int ray = q / NBG, s = q % NBG;
         float d[3] = {0.f, 0.f, 1.f};
@@ -646,45 +714,59 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
         opx8 Bcur[KS_REG][NB];
         f32x4 out[NB];
         zero_b<NB>(Bcur);
-        prologue_wait();
+        stream_prologue_wait(rs);
         run_net<NB, false, KS_IN, HID_SOFTPLUS, WAVES>(net_imp, wp_imp, bias_lds0, smem + L::ring, Bcur, stage, out, wave,
-                                                       lane);
-        // the colour net's first chunks: behind the last barrier of the network above the ring is free; their latency runs beside
-        // the density / view-direction staging below
-        prologue_issue<KS_IN, WAVES>(net_ren, wp_ren, smem + L::ring, wave, lane);
+                                                       lane, SigIO{nullptr, 0}, NoCapture(), rs, cm_imp, wraps ? wp_ren : nullptr, cm_ren);
+        // the colour net's first chunks came with the tail of the density net's stream; a pack that cannot wrap: behind the last
+        // barrier of the network above the ring is free, their latency runs beside the density / view-direction staging below
+        stream_prologue_issue<KS_IN, WAVES>(rs, net_ren, wp_ren, smem + L::ring, wave, lane);
         if (lane < 16) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) scr[(nb * 16 + lane) * 4 + 3] = fabsf(out[nb][0]);  // AbsDensity (density.py:32-34)
         }
         // colour net: [PE_4(view dir) (27), frame code (hoisted), features (registers)]
         if (lane < L::PTS) stage_pe<3, 4, KS_IN>(stage + lane * in_stride(KS_IN), d);
-        prologue_wait();
-        run_net<NB, false, KS_IN, HID_RELU, WAVES>(net_ren, wp_ren, bias_lds1, smem + L::ring, Bcur, stage, out, wave, lane);
+        stream_prologue_wait(rs);
+        run_net<NB, false, KS_IN, HID_RELU, WAVES>(net_ren, wp_ren, bias_lds1, smem + L::ring, Bcur, stage, out, wave, lane,
+                                                   SigIO{nullptr, 0}, NoCapture(), rs, cm_ren, more ? wp_imp : nullptr, cm_imp);
         if (lane < 16) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) scr[(nb * 16 + lane) * 4 + c] = 1.0f / (1.0f + __expf(-out[nb][c]));
         }
-        __syncthreads();
-        // bg_volume_rendering (multiply.py:682-696): the first lanes composite one ray each
-        if (lane < L::PTS / NBG) {
-            const int r = (t * L::TILE + wave * L::PTS) / NBG + lane;
-            if (r < n_rays) {
-                float acc[3] = {0.f, 0.f, 0.f}, csum = 0.0f;
-                for (int i = 0; i < NBG; ++i) {
-                    const float zi = z_per_ray ? z_bg[(size_t)r * NBG + i] : z_bg[i];
-                    const float zn = i + 1 < NBG ? (z_per_ray ? z_bg[(size_t)r * NBG + i + 1] : z_bg[i + 1]) : 0.f;
-                    const float dist = i + 1 < NBG ? zi - zn : 1e10f;
-                    const float* sp = scr + (lane * NBG + i) * 4;
-                    const float fe = dist * sp[3];
-                    const float alpha = 1.0f - expf(-fe);
-                    const float wgt = alpha * expf(-csum);
-                    acc[0] += wgt * sp[0]; acc[1] += wgt * sp[1]; acc[2] += wgt * sp[2];
-                    csum += fe;
-                }
-                bg_rgb[3 * r] = acc[0]; bg_rgb[3 * r + 1] = acc[1]; bg_rgb[3 * r + 2] = acc[2];
+        // bg_volume_rendering (multiply.py:682-696), the wave's ray over its lanes: lane i evaluates sample i (its two expf), and
+        // the exclusive prefix sum of the free energy and the three weighted sums run as uniform chains over the lanes' values IN
+        // SAMPLE ORDER -- the association of a serial loop over the samples, bit for bit, at one add / one fused multiply-add per
+        // sample instead of the whole sample.  scr is this wave's own: no barrier.
+        const int r = (t * L::TILE + wave * L::PTS) / NBG;
+        if (r < n_rays) {
+            float dist = 0.0f, dens = 0.0f, alpha = 0.0f, col[3] = {0.f, 0.f, 0.f};
+            if (lane < NBG) {
+                const int i = lane;
+                const float zi = z_per_ray ? z_bg[(size_t)r * NBG + i] : z_bg[i];
+                const float zn = i + 1 < NBG ? (z_per_ray ? z_bg[(size_t)r * NBG + i + 1] : z_bg[i + 1]) : 0.f;
+                dist = i + 1 < NBG ? zi - zn : 1e10f;
+                const float* sp = scr + i * 4;
+                dens = sp[3];
+                alpha = 1.0f - expf(-(dist * dens));
+                col[0] = sp[0]; col[1] = sp[1]; col[2] = sp[2];
             }
+            float csum = 0.0f, before = 0.0f;   // before: the sum over the samples in front of this lane's
+#pragma unroll 2   // rolled: unrolled, the lanes' values crowd the scalar registers
+            for (int i = 0; i < NBG; ++i) {
+                before = lane == i ? csum : before;
+                csum = __builtin_fmaf(lane_value(dist, i), lane_value(dens, i), csum);   // the serial loop's csum += dist * density, contracted
+            }
+            const float wgt = alpha * expf(-before);
+            float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll 2   // rolled: unrolled, the lanes' values crowd the scalar registers
+            for (int i = 0; i < NBG; ++i) {
+                const float wi = lane_value(wgt, i);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] = __builtin_fmaf(wi, lane_value(col[c], i), acc[c]);
+            }
+            if (lane == 0) { bg_rgb[3 * r] = acc[0]; bg_rgb[3 * r + 1] = acc[1]; bg_rgb[3 * r + 2] = acc[2]; }
         }
     }
 }

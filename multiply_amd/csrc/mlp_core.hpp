@@ -137,7 +137,9 @@ __device__ unsigned long long mp_stamps[8 * 128 * 4];
 #endif
 #define MP_STAMP_OK(hid) (MP_STAMP_HID < 0 || (hid) == MP_STAMP_HID)
 #define MP_STAMP(ev) do { if (MP_STAMP_OK(HID) && blockIdx.x == 0 && lane == 0 && ci < 120) mp_stamps[((wave) * 128 + ci) * 4 + (ev)] = __builtin_amdgcn_s_memtime(); } while (0)
-// tile-level stamps in slots 120..127 of the same table (tools/tile_timeline.py)
+// tile-level stamps in slots 120..127 of the same table (tools/tile_timeline.py); MP_TILE_SLOT: the workgroup's tiles alternate between
+// slots 120, 121 and 122, 123, so that its last TWO tiles survive (the boundary between them is what the tool reports)
+#define MP_TILE_SLOT(t) (2 * (((t) / (int)gridDim.x) & 1))
 #define MP_STAMP_AT(hid, slot, ev) do { if (MP_STAMP_OK(hid) && blockIdx.x == 0 && (threadIdx.x & 63) == 0) mp_stamps[((threadIdx.x >> 6) * 128 + (slot)) * 4 + (ev)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define MP_STAMP(ev)
@@ -764,10 +766,37 @@ __device__ __forceinline__ void pp_issue(const char* __restrict__ wpack, char* w
     }
 }
 
+template <int P>
+struct PartC { static constexpr int value = P; };   // pp_issue's PART as a value (for a generic lambda)
+
 struct NoCapture {
     template <int NB>
     __device__ __forceinline__ void operator()(int, int, const f32x4 (&)[NB]) const {}
 };
+
+// The weight ring as ONE stream across the tiles of a workgroup (phase-separated stream only).  The packs are the same for every
+// tile, so the ring does not drain and refill at a tile boundary: the DMA that runs two (three) chunks ahead of the M phases wraps
+// past the pack's last chunk into the first chunks of the pack that runs NEXT -- the same pack for the next tile, or, in a kernel
+// that alternates two networks, the other one -- and the ring position carries over.  The prologue (fill three slots, drain, barrier)
+// runs once per workgroup; the workgroup's last network names no successor and issues nothing past its last chunk, so every DMA
+// piece in flight is waited for by the chunk barriers as before.
+struct RingStream {
+    int pos;     // ring slot of the chunk that is multiplied next
+    bool fed;    // the next pack's first chunks are in the ring / on their way already: no prologue
+};
+// one-shot prologue per tile: the interleaved stream (MP_EXP_NOPP, MP_EXP_GRAD_OLD, the forward-mode kernel) and packs too short to
+// wrap (a DMA issued three chunks ahead of a pack's last chunk must land in the SAME next pack)
+template <int HID>
+__host__ __device__ constexpr bool ring_stream_path() {
+#if defined(MP_EXP_NOPP)
+    return false;
+#elif defined(MP_EXP_GRAD_OLD)
+    return HID != HID_SIGMUL;
+#else
+    return true;
+#endif
+}
+__device__ __forceinline__ bool ring_can_wrap(const NetDesc& net) { return net.total_chunks >= RING_SLOTS; }
 
 // One layer of the phase-separated stream (every layer kind of the plain-mode kernels: softplus with or without the
 // stored sigmoids, ReLU, the reverse sweep's multiplication by the stored sigmoids, and -- HIDDEN = false -- the linear
@@ -777,7 +806,8 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                                              const float* bias_lds, char* wring, opx8 (&Bcur)[KS_REG][2], NB_T& Bn,
                                              opx8 (&aq)[AQ_LEN], u32x4 (&sgb)[SIG_BUFS][2], const op_t* stage_wave,
                                              f32x4 (&out)[2], int wave, int lane, const SigIO& sig, Cap& cap, int& ci,
-                                             int& ring_pos, const ChunkMasks& cm, const DmaLanes<KS_IN>& dl, int pp_last) {
+                                             int& ring_pos, const ChunkMasks& cm, const DmaLanes<KS_IN>& dl, int pp_last, bool fed,
+                                             const char* __restrict__ next_wpack, const ChunkMasks& next_cm) {
     constexpr int PF = PP_PF, QN = PP_QN, NT = 2 * KS_REG;   // register-fed A tiles of a chunk, order (ks, mbl)
     constexpr bool BIAS = HID != HID_SIGMUL;                 // the reverse sweep has no bias
     const int g = lane >> 4;
@@ -788,11 +818,22 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
     // readfirstlane: a scalar branch, not an exec-masked region
     const bool late = __builtin_amdgcn_readfirstlane(wave) >= WAVES / 2;
     const ActConst kact = act_const();
+    // the chunk `ahead` chunks down the stream from chunk ci into ring slot `slot`: this pack's, or -- past its end -- one of the
+    // first chunks of the pack that runs next (RingStream); none when the workgroup's last network ends
+    auto issue_ahead = [&](auto part, int ahead, int slot) {
+        const int cn = ci + ahead;
+        const bool wrap = cn > pp_last;
+        if (!wrap || next_wpack != nullptr) {
+            const ChunkMasks m = {{wrap ? next_cm.reg[0] : cm.reg[0], wrap ? next_cm.reg[1] : cm.reg[1]},
+                                  {wrap ? next_cm.in[0] : cm.in[0], wrap ? next_cm.in[1] : cm.in[1]}};
+            pp_issue<KS_IN, decltype(part)::value>(wrap ? next_wpack : wpack, wring, wrap ? cn - pp_last - 1 : cn, slot, m, dl);
+        }
+    };
 #pragma unroll
     for (int c = 0; c < MAX_CHUNKS; ++c) {
         if ((HIDDEN ? c < KS_REG : true) && c < L.n_chunk) {
             MP_STAMP(0);
-            // ring_pos = ci % RING_SLOTS, carried along (a division by 3 per use costs ~8 scalar instructions)
+            // ring_pos: the ring slot of chunk ci, carried along from chunk to chunk and -- on the continuous stream -- from tile to tile
             const int ring_next = ring_pos + 1 == RING_SLOTS ? 0 : ring_pos + 1;
             const char* slot = wring + ring_pos * chunk_bytes(KS_IN) + lane * 16;
             const char* slot_next = wring + ring_next * chunk_bytes(KS_IN) + lane * 16;
@@ -902,7 +943,7 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                 // chunk ci + 2 at the tail of their V phase (below)
                 if constexpr (!REV) dma_wait_all();
                 __syncthreads();
-                if (ci + 3 <= pp_last) pp_issue<KS_IN, 2>(wpack, wring, ci + 3, ring_pos, cm, dl);
+                issue_ahead(PartC<2>{}, 3, ring_pos);
 #elif defined(MP_DMA_EARLY)
                 __syncthreads();   // the late waves issue no DMA in this variant: nothing of theirs to wait for
 #else
@@ -911,7 +952,7 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                 if constexpr (!REV) dma_wait_all();
                 __syncthreads();
 #ifndef MP_EXP_NOLOAD
-                if (ci + 3 <= pp_last) pp_issue<KS_IN>(wpack, wring, ci + 3, ring_pos, cm, dl);   // (ci + 3) % 3 == ring_pos
+                issue_ahead(PartC<0>{}, 3, ring_pos);   // three chunks on, the stream is back at this chunk's slot
 #endif
 #endif
                 MP_STAMP(2);
@@ -954,12 +995,11 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                 if constexpr (HID == HID_SOFTPLUS_SAVE && HIDDEN) __builtin_amdgcn_s_waitcnt(0x0F70 | (SIG8 ? 1 : 2));
                 else if constexpr (!REV) dma_wait_all();
 #ifndef MP_EXP_NOLOAD
+                // (a pack entered through the prologue has its chunk 2 already; one entered from the stream fetches it here)
 #ifdef MP_DMA_SPLIT
-                if (ci >= 1 && ci + 2 <= pp_last)
-                    pp_issue<KS_IN, 1>(wpack, wring, ci + 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1, cm, dl);
+                if (ci >= 1 || fed) issue_ahead(PartC<1>{}, 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1);
 #else
-                if (ci >= 1 && ci + 2 <= pp_last)
-                    pp_issue<KS_IN>(wpack, wring, ci + 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1, cm, dl);
+                if (ci >= 1 || fed) issue_ahead(PartC<0>{}, 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1);
 #endif
 #endif
 #endif
@@ -1160,12 +1200,14 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
 //   stage_wave : this wave's input staging tile in LDS ([16*NB rows][in_stride] halves, rows = columns): the encoded
 //          network input, read on demand as the K operand of K steps 8.. of every layer with use_in.
 //   out  : fp32 rows 0..15 of the `out_chunk` (must be the last chunk of its layer).
-// The caller must have run prologue() (chunks 0 and 1 in ring slots 0 and 1, barrier).
+// The caller must have run prologue() (the pack's first chunks in ring slots 0, 1 (, 2), barrier) -- or, on the phase-separated stream, have
+// been handed the ring by the network that ran before (rs.fed).  rs / cm / next_wpack / next_cm: the continuous weight stream
+// (RingStream); cm = chunk_masks(net), next_cm those of the pack behind next_wpack (nullptr: the ring drains with this network).
 template <int NB, bool FWD, int KS_IN, int HID, int WAVES, typename Cap = NoCapture>
 __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restrict__ wpack, const float* bias_lds,
                                         char* wring, opx8 (&Bcur)[KS_REG][NB], const op_t* stage_wave,
-                                        f32x4 (&out)[NB], int wave, int lane, SigIO sig = SigIO{nullptr, 0},
-                                        Cap cap = Cap()) {
+                                        f32x4 (&out)[NB], int wave, int lane, SigIO sig, Cap cap, RingStream& rs,
+                                        const ChunkMasks& cm, const char* __restrict__ next_wpack, const ChunkMasks& next_cm) {
     int ci = 0;
     // sigmoid fragments of the K steps under construction (HID_SOFTPLUS_SAVE) / about to be applied (HID_SIGMUL): sig_slot
     u32x4 sgb[SIG_BUFS][NB];
@@ -1196,19 +1238,23 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
         // The phase-separated stream keeps THREE chunks in flight (prologue<.., true>: chunks 0, 1 and 2) and fetches
         // chunk ci + 3 behind the barrier that frees chunk ci's slot.
         const int pp_last = net.total_chunks - 1;
-        const ChunkMasks cm = chunk_masks(net);
         const DmaLanes<KS_IN> dl = dma_lanes<KS_IN>(__builtin_amdgcn_readfirstlane(wave) & (WAVES / 2 - 1), lane);
-        int ring_pos = 0;
-        // tile order of the phase-separated stream: (K step, row block); chunk 0's first tiles
+        int ring_pos = rs.pos;
+        const bool fed = rs.fed;
+        // tile order of the phase-separated stream: (K step, row block); chunk 0's first tiles (complete in the ring: from the
+        // prologue, or fetched two chunks before the previous network's last barrier)
 #pragma unroll
         for (int t = 0; t < PP_PF; ++t)
-            aq[t % PP_QN] = *(const opx8*)(wring + (t % 2) * mb_bytes(KS_IN) + (t / 2) * TILE_BYTES + lane * 16);
+            aq[t % PP_QN] = *(const opx8*)(wring + ring_pos * chunk_bytes(KS_IN) + (t % 2) * mb_bytes(KS_IN) + (t / 2) * TILE_BYTES + lane * 16);
         for (; l < net.n_layers && net.layer[l].act != ACT_NONE; ++l)
             run_layer_pp<KS_IN, HID, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave, out,
-                                                  wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last);
+                                                  wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
         for (; l < net.n_layers; ++l)
             run_layer_pp<KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave, out,
-                                                   wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last);
+                                                   wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
+        // handed on: the next pack's chunks 0 and 1 are in flight; or drained: the next prologue starts at slot 0
+        rs.pos = next_wpack != nullptr ? ring_pos : 0;
+        rs.fed = next_wpack != nullptr;
     }
     if constexpr (!PP) {
         for (; l < net.n_layers && net.layer[l].act != ACT_NONE; ++l)
@@ -1218,6 +1264,17 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
     for (; l < net.n_layers; ++l)
         run_layer<NB, FWD, KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave,
                                                      out, wave, lane, sig, cap, ci);
+}
+
+// One network behind its own prologue, nothing handed on (the interleaved-stream kernels; k_mlp_full).
+template <int NB, bool FWD, int KS_IN, int HID, int WAVES, typename Cap = NoCapture>
+__device__ __forceinline__ void run_net(const NetDesc& net, const char* __restrict__ wpack, const float* bias_lds,
+                                        char* wring, opx8 (&Bcur)[KS_REG][NB], const op_t* stage_wave,
+                                        f32x4 (&out)[NB], int wave, int lane, SigIO sig = SigIO{nullptr, 0},
+                                        Cap cap = Cap()) {
+    RingStream rs = {0, false};
+    const ChunkMasks cm = chunk_masks(net);
+    run_net<NB, FWD, KS_IN, HID, WAVES, Cap>(net, wpack, bias_lds, wring, Bcur, stage_wave, out, wave, lane, sig, cap, rs, cm, nullptr, cm);
 }
 
 // Issues the first two weight chunks into ring slots 0 and 1 and synchronises (also publishes the staging rows).
@@ -1247,6 +1304,17 @@ __device__ __forceinline__ void prologue(const NetDesc& net, const char* __restr
                                          int lane) {
     prologue_issue<KS_IN, WAVES, THREE>(net, wpack, wring, wave, lane);
     prologue_wait();
+}
+// The same two halves at the head of a tile of a kernel on the continuous stream: only the workgroup's first tile (and every tile
+// of a pack that cannot wrap) runs them.  rs.fed is uniform over the workgroup, so the barrier inside is too.  The barrier also
+// publishes what the workgroup wrote to LDS before its first tile (bias table); per-tile LDS inputs are per-wave and need none.
+template <int KS_IN, int WAVES, bool THREE = PROLOGUE_THREE>
+__device__ __forceinline__ void stream_prologue_issue(const RingStream& rs, const NetDesc& net, const char* __restrict__ wpack,
+                                                      char* wring, int wave, int lane) {
+    if (!rs.fed) prologue_issue<KS_IN, WAVES, THREE>(net, wpack, wring, wave, lane);
+}
+__device__ __forceinline__ void stream_prologue_wait(const RingStream& rs) {
+    if (!rs.fed) prologue_wait();
 }
 __device__ __forceinline__ void load_bias(const NetDesc& net, const float* __restrict__ bias, float* bias_lds) {
     for (int i = threadIdx.x; i < net.n_layers * BIAS_STRIDE; i += blockDim.x) bias_lds[i] = bias[i];

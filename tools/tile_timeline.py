@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Ablation tool: shader-clock timeline of the LAST tile of workgroup 0 of k_mlp_sdf (library built with -DMP_EXP_STAMP):
+"""Ablation tool: shader-clock timeline of the last TWO tiles of workgroup 0 of k_mlp_sdf (library built with -DMP_EXP_STAMP):
 tile-level phases (input staging, prologue, network, output) and the start time of every weight chunk per wave.
     MP_LIB_PATH=.../libmultiply_hip_stamp.so python tools/tile_timeline.py"""
 import ctypes as C, os, sys
@@ -35,11 +35,29 @@ for _ in range(2):
 torch.cuda.synchronize()
 assert L.mp_debug_stamps(buf.ctypes.data) == 0
 s = buf.reshape(8, 128, 4).astype(np.int64)
-t0 = s[:, 120, 0].min() if s[:, 120, 0].min() > 0 else s[:, 120, 2].min()   # kernels without the staging stamps
-print("tile phases (cycles from the earliest wave's tile start), per wave 0..7")
-for name, (slot, ev) in {"tile start": (120, 0), "inputs staged": (120, 1), "prologue done": (120, 2), "network done": (120, 3),
-                         "outputs written": (121, 0)}.items():
-    print(f"  {name:16s}", (s[:, slot, ev] - t0).tolist())
+# the workgroup's tiles alternate between slots (120, 121) and (122, 123) (MP_TILE_SLOT): its last two tiles survive
+first = lambda base: s[:, base, 0].min() if s[:, base, 0].min() > 0 else s[:, base, 2].min()   # kernels without the staging stamps
+order = sorted((120, 122), key=first)
+if first(order[0]) == 0:          # a workgroup that ran one tile only
+    order = order[1:]
+t0 = first(order[0])
+PH = {"tile start": (0, 0), "inputs staged": (0, 1), "prologue done": (0, 2), "network done": (0, 3), "outputs written": (1, 0)}
+for k, base in enumerate(order):
+    print(f"tile {k + 1 - len(order)} (0 = the workgroup's last): phases in cycles from the earlier tile's start, per wave 0..7")
+    for name, (ds, ev) in PH.items():
+        print(f"  {name:16s}", (s[:, base + ds, ev] - t0).tolist())
+if len(order) == 2:
+    a, b = order
+    med = lambda v: int(np.median(v))
+    head = [med(s[:, x, 2] - s[:, x, 0]) for x in order]
+    net = [med(s[:, x, 3] - s[:, x, 2]) for x in order]
+    tail = [med(s[:, x + 1, 0] - s[:, x, 3]) for x in order]
+    print("per tile, median over the waves:   head (tile start -> first M phase)  network  tail (last V phase -> outputs written)")
+    for k in range(2):
+        print(f"  tile {k - 1}: head {head[k]:6d}  network {net[k]:7d}  tail {tail[k]:6d}   outside run_net {head[k] + tail[k]:6d} = "
+              f"{100.0 * (head[k] + tail[k]) / (head[k] + net[k] + tail[k]):.1f} %")
+    print(f"  tile -1 outputs written -> tile 0 start (median): {med(s[:, b, 0] - s[:, a + 1, 0])}")
+    print(f"  tile period (start to start, median): {med(s[:, b, 0] - s[:, a, 0])} cycles")
 nch = int((s[0, :120, 0] > 0).sum())
 print(f"{nch} chunks; per chunk and wave (0 = first wave of SIMD 0, 4 = second): start, then the spans between the stamps")
 print("  phase-separated layers: waves 0..3: M | V | barrier wait;  waves 4..7: M | barrier wait + DMA issue | V;   old stream: compute | dma wait | barrier")
@@ -48,6 +66,4 @@ for c in range(nch):
     for w in (0, 4):
         r.append((int(s[w, c, 0] - t0), int(s[w, c, 1] - s[w, c, 0]), int(s[w, c, 2] - s[w, c, 1]), int(s[w, c, 3] - s[w, c, 2])))
     print(f"  chunk {c:2d}: wave0 @{r[0][0]:7d} {r[0][1:]}   wave4 @{r[1][0]:7d} {r[1][1:]}")
-print("  next tile start ", "(stamps of the LAST tile: its start relative to the previous tile is not recorded)")
-tot = max(s[:, 121, 0].max(), s[:, 120, 3].max()) - t0
-print("tile total", tot, "cycles")
+print("(chunk stamps: the last tile's, cycles from the earlier tile's start)")
