@@ -217,7 +217,8 @@ int mp_ray_setup(const float* uv, const float* intrinsics, const float* pose, in
                  float* far, void* stream);
 /* Ray / box test and ordered compaction (multiply.py:256-266): hit_index [<=R] ascending ray ids, *hit_count;
  * inv_index [R] = position in hit_index or -1.  group_size: rays of a convergence group without a hit get their
- * first ray as fallback (multiply.py:262-263 applied per chunk). scan_tmp: >= R+1 ints. */
+ * first ray as fallback (multiply.py:262-263 applied per chunk). scan_tmp: >= R + ceil(R / 1024) ints (the flags, then one
+ * partial sum per scan block of 1024 rays). */
 int mp_ray_cull(const float* dirs, const float* pose, const float* obb, int n_rays, int group_size, int* hit_index,
                 int* hit_count, int* inv_index, int* scan_tmp, void* stream);
 /* The same, refined for eval-mode rendering without changing a pixel: a ray that passes the box but stays further than the

@@ -182,3 +182,15 @@ MLP_BY_REGIME = {"geometric": MLP_GEOMETRIC, "trained": MLP_TRAINED, "near_range
 # stated; the bound pins what holds.
 MLP_PRECISE_RATIO = 5.0
 MLP_SPLIT_RATIO = 1.2
+# The geometry front end (rays, blend table, canonical warp on implicit samples, Jacobian rows) against the FLOAT64 reference
+# (oracle/geom_oracle64.py; tests/test_rays_gpu.py, tests/test_warp_samples_gpu.py): max |err| over the tests' rays / points.  All of it
+# is fp32 arithmetic on numbers of order 1 (x_c: |x - c| up to ~1.5 for the far outliers of the beta = 1 case).  Bounds <= 5x the
+# largest value measured on MI355X (first figure beside each); the second figure is the fp32 oracle's own distance to float64 on the
+# same inputs (tests/test_geom_oracle64_cpu.py asserts it below half of the bound): oracle and kernel round alike, neither is the
+# yardstick of the other here.
+GEOM64 = dict(
+    dirs=5e-7,            # 1.16e-7 (camera inside and outside the sphere, 1 ... 257 rays); oracle 1.2e-7
+    far=5e-6,             # 1.38e-6 (rays with |discriminant| >= 1e-2; radius 3: 8.1e-7); oracle 1.1e-6
+    blend_table=1e-6,     # 2.65e-7 (6 890 vertices; 1 / 255 / 257: 1.1e-7 / 2.3e-7 / 2.3e-7); oracle 2.0e-7
+    x_c=1.5e-6,           # 3.52e-7 (mode 0, 44 733 points; mode 1: 2.2e-7; shading beta 1 with the far branch: 3.4e-7); oracle 2.6e-7
+    jinv=1e-6)            # 2.14e-7 (2 167 flagged samples); oracle 2.0e-7 (the table's 3 x 3 blocks)
