@@ -523,6 +523,21 @@ int mp_mesh_signed_distance(const float* pts, int n, const float* face_verts, in
 int mp_mesh_ray_flags(const float* sdist, int n_rays, int n_s, float threshold, unsigned char* off, unsigned char* in,
                       void* stream);
 
+/* ---- face index for the same signed distance (csrc/mesh_index.hip): a tree of boxes over the faces in Hilbert-curve order, leaves of 8
+ * faces.  mp_mesh_index_signed_distance returns exactly what mp_mesh_signed_distance returns (same per-face arithmetic, faces
+ * skipped only when they can neither lower the minimum nor cross the ray, with slack for fp32 rounding), in sub-linear time per
+ * point.  Built on the device in three steps, no host synchronisation:
+ *   mp_mesh_index_bytes           : size of `index` for n_faces faces (a value, not a status; 16-byte aligned buffer)
+ *   mp_mesh_index_keys            : box of all vertices -> index header; keys [n_faces] ints = 30-bit Hilbert-curve key of each centroid
+ *   (caller)                      : order [n_faces] 64-bit ints = the permutation that sorts the keys (torch.sort indices)
+ *   mp_mesh_index_build           : faces gathered in that order, leaf boxes, inner levels bottom-up
+ *   mp_mesh_index_signed_distance : sdist [n]; visits (optional) [n][2] ints = boxes tested, faces evaluated by each point */
+int mp_mesh_index_bytes(int n_faces);
+int mp_mesh_index_keys(const float* face_verts, int n_faces, void* index, int* keys, void* stream);
+int mp_mesh_index_build(const float* face_verts, int n_faces, const long long* order, void* index, void* stream);
+int mp_mesh_index_signed_distance(const float* pts, int n, const void* index, int n_faces, float* sdist, int* visits,
+                                  void* stream);
+
 /* ---- general deformer queries (deformer.py:19-50, 72-88) for K <= 8 nearest vertices; the render / training path uses
  * the fused K = 1 kernels above.  weights [n][24] = sum_k conf_k skin_w[idx_k], conf = exp(-min(d^2,4)) normalised;
  * outlier (optional) = sqrt(min(d_0^2, 4)) > 0.1.  mp_skinning: x' = (sum_j w_j tfs_j) x, or its inverse. */

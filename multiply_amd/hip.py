@@ -121,7 +121,7 @@ def header_prototypes(path=HEADER_PATH):
 # Every entry point returns a status (0, or a hipError_t / negative argument-error code: the header's top comment) except these,
 # which return a value
 VALUE_RETURNING = ("mp_device_ok", "mp_sig_bytes_per_point", "mp_obb_hull_device_work_bytes", "mp_warp_bin_work_bytes",
-                   "mp_debug_hull_abandon", "mp_arch")
+                   "mp_debug_hull_abandon", "mp_arch", "mp_mesh_index_bytes")
 _DEBUG_SYNC = bool(int(os.environ.get("MP_DEBUG_SYNC", "0")))
 
 
@@ -782,8 +782,113 @@ def fit_loss(sdf, grad, normals, dist, weights, truncation=0.0, out=None):
     return terms, d_sdf, d_grad
 
 
-def mesh_signed_distance(pts, face_verts, out=None):
-    """exact signed distance (negative inside) of pts (n,3) to the closed mesh face_verts (F,3,3): mp_mesh_signed_distance"""
+# ------------------------------------------------------------------------------------------------ mesh signed distance
+# 'auto' | 'index' | 'brute': the face index (csrc/mesh_index.hip) or the brute-force kernel (csrc/mesh.hip); both return the same
+# bits.  MP_MESH_INDEX=0 makes brute force the default.  'auto' picks the index only where it was MEASURED to win
+# (profiles/mesh_index.txt): for a CLOSED SURFACE (every edge shared by exactly two faces) of at least MESH_INDEX_MIN_FACES
+# faces.  Both conditions matter: below that count brute force is faster, and on a face list that is no surface (the synthetic
+# SMPL tables' `f`: triangles between near neighbours of a sorted vertex list, overlapping at random) the boxes overlap
+# everywhere and the index loses (0.7 x at 13 776 faces).  A caller that cannot say whether the faces are closed gets brute force.
+# The count is the same for an index that is reused (training flags, the fit) and one built for a single query
+# (interpenetration_loss): the build is 65-150 us and query + build was measured ahead from the same size on.
+MESH_INDEX_MODES = ("auto", "index", "brute")
+MESH_INDEX_MODE = "brute" if os.environ.get("MP_MESH_INDEX", "1") == "0" else "auto"
+MESH_INDEX_MIN_FACES = 2048
+
+
+def mesh_index_mode(mode):
+    """validates a mesh_index_mode ('auto' | 'index' | 'brute'; None = the process default) and returns it"""
+    mode = MESH_INDEX_MODE if mode is None else mode
+    if mode not in MESH_INDEX_MODES:
+        raise ValueError(f"mesh_index_mode must be one of {MESH_INDEX_MODES}, got {mode!r}")
+    return mode
+
+
+_CLOSED = {}
+
+
+def faces_closed(faces):
+    """is the face list (F,3) (any leading 1) a closed surface?  smpl_init.mesh_is_closed on the host (one copy + one sort of the
+    edges), remembered per tensor (data_ptr, _version, shape; the entry keeps the tensor alive so that its address is not reused)"""
+    from .smpl_init import mesh_is_closed
+    if not torch.is_tensor(faces):
+        return mesh_is_closed(faces)
+    key = (faces.data_ptr(), faces._version, tuple(faces.shape), str(faces.device))
+    e = _CLOSED.get(key)
+    if e is None:
+        if len(_CLOSED) >= 64:
+            _CLOSED.clear()
+        e = _CLOSED[key] = (mesh_is_closed(faces), faces)
+    return e[0]
+
+
+def mesh_index_wanted(mode, n_faces, faces=None):
+    """does `mode` ask for the index on a mesh of n_faces faces?  faces: its (F,3) vertex ids, or True / False when the caller
+    knows whether they form a closed surface; 'auto' without that knowledge (None) means brute force"""
+    mode = mesh_index_mode(mode)
+    if mode != "auto":
+        return mode == "index"
+    if n_faces < MESH_INDEX_MIN_FACES or faces is None:
+        return False
+    if isinstance(faces, bool):
+        return faces
+    return faces.numel() == 3 * n_faces and faces_closed(faces)
+
+
+class MeshIndex:
+    """Box tree over the faces of a triangle mesh (F,3,3) for mp_mesh_index_signed_distance; built on the device without a host
+    synchronisation (torch sorts the curve keys, as plumbing).  The faces are copied into the index: the source tensor may change
+    or go away afterwards -- the index then still describes the mesh it was built from (see MeshIndexCache)."""
+
+    def __init__(self, face_verts):
+        fv = face_verts.detach().reshape(-1, 9).float().contiguous()
+        self.n_faces, dev = fv.shape[0], fv.device
+        if self.n_faces < 1:
+            raise ValueError("a mesh index needs at least one face")
+        L = lib()
+        self.buf = torch.empty(int(L.mp_mesh_index_bytes(self.n_faces)), dtype=torch.uint8, device=dev)
+        keys = torch.empty(self.n_faces, dtype=torch.int32, device=dev)
+        L.mp_mesh_index_keys(fv, self.n_faces, self.buf, keys, stream())
+        order = torch.sort(keys, stable=True).indices
+        L.mp_mesh_index_build(fv, self.n_faces, order, self.buf, stream())
+
+    def signed_distance(self, pts, out=None, visits=None):
+        """signed distance (n,) of pts (n,3), equal to mesh_signed_distance's; visits: optional (n,2) int32 = boxes tested, faces
+        evaluated per point"""
+        n = pts.shape[0]
+        sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
+        lib().mp_mesh_index_signed_distance(pts, n, self.buf, self.n_faces, sd, visits, stream())
+        return sd
+
+
+class MeshIndexCache:
+    """Per slot (a person): the MeshIndex of the slot's face tensor, or None where the mode asks for brute force; decided and
+    built again when the tensor is another tensor or was written in place, when its face list changes, or when the mode does.  The
+    key is the tensors' (data_ptr, _version, shape); the entry keeps them alive, so that the address of a replaced tensor cannot
+    come back with a new mesh behind the same key.  Under 'auto' a new mesh costs one host-side closedness check (faces_closed)."""
+
+    def __init__(self):
+        self.slots = {}
+
+    @staticmethod
+    def _id(t):
+        return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.device), t.dtype)
+
+    def get(self, slot, face_verts, faces=None, mode="index"):
+        key = (self._id(face_verts), self._id(faces), mesh_index_mode(mode))
+        e = self.slots.get(slot)
+        if e is None or e[0] != key:
+            use = mesh_index_wanted(mode, face_verts.numel() // 9, faces)
+            e = self.slots[slot] = (key, MeshIndex(face_verts) if use else None, face_verts, faces)
+        return e[1]
+
+
+def mesh_signed_distance(pts, face_verts, out=None, index=None):
+    """exact signed distance (negative inside) of pts (n,3) to the closed mesh face_verts (F,3,3): mp_mesh_signed_distance, or
+    through a MeshIndex of the same faces (same values)"""
+    if index is not None:
+        assert index.n_faces == face_verts.reshape(-1, 9).shape[0], "the index was built from another mesh"
+        return index.signed_distance(pts, out)
     n = pts.shape[0]
     sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
     lib().mp_mesh_signed_distance(pts, n, face_verts, face_verts.shape[0], sd, stream())

@@ -84,13 +84,15 @@ def _nearest(points, verts, chunk=2048):
     return torch.cat(out) if out else torch.zeros(0, dtype=torch.long, device=points.device)
 
 
-def interpenetration_loss(vertex_list, face_list, num_points=5120, draws=None):
+def interpenetration_loss(vertex_list, face_list, num_points=5120, draws=None, mesh_index_mode=None):
     """multiply_model.py:521-551: `num_points` random vertices of every mesh that lie INSIDE another person's mesh are
     pulled to that mesh's nearest vertex (summed squared distance), outliers further than 0.1 ignored.
-    vertex_list[p] (1,N,3), face_list[p] (1,F,3); draws[p] = the vertex ids to use instead of torch.randperm."""
+    vertex_list[p] (1,N,3), face_list[p] (1,F,3); draws[p] = the vertex ids to use instead of torch.randperm.
+    mesh_index_mode: 'auto' | 'index' | 'brute' (None = hip.MESH_INDEX_MODE); the posed meshes are new in every call, so an index
+    serves one query per pair of persons here.  'auto' (hip.mesh_index_wanted): a closed face list of hip.MESH_INDEX_MIN_FACES
+    faces or more -- closedness is checked on the host once per face tensor (hip.faces_closed)."""
     dev = vertex_list[0].device
     total = torch.zeros(1, device=dev)
-    L = hip.lib()
     for pid, vertex in enumerate(vertex_list):
         idx = (torch.randperm(vertex.shape[1])[:num_points] if draws is None else draws[pid]).to(dev)
         sample = torch.index_select(vertex, 1, idx)                                # (1,n,3)
@@ -99,8 +101,8 @@ def interpenetration_loss(vertex_list, face_list, num_points=5120, draws=None):
             if qid == pid:
                 continue
             fv = partner[0].detach()[face_list[qid].reshape(-1, 3).long()].float().contiguous()     # (F,3,3)
-            sd = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
-            L.mp_mesh_signed_distance(pts, pts.shape[0], fv, fv.shape[0], sd, hip.stream())
+            index = hip.MeshIndex(fv) if hip.mesh_index_wanted(mesh_index_mode, fv.shape[0], face_list[qid].reshape(-1, 3)) else None
+            sd = hip.mesh_signed_distance(pts, fv, index=index)
             inside = sd < 0
             pen = sample[0][inside]
             nn_pts = partner[0][_nearest(pen.detach(), partner[0].detach())]
@@ -143,7 +145,8 @@ def get_depth_order_loss(model, inputs, epoch, loss_opt=None, meshes=None, draws
     vs, fs, _ = posed_meshes(model, inputs, meshes=meshes)
     depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(vs, fs)]
     fade = 1 - min(DEPTH_LOSS_MILESTONE, epoch) / DEPTH_LOSS_MILESTONE
-    inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * interpenetration_loss(vs, fs, draws=draws)
+    inter = interpenetration_loss(vs, fs, draws=draws, mesh_index_mode=model.mesh_index_mode)
+    inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
     sil_w = loss_opt.get("silhouette_weight", 0.0)
     sil = torch.zeros((), device=depth[0].device)
     if sil_w != 0.0:                       # multiply_model.py:618-637, :656-668, :721 (the reference renders it even at weight 0)
@@ -229,7 +232,8 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
             so = server(scale[:, p], trans[:, p], pose[:, p], shape[:, p])
             verts.append((1 / scale[:, p].squeeze()) * deformed_mesh_vertices(model, meshes[p]["vertices"][None], so["smpl_tfs"], p))
         depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(verts, faces)]
-        inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * interpenetration_loss(verts, faces)
+        inter = interpenetration_loss(verts, faces, mesh_index_mode=model.mesh_index_mode)
+        inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
         order = depth_order_loss(depth, inputs["org_sam_mask"], epoch, loss_opt.get("depth_order_weight", 0.005))
         (inter.sum() + order + render.sum()).backward()
         opt.step()

@@ -106,6 +106,11 @@ class Multiply(nn.Module):
         self.sdf_bounding_sphere = 3.0
         self.threshold = 0.05
         self.shade_mode = hip.SHADE_MODE      # 'reverse' | 'forward' (csrc/mlp.hip: k_mlp_shade_rev | k_mlp_shade)
+        # in / off-surface flags (training, epochs < 250): 'auto' | 'index' | 'brute' -- the face index (csrc/mesh_index.hip) or brute
+        # force (csrc/mesh.hip), same values; 'auto' = the index for a closed surface of hip.MESH_INDEX_MIN_FACES faces or more, where it
+        # was measured to win (hip.mesh_index_wanted); MP_MESH_INDEX=0: brute; fit_smpl_init(model, ...) follows it too
+        self.mesh_index_mode = hip.MESH_INDEX_MODE
+        self.mesh_index_cache = hip.MeshIndexCache()       # one index per person, rebuilt when mesh_face_vertices_list[p] changes
         self.density = LaplaceDensity(**opt.density)
         self.bg_density = AbsDensity()
         self.ray_sampler = ErrorBoundSampler(self.sdf_bounding_sphere, inverse_sphere_bg=True, **opt.ray_sampler)
@@ -169,6 +174,14 @@ class Multiply(nn.Module):
         """{phase: (n_brackets, total ms)} of the events recorded since the last reset (synchronises)."""
         torch.cuda.synchronize()
         return {k: (len(v), sum(a.elapsed_time(b) for a, b in v)) for k, v in self.phase_events.items()}
+
+    @property
+    def mesh_index_mode(self):
+        return self._mesh_index_mode
+
+    @mesh_index_mode.setter
+    def mesh_index_mode(self, mode):
+        self._mesh_index_mode = hip.mesh_index_mode(mode)
 
     def train(self, mode=True):
         """nn.Module.train, and every switch of mode drops the packed-weight caches (hip.invalidate_packed: an optimizer may have

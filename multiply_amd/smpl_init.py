@@ -110,28 +110,33 @@ def _mesh_tensors(verts, faces, device):
 class MeshTarget:
     """device-side tables of the mesh a fit samples: face vertices, areas, normals, the area CDF"""
 
-    def __init__(self, verts, faces, device="cuda"):
+    def __init__(self, verts, faces, device="cuda", mesh_index_mode=None):
         self.verts, self.faces = _mesh_tensors(verts, faces, device)
         self.face_verts = self.verts[self.faces].contiguous()                 # (F,3,3), the layout of mesh_face_vertices_list
         self.area, self.normal, self.cdf = hip.fit_area_cdf(self.face_verts)
         self.n_faces = self.faces.shape[0]
+        # the distances of every step's volume points go through a face index ('auto': a closed mesh of hip.MESH_INDEX_MIN_FACES
+        # faces or more; the fit itself refuses a mesh that is not closed)
+        self.index = hip.MeshIndex(self.face_verts) if hip.mesh_index_wanted(mesh_index_mode, self.n_faces, self.faces) else None
 
 
 def fit_step_points(target, cfg, box, draws, out=None):
     """mp_fit_sample + mp_mesh_signed_distance: points (n_s + n_v,3), surface normals, face ids, exact distances of the volume points"""
     u_surf, z_near, u_box = draws
     pts, nrm, fid = hip.fit_sample(target.face_verts, target.normal, target.cdf, u_surf, z_near, cfg.sigma_local, u_box, box, out)
-    dist = hip.mesh_signed_distance(pts[cfg.n_surface:], target.face_verts)
+    dist = hip.mesh_signed_distance(pts[cfg.n_surface:], target.face_verts, index=target.index)
     return pts, nrm, fid, dist
 
 
-def fit_implicit_net(net, verts, faces, cond=None, cfg=None, log_every=0):
+def fit_implicit_net(net, verts, faces, cond=None, cfg=None, log_every=0, mesh_index_mode=None):
     """Fits `net` (a foreground ImplicitNet on the device) to the CLOSED triangle mesh (verts (V,3), faces (F,3): device tensors or
     numpy, canonical space) and returns a FitRecord.  The parameters are updated in place.
 
     cond: the pose conditioning (69,) the network sees during the fit; None = the all-zero vector.  With zeros the conditioning
     columns of layer 0 multiply zeros: they receive NO gradient and keep their initial values (the geometric initialisation
     sets them to zero, so the fitted network starts pose-independent, like a network fitted without conditioning).
+
+    mesh_index_mode: 'auto' | 'index' | 'brute' for the exact distances (None = hip.MESH_INDEX_MODE; same values either way).
 
     log_every > 0: the five terms are read back (a host synchronisation) at step 1, every log_every steps and at the last."""
     from . import train as T
@@ -143,7 +148,7 @@ def fit_implicit_net(net, verts, faces, cond=None, cfg=None, log_every=0):
     hip.require_device()
     dev = next(net.parameters()).device
     require_closed(faces)
-    target = MeshTarget(verts, faces, dev)
+    target = MeshTarget(verts, faces, dev, mesh_index_mode)
     box = fit_box(cfg, target.verts, dev)
     cond = torch.zeros(69, dtype=torch.float32, device=dev) if cond is None else cond.detach().to(dev).float().reshape(-1).contiguous()
     gen = torch.Generator(device=dev).manual_seed(int(cfg.seed))
@@ -188,13 +193,14 @@ def save_smpl_init(net, path):
     return path
 
 
-def heldout_error(net, verts, faces, cond=None, n_surface=4096, n_box=4096, seed=12345, box=None, box_inflate=0.2):
+def heldout_error(net, verts, faces, cond=None, n_surface=4096, n_box=4096, seed=12345, box=None, box_inflate=0.2,
+                  mesh_index_mode=None):
     """mean / max |sdf - exact signed distance| of the network on held-out points: n_surface area-uniform surface points (exact
     distance 0) and n_box points uniform in the fit's box.  The network runs through the near-fp32 training sweep (forward only).
     Returns {"surface_mean", "surface_max", "box_mean", "box_max"} (host floats; synchronises)."""
     from . import train as T
     dev = next(net.parameters()).device
-    target = MeshTarget(verts, faces, dev)
+    target = MeshTarget(verts, faces, dev, mesh_index_mode)
     cfg = FitConfig(n_surface=n_surface, n_volume=n_box, near_fraction=0.0, box=box, box_inflate=box_inflate)
     gen = torch.Generator(device=dev).manual_seed(int(seed))
     pts, _, _, dist = fit_step_points(target, cfg, fit_box(cfg, target.verts, dev), make_draws(cfg, gen, dev))
@@ -211,9 +217,12 @@ def fit_smpl_init(model_or_opt, path, person=0, mesh=None, cfg=None, log_every=0
     model_or_opt: a Multiply model (its network is fitted in place) or a model config (a fresh ImplicitNet is built from
     opt.implicit_network on the device; `mesh` is then required).  mesh = (verts, faces), default the model's canonical mesh
     (mesh_v_cano_list[person], mesh_f_cano_list[person]): with real SMPL tables the canonical SMPL surface.  A mesh that is not
-    closed is refused (the synthetic tables' `f` is a list of near-neighbour triangles, not a surface)."""
+    closed is refused (the synthetic tables' `f` is a list of near-neighbour triangles, not a surface).  A model's
+    mesh_index_mode applies to the fit's exact distances too."""
+    mode = None
     if hasattr(model_or_opt, "foreground_implicit_network_list"):
         model = model_or_opt
+        mode = model.mesh_index_mode
         net = model.foreground_implicit_network_list[person]
         if mesh is None:
             mesh = (model.mesh_v_cano_list[person].reshape(-1, 3), model.mesh_f_cano_list[person])
@@ -224,6 +233,6 @@ def fit_smpl_init(model_or_opt, path, person=0, mesh=None, cfg=None, log_every=0
         net = ImplicitNet(model_or_opt.implicit_network).to("cuda")
     verts, faces = mesh
     require_closed(faces, "the mesh to fit")
-    rec = fit_implicit_net(net, verts, faces, cond=None, cfg=cfg, log_every=log_every)
+    rec = fit_implicit_net(net, verts, faces, cond=None, cfg=cfg, log_every=log_every, mesh_index_mode=mode)
     save_smpl_init(net, path)
     return net, rec

@@ -1109,9 +1109,16 @@ class TrainGraph:
                            dfm.verts_c_flat, st)
         flags = None
         if self.surface_flags:        # multiply.py:311-315: in / off-surface rays w.r.t. the current canonical mesh
-            fv = m.mesh_face_vertices_list[p].detach().reshape(-1, 9).to(dev).float().contiguous()
+            src = m.mesh_face_vertices_list[p]
             sd = torch.empty(npts, **f32)
-            L.mp_mesh_signed_distance(X, npts, fv, fv.shape[0], sd, st)
+            index = None
+            if src.device == X.device:       # 'auto': the index for a closed surface of hip.MESH_INDEX_MIN_FACES faces or more
+                index = m.mesh_index_cache.get(p, src, m.mesh_f_cano_list[p], m.mesh_index_mode)
+            if index is not None:
+                index.signed_distance(X[:npts], out=sd)                               # same values as the brute-force kernel
+            else:
+                fv = src.detach().reshape(-1, 9).to(dev).float().contiguous()
+                L.mp_mesh_signed_distance(X, npts, fv, fv.shape[0], sd, st)
             off_p = torch.empty(Rp, dtype=torch.uint8, device=dev); in_p = torch.empty(Rp, dtype=torch.uint8, device=dev)
             L.mp_mesh_ray_flags(sd, Rp, S, m.threshold, off_p, in_p, st)
             flags = (off_p.bool(), in_p.bool(), sd)
