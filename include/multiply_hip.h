@@ -474,6 +474,17 @@ int mp_tf_sdf_fwd(const void* wpack, const float* bias_all, const float* w8, flo
                   void* stream);
 int mp_tf_sdf_bwd(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf, float* dw8,
                   float* db8, void* stream);
+/* mp_tf_sdf_dx: the adjoint of the input POINTS (pose optimisation) from the stash mp_tf_sdf_bwd has left in `arena`:
+ *   dx [P][3] += J_PE(x)^T ( dZ(0) W0[:, 0:39] + (1/sqrt 2) dZ(4) W4[:, 217:256] )
+ * W0 / W4 = the effective fp32 weights of layers 0 and 4, row-major [256][ldw0 >= 39] / [256][ldw4 >= 256] (the Fourier columns
+ * come first in layer 0 and last in layer 4, where the skip connection re-injects them); x [P][3] the points of the forward
+ * call.  ACCUMULATES: the caller has put the gradient sweep's second-order share there (mp_tr_pe_grad_bwd's dx).  Exact fp32
+ * (one rounding per product, fp32 accumulation in a fixed order: bit-identical from launch to launch), no atomics; the 39
+ * intermediate values never reach memory and the pad rows of the stash are never read.  Reads the stash only: its order
+ * against the weight-gradient contractions is free.  P <= 0: nothing to do, returns 0; ldw0 < 39 or ldw4 < 256 (a row too
+ * short to hold the Fourier columns): returns -1 without a launch. */
+int mp_tf_sdf_dx(const float* arena, int P, const float* W0, int ldw0, const float* W4, int ldw4, const float* x,
+                 float* dx, void* stream);
 /* mp_tf_sdf_val: the VALUE sweep alone, sdf column only, nothing stashed -- mp_mlp_sdf's interface (worklist of point ids or NULL,
  * device-side count or NULL, sdf_out written at the point ids) at the training path's arithmetic: split-bfloat16 products, fp32
  * accumulation, fp32 softplus, Fourier features from sinf / cosf.  The sampler's queries with `Multiply.sampler_sdf_mode = 'bf16x3'`

@@ -1,4 +1,4 @@
-// Small device helpers shared by the kernels: density, the wave / workgroup reductions, the per-device LDS attribute.
+// Small device helpers shared by the kernels: density, the wave / workgroup reductions and the wave-level LDS fence, the per-device LDS attribute.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,12 @@ __device__ __forceinline__ float wmin(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
     return v;
 }
+// orders this wave's LDS traffic: writes by any lane before, reads by any lane after (LDS the wave shares with no other wave)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // block-wide sum for blockDim.x = 256 (4 waves)
 __device__ __forceinline__ float block_sum256(float v, float* sh) {
     v = wsum(v);
@@ -51,6 +57,24 @@ __device__ __forceinline__ float wave_excl_scan(float v, float& total) {
     }
     total = __shfl(incl, 63);
     return incl - v;
+}
+
+// Adjoint of one point's Fourier features (embedders.py layout: x, then per octave k  sin(2^k x), cos(2^k x), D columns each)
+// w.r.t. component a of the point: dv(c) = adjoint of column c of the value row; fwd: dt(c) = adjoint of column c of
+// component a's tangent row (1, f cos(f x_a), -f sin(f x_a)).  THE arithmetic of k_pe_bwd (train.hip) and of k_tf_sdf_dx
+// (tfuse.hip): both paths to the points' adjoint evaluate the same expression in the same order.
+template <int D, class DV, class DT>
+__device__ __forceinline__ float pe_adjoint(float xa, int a, int L, bool fwd, DV dv, DT dt) {
+    float acc = dv(a);
+    for (int k = 0; k < L; ++k) {
+        const float f = (float)(1 << k);
+        float sn, cs;
+        sincosf(xa * f, &sn, &cs);
+        const int cs_ = D + 2 * D * k + a, cc_ = cs_ + D;
+        acc += f * (cs * dv(cs_) - sn * dv(cc_));
+        if (fwd) acc -= f * f * (sn * dt(cs_) + cs * dt(cc_));
+    }
+    return acc;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute: a `static int once = hipFuncSetAttribute(...)` covers

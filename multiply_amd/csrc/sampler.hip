@@ -12,13 +12,6 @@ namespace {
 
 constexpr int WAVES = 4;
 
-// orders this wave's LDS traffic: writes by any lane before, reads by any lane after
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The sampler's exponentials and densities in the hardware's own precision: v_exp_f32 of x * log2(e) (relative error about
 // |x| * 6e-8, i.e. < 6e-6 for the arguments that matter) and a multiplication by 1 / beta instead of three IEEE
 // divisions.  The sampler decides where to put samples from f16 SDF queries (its depths are compared with the oracle at

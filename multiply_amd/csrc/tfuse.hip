@@ -917,6 +917,94 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_bwd(TfArgs a) {
     if (threadIdx.x == 256) atomicAdd(a.db8, cx.redf[256]);
 }
 
+// ================================================================================================================ points' adjoint
+// d x_c of the SDF net (pose optimisation) from the stash k_tf_sdf_bwd leaves behind; the two big kernels are untouched.
+// The Fourier features enter the value sweep twice, through layer 0 and through the skip connection into layer 4, so
+//     dIN [39] = dZ_0 W_0[:, 0:39] + (1/sqrt 2) dZ_4 W_4[:, 217:256]              (_LayerwiseImplicit._value_adjoint, train.py)
+//     dx      += J_PE(x)^T dIN                                                      (mp::pe_adjoint: k_pe_bwd's arithmetic)
+// (the gradient sweep's second-order share of dx is mp_tr_pe_grad_bwd's, already in dx).  Exact fp32: v_mfma_f32_16x16x4_f32
+// rounds every product once and accumulates in fp32 in a fixed K order, so the result is the same from launch to launch.
+// A workgroup stages the two weight slices in LDS once, as [k][48] (39 outputs = 3 row blocks of 16, the rest zeros), and
+// walks over tiles of 128 points; a wave owns 16 points (the MFMA's columns).  Lane (g, j) loads the 16 bytes at column
+// 16 s + 4 g of point j's row, s = 0..15: four lanes cover 64 contiguous bytes of a row, and element t of the vector is the
+// B operand of K step (s, t), whose four K slots are therefore k = 16 s + 4 g + t.  The LDS rows are permuted to match
+// (dx_krow), so the A operand of a step is four CONSECUTIVE rows: bank-conflict free at a row stride of 48 floats.
+// Rows >= P are never read (the row index is clamped to P - 1): neither the pad row nor another tensor reaches a result.
+constexpr int DX_LD = 48, DX_T_LD = 49;         // LDS row strides: weight slices [k][48]; a wave's dIN tile [16 points][49]
+constexpr int DX_W_FLOATS = 2 * HID * DX_LD;
+constexpr int DX_LDS_BYTES = (DX_W_FLOATS + TF_WAVES * 16 * DX_T_LD) * 4;
+constexpr int DX_MAX_GRID = 256;
+
+__device__ __forceinline__ int dx_krow(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
+
+__device__ __forceinline__ void dx_load(f32x4 (&b)[16], const float* __restrict__ row) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) b[s] = *(const f32x4*)(row + 16 * s);
+}
+
+// acc[rb] (outputs 16 rb + 4 g + r of point j) += the 256-term contraction of one stash row with one weight slice
+__device__ __forceinline__ void dx_mma(const float* wa, int g, const f32x4 (&b)[16], f32x4 (&acc)[3]) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float* wr = wa + (16 * s + 4 * t + g) * DX_LD;
+#pragma unroll
+            for (int rb = 0; rb < 3; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * rb], b[s][t], acc[rb], 0, 0, 0);
+        }
+    }
+}
+
+__global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_dx(const float* __restrict__ arena, int P, const float* __restrict__ W0,
+                                                          int ldw0, const float* __restrict__ W4, int ldw4,
+                                                          const float* __restrict__ x, float* __restrict__ dx) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* wl = (float*)smem;                                      // [2][256 (dx_krow order)][48]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
+    float* tl = wl + DX_W_FLOATS + wave * 16 * DX_T_LD;            // this wave's dIN tile: no other wave touches it
+    const size_t R1 = (size_t)(P + 1) * HID;
+    const int n_tiles = (P + TF_PTS - 1) / TF_PTS;
+    auto row_of = [&](int tile) {
+        const int p = min(tile * TF_PTS + 16 * wave + j, P - 1);
+        return arena + off_dZ(R1, 0) + (size_t)p * HID + 4 * g;
+    };
+    f32x4 b0[16], b4[16];
+    int tile = blockIdx.x;                                         // (blockIdx.x < n_tiles: the grid is at most n_tiles)
+    dx_load(b0, row_of(tile));                                     // the first tile's dZ_0 rows fly while the weights are staged
+    for (int e = threadIdx.x; e < DX_W_FLOATS; e += TF_THREADS) {
+        const int o = e % DX_LD, k = (e / DX_LD) % HID, t = e / (DX_LD * HID);
+        float v = 0.0f;
+        if (o < E_PE) v = t == 0 ? W0[(size_t)k * ldw0 + o] : W4[(size_t)k * ldw4 + OUT3 + o];
+        wl[(t * HID + dx_krow(k)) * DX_LD + o] = v;
+    }
+    __syncthreads();
+    const float* wa = wl + j;                                      // A operand: output row 16 rb + j
+    for (; tile < n_tiles; tile += gridDim.x) {
+        dx_load(b4, row_of(tile) + (off_dZ(R1, 4) - off_dZ(R1, 0)));
+        f32x4 a0[3], a4[3];
+#pragma unroll
+        for (int rb = 0; rb < 3; ++rb) a0[rb] = a4[rb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dx_mma(wa, g, b0, a0);
+        if (tile + (int)gridDim.x < n_tiles) dx_load(b0, row_of(tile + gridDim.x));      // the next tile's dZ_0 rows, in flight
+        dx_mma(wa + HID * DX_LD, g, b4, a4);
+#pragma unroll
+        for (int rb = 0; rb < 3; ++rb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tl[j * DX_T_LD + 16 * rb + 4 * g + r] = fmaf(R2, a4[rb][r], a0[rb][r]);
+        }
+        mp::wave_sync();
+        if (lane < 48) {                                           // lane = 3 (point of the wave) + component
+            const int pj = lane / 3, a = lane - 3 * pj, p = tile * TF_PTS + 16 * wave + pj;
+            if (p < P) {
+                const float* dv = tl + pj * DX_T_LD;
+                dx[3 * (size_t)p + a] += mp::pe_adjoint<3>(x[3 * (size_t)p + a], a, 6, false, [&](int c) { return dv[c]; },
+                                                           [](int) { return 0.0f; });
+            }
+        }
+        mp::wave_sync();                                           // the next tile overwrites tl
+    }
+}
+
 // ================================================================================================================ background net
 // The NeRF++ background ImplicitNet (networks.py:126-208 with confs/model: d_in 4, multires 10 -> 84 Fourier features, frame code
 // (32) hoisted into layer 0's bias, 8 x 256 softplus, skip connection at layer 4 = [172 | 84] / sqrt 2, 257 outputs, no weight
@@ -1297,6 +1385,17 @@ extern "C" int mp_tf_sdf_bwd(const void* wpack, const float* w8, float* arena, i
     MP_LDS_ATTR(k_tf_sdf_bwd, LDS_BYTES);
     TfArgs a{(const char*)wpack, nullptr, w8, arena, nullptr, nullptr, dfeat, dsdf, dw8, db8, P};
     hipLaunchKernelGGL(k_tf_sdf_bwd, dim3((P + TF_PTS - 1) / TF_PTS), dim3(TF_THREADS), LDS_BYTES, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_tf_sdf_dx(const float* arena, int P, const float* W0, int ldw0, const float* W4, int ldw4, const float* x,
+                            float* dx, void* stream) {
+    if (P <= 0) return 0;
+    if (ldw0 < E_PE || ldw4 < HID) return -1;
+    MP_LDS_ATTR(k_tf_sdf_dx, DX_LDS_BYTES);
+    const int tiles = (P + TF_PTS - 1) / TF_PTS;
+    hipLaunchKernelGGL(k_tf_sdf_dx, dim3(tiles < DX_MAX_GRID ? tiles : DX_MAX_GRID), dim3(TF_THREADS), DX_LDS_BYTES,
+                       (hipStream_t)stream, arena, P, W0, ldw0, W4, ldw4, x, dx);
     return (int)hipGetLastError();
 }
 

@@ -587,16 +587,7 @@ __global__ void k_pe_bwd(const float* __restrict__ x, int P, int L, int fwd, con
     for (int a = 0; a < D; ++a) {
         const float xa = x[(size_t)i * D + a];
         const float* dt = fwd ? dIN + (size_t)((a + 1) * P + i) * ld : nullptr;
-        float acc = dv[a];
-        for (int k = 0; k < L; ++k) {
-            const float f = (float)(1 << k);
-            float sn, cs;
-            sincosf(xa * f, &sn, &cs);
-            const int cs_ = D + 2 * D * k + a, cc_ = cs_ + D;
-            acc += f * (cs * dv[cs_] - sn * dv[cc_]);
-            if (fwd) acc -= f * f * (sn * dt[cs_] + cs * dt[cc_]);
-        }
-        dx[(size_t)i * D + a] += acc;
+        dx[(size_t)i * D + a] += mp::pe_adjoint<D>(xa, a, L, fwd != 0, [&](int c) { return dv[c]; }, [&](int c) { return dt[c]; });
     }
 }
 

@@ -324,7 +324,7 @@ class ImplicitTrainRev(_LayerwiseImplicit):
     = what torch autograd does for the reference (multiply.py:643-659 with create_graph=True): 6 GEMMs per layer over P
     rows, where the forward-mode class above spends 3 GEMMs over 4P rows.  Same results, same parameter gradients.
     The value sweep and its adjoint are _LayerwiseImplicit's; this class adds the gradient sweep and that sweep's adjoint.
-    The only evaluator that yields the adjoint of the input points (pose optimisation)."""
+    Yields the adjoint of the input points (pose optimisation); the default evaluator for it (SDF_POSE_GRAD_MODE)."""
 
     def __init__(self, net, x, cond_vec, lins=None):
         L = hip.lib()
@@ -738,8 +738,9 @@ class ImplicitTrainFused(_FusedImplicit):
     """ImplicitTrainRev's arithmetic (value sweep + gradient sweep, and the adjoint of both) on the LAYER-FUSED kernels of
     csrc/tfuse.hip: two launches instead of ~90 per person -- mp_tf_sdf_fwd (both forward sweeps) and mp_tf_sdf_bwd (the adjoint
     w.r.t. the activations) -- plus one weight-gradient contraction per layer over [dZ_l; V_l]^T [X_l; dT_l] (K = 2 P rows).
-    The adjoint of the input points (pose optimisation) is not produced here: sdf_evaluator takes ImplicitTrainRev when it is
-    needed."""
+    backward(want_dx=True) also yields the adjoint of the input points (pose optimisation): one more launch, mp_tf_sdf_dx,
+    which contracts the dZ_0 / dZ_4 stashes with the Fourier columns of W_0 / W_4; sdf_evaluator takes this class under
+    pose_grad when SDF_POSE_GRAD_MODE is 'fused' (the default there is still ImplicitTrainRev)."""
 
     def __init__(self, net, x, cond_vec, lins=None, p_cap=None, cap_bytes=6 << 30):
         """p_cap: the largest P this caller can ever pass (all rays hit the body): the stash is then sized for it, i.e. the SAME
@@ -757,16 +758,19 @@ class ImplicitTrainFused(_FusedImplicit):
         L.mp_tr_pe_grad_fwd(x, P, net.multires, off(self.arena, self.o_G), E, self.grad, st)
 
     def backward(self, dfeat, dsdf, dgrad, want_dx=False, tn_groups=None):
-        assert not want_dx, "the fused SDF kernels do not produce the adjoint of the input points"
         assert dfeat.shape[1] == 256
         L, st = hip.lib(), hip.stream()
         net, P, E, fs, A = self.net, self.P, self.E, self.fs, self.arena
         dG = off(A, self.o_dG)
-        L.mp_tr_pe_grad_bwd(self.x, P, net.multires, dgrad, off(A, self.o_G), E, dG, E, None, st)
+        # want_dx: the gradient sweep's second-order share of d x_c first, the value sweep's (mp_tf_sdf_dx) added below
+        self.dx = torch.zeros(P, 3, dtype=F32, device=self.x.device) if want_dx else None
+        L.mp_tr_pe_grad_bwd(self.x, P, net.multires, dgrad, off(A, self.o_G), E, dG, E, self.dx, st)
         lw8 = self.lins[8]                              # the sdf row's gradient goes straight into row 0 of dW_8 / db_8
         L.mp_tf_sdf_bwd(fs.wpack, self.w8, A, P, dfeat, dsdf, lw8.dW, lw8.db, st)
         L.mp_tr_copy_cols(dG, E, 0, self._at(self.t_dT, 4), 256, 256 - E, P, E, 1.0 / math.sqrt(2.0), 0, st)
-        self.dx = None
+        if want_dx:                                     # d x_c += J_PE^T (dZ_0 W_0[:, :39] + dZ_4 W_4[:, 217:] / sqrt 2)
+            lw0, lw4 = self.lins[0], self.lins[4]
+            L.mp_tf_sdf_dx(A, P, lw0.W, lw0.in_dim, lw4.W, lw4.in_dim, self.x, self.dx, st)
         return self._weight_grads(dfeat, tn_groups, gradient_sweep=True)
 
 
@@ -936,6 +940,9 @@ ARENA_BUDGET_BYTES = int(os.environ.get("MP_TRAIN_ARENA_GB", "24")) << 30   # fi
 SDF_TRAIN_MODE = os.environ.get("MP_SDF_TRAIN_MODE", "fused")
 # background ImplicitNet: 'fused' (ImplicitTrainFusedBG, default) | 'layerwise' (ImplicitTrain: the cross-check)
 BG_TRAIN_MODE = os.environ.get("MP_BG_TRAIN_MODE", "fused")
+# the SDF evaluator while the body-model inputs are optimised (pose_grad): 'layerwise' (ImplicitTrainRev, default) | 'fused'
+# (ImplicitTrainFused + mp_tf_sdf_dx, where SDF_TRAIN_MODE, the precision and the network's shape allow the fused kernels)
+SDF_POSE_GRAD_MODE = os.environ.get("MP_SDF_POSE_GRAD_MODE", "layerwise")
 
 
 ZERO_POSE_SAMPLES = 2000          # multiply.py:363
@@ -1008,10 +1015,14 @@ def make_draws(model, cx, gen=None):
 
 
 def sdf_evaluator(net, x, cond_vec, lins, pose_grad, p_cap, cap_bytes):
-    """THE choice of the foreground SDF evaluator (SDF_TRAIN_MODE, TRAIN_PRECISION, pose_grad, the network's shape)"""
+    """THE choice of the foreground SDF evaluator (SDF_TRAIN_MODE, TRAIN_PRECISION, the network's shape; under pose_grad also
+    SDF_POSE_GRAD_MODE: the fused kernels yield d x_c through mp_tf_sdf_dx only when it is 'fused')"""
+    if SDF_POSE_GRAD_MODE not in ("layerwise", "fused"):
+        raise ValueError(f"MP_SDF_POSE_GRAD_MODE = {SDF_POSE_GRAD_MODE!r}: 'layerwise' or 'fused'")
     mode = SDF_TRAIN_MODE
-    if mode == "fused" and (pose_grad or TRAIN_PRECISION != "bf16x3" or not fused_sdf_supported(net)):
-        mode = "reverse"      # the fused kernels: split-bf16 arithmetic, the shipped network shape, no d x_c
+    if mode == "fused" and ((pose_grad and SDF_POSE_GRAD_MODE != "fused") or TRAIN_PRECISION != "bf16x3"
+                            or not fused_sdf_supported(net)):
+        mode = "reverse"      # the fused kernels: split-bf16 arithmetic, the shipped network shape
     if mode == "fused":
         return ImplicitTrainFused(net, x, cond_vec, lins=lins, p_cap=p_cap, cap_bytes=cap_bytes)
     if mode == "forward":

@@ -1,19 +1,42 @@
 #!/usr/bin/env python
 """Training iterations only (bench.py's train_iter leg): ms/iter, GPU phase times; run it under
 `rocprofv3 --kernel-trace` + tools/rocpd_summary.py for the per-kernel table of ONE iteration's work.
-    python tools/train_bench.py [steps] [warmup] [--epoch E] [--mesh-index auto|index|brute]
+    python tools/train_bench.py [steps] [warmup] [--epoch E] [--mesh-index auto|index|brute] [--pose-grad]
 --epoch E: every forward sees current_epoch = E instead of bench.py's 301.  Below 250 the in / off-surface flags are on; as the
 trainer has refreshed the canonical meshes by then (every 20 epochs), they are extracted once before the loop.
---mesh-index: model.mesh_index_mode (the flags' signed distance through the face index or by brute force)."""
+--mesh-index: model.mesh_index_mode (the flags' signed distance through the face index or by brute force).
+--pose-grad: smpl_pose / smpl_trans / smpl_shape require grad (the reference optimises them in every step), and the iteration is
+timed once per MP_SDF_POSE_GRAD_MODE ('layerwise', 'fused'), each in a fresh child process of this one, back to back on the same
+device; every line names the SDF evaluator class in use.  As in the trainer, the previous frame's pose enters the temporal term as
+a constant and the three inputs' gradients are cleared before every forward."""
 import json
 import os
+import subprocess
 import sys
+
+if "--pose-grad" in sys.argv[1:]:            # the parent: starts one child per mode and never touches the device itself
+    rest = [a for a in sys.argv[1:] if a != "--pose-grad"]
+    res = {}
+    for mode in ("layerwise", "fused"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + rest + ["--pose-grad-child"], stdout=subprocess.PIPE, text=True,
+                           env=dict(os.environ, MP_SDF_POSE_GRAD_MODE=mode))
+        sys.stdout.write(r.stdout)
+        if r.returncode != 0:
+            sys.exit(f"the {mode!r} run failed with status {r.returncode}")
+        res[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    lw, fu = res["layerwise"]["ms_per_iter"], res["fused"]["ms_per_iter"]
+    print(f"pose-optimising iteration: layerwise {lw:.3f} ms ({res['layerwise']['sdf_evaluator']}), fused {fu:.3f} ms "
+          f"({res['fused']['sdf_evaluator']}): {lw - fu:+.3f} ms, x{lw / fu:.3f}")
+    sys.exit(0)
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.argv, args = sys.argv[:1], sys.argv[1:]
 opts = {}
+POSE_GRAD = "--pose-grad-child" in args
+if POSE_GRAD:
+    args.remove("--pose-grad-child")
 for flag in ("--epoch", "--mesh-index"):
     if flag in args:
         i = args.index(flag)
@@ -26,6 +49,18 @@ warm = int(args[1]) if len(args) > 1 else 3
 model, inp, tables, sc = bench.build_model(128, seed=0)
 model.convergence_group = 512
 gin = bench.to_dev(inp)
+if POSE_GRAD:
+    BODY = ("smpl_pose", "smpl_trans", "smpl_shape")
+    for k in BODY:
+        gin[k] = gin[k].detach().clone().requires_grad_(True)
+
+    def _as_the_trainer(mod, a):
+        """the trainer's optimiser clears the body parameters' gradients every step, and the previous frame's pose is a constant
+        (bench.train_iterations derives it from the tensor that now requires grad: the temporal term would cancel)"""
+        for k in BODY:
+            gin[k].grad = None
+        return (dict(a[0], smpl_pose_last=a[0]["smpl_pose_last"].detach()),) + tuple(a[1:])
+    model.register_forward_pre_hook(_as_the_trainer)
 if "--mesh-index" in opts:
     model.mesh_index_mode = opts["--mesh-index"]
 EPOCH = int(opts.get("--epoch", 301))
@@ -42,8 +77,18 @@ def barrier():
 
 
 dt, ph, loss, stats, host_ms = bench.train_iterations(model, gin, steps, warm, False, barrier, seed=0, rays=512)
-print(json.dumps({"current_epoch": EPOCH, "mesh_index_mode": model.mesh_index_mode, "ms_per_iter": 1e3 * dt / steps, "host_ms_per_iter": host_ms, "gpu_ms": {"forward+loss": ph[0], "backward": ph[1], "allreduce": ph[2],
+extra = {}
+if POSE_GRAD:
+    from multiply_amd import train as T
+    graph = model._last_train
+    assert graph.pose_grad
+    extra = {"pose_grad": True, "sdf_pose_grad_mode": T.SDF_POSE_GRAD_MODE,
+             "sdf_evaluator": "/".join(sorted({type(f["it"]).__name__ for f in graph.fg.values()}))}
+print(json.dumps({**extra, "current_epoch": EPOCH, "mesh_index_mode": model.mesh_index_mode, "ms_per_iter": 1e3 * dt / steps, "host_ms_per_iter": host_ms, "gpu_ms": {"forward+loss": ph[0], "backward": ph[1], "allreduce": ph[2],
                                                                "adam": ph[3]}, "hit_rays": stats["n_hit"], "loss": loss}))
+
+if POSE_GRAD:
+    sys.exit(0)
 
 # ---- host-side view: how long does the HOST need to enqueue each part (it runs ahead of the GPU unless something syncs)?
 import time
