@@ -142,7 +142,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_sdf(const NetDesc net, const
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * in_stride(KS_IN);
     load_bias(net, bias, bias_lds);
     const ChunkMasks cm = chunk_masks(net);
-    const bool wraps = ring_stream_path<HID_SOFTPLUS>() && ring_can_wrap(net);
+    const bool wraps = ring_can_wrap(net);
     RingStream rs = {0, false};
     TileInputs<L::TILE> in(xc, worklist, 0, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
     for (int t = blockIdx.x; t * L::TILE < count; t += gridDim.x) {
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_sdf_x2(const NetDesc net, co
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * STR;
     load_bias(net, bias, bias_lds);
     const ChunkMasks cm = chunk_masks(net);
-    const bool wraps = ring_stream_path<HID_SOFTPLUS_X2>() && ring_can_wrap(net);
+    const bool wraps = ring_can_wrap(net);
     RingStream rs = {0, false};
     for (int t = blockIdx.x; t * TILE < count; t += gridDim.x) {
         const bool more = wraps && (long long)(t + gridDim.x) * TILE < count;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, c
     load_bias(net, bias, bias_lds);
     constexpr int SIG_LAYER = KS_REG * SIG_CHUNK_BYTES;   // one wave's sigmoids of one layer: 8 (UNORM8) or 16 KiB
     const ChunkMasks cm = chunk_masks(net);
-    const bool wraps = ring_stream_path<HID_SOFTPLUS_SAVE>() && ring_can_wrap(net);
+    const bool wraps = ring_can_wrap(net);
     RingStream rs = {0, false};
     TileInputs<L::TILE> in(xc, worklist, offset, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
     for (int t = blockIdx.x; offset + t * L::TILE < count; t += gridDim.x) {
@@ -425,11 +425,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, c
         zero_b<NB>(Bcur);
         stream_prologue_wait(rs);
         MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 2);
-        #ifdef MP_EXP_SIGCACHED   // ablation: every tile uses the first workgroup-slots of the buffer (cache resident)
-        const SigIO sio = {sigbuf + ((size_t)(blockIdx.x) * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
-#else
         const SigIO sio = {sigbuf + ((size_t)t * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
-#endif
         run_net<NB, false, KS_IN, HID_SOFTPLUS_SAVE, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
                                                             sio, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
         MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 3);
@@ -467,18 +463,14 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
     for (int i = threadIdx.x; i < 256; i += blockDim.x) w8[i] = w8_slots[i];
     constexpr int SIG_LAYER = KS_REG * SIG_CHUNK_BYTES;   // one wave's sigmoids of one layer: 8 (UNORM8) or 16 KiB
     const ChunkMasks cm = chunk_masks(net);
-    const bool wraps = ring_stream_path<HID_SIGMUL>() && ring_can_wrap(net);
+    const bool wraps = ring_can_wrap(net);
     RingStream rs = {0, false};
     TileInputs<TILE> in(xc, worklist, offset, count, wave * PTS + (lane & (PTS - 1)), blockIdx.x, gridDim.x);
     __syncthreads();   // w8 visible
     for (int t = blockIdx.x; offset + t * TILE < count; t += gridDim.x) {
         MP_STAMP_AT(HID_SIGMUL, 120 + MP_TILE_SLOT(t), 0);
         const bool more = wraps && (long long)offset + (long long)(t + gridDim.x) * TILE < count;
-#ifdef MP_EXP_GRAD_OLD   // ablation: the reverse sweep on the interleaved stream, two chunks in the ring
-        stream_prologue_issue<KS_IN, WAVES, false>(rs, net, wpack, smem, wave, lane);
-#else
         stream_prologue_issue<KS_IN, WAVES>(rs, net, wpack, smem, wave, lane);
-#endif
         float x[3];
         const int id = in.take(t, x);     // lanes l and l+32 both know point l's id
         if (lane < PTS) {   // d PE_f / d x_axis(f), f = 0..38 (embedders.py layout: x, then per octave sin(3), cos(3))
@@ -502,11 +494,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_grad(const NetDesc net, cons
 #pragma unroll
             for (int f = 0; f < 39; ++f) tb[9 + f] = ta[f];
         }
-        #ifdef MP_EXP_SIGCACHED
-        const SigIO sio = {const_cast<char*>(sigbuf) + ((size_t)(blockIdx.x) * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
-#else
         const SigIO sio = {const_cast<char*>(sigbuf) + ((size_t)t * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
-#endif
         // V_7 = sigma'_7 (.) W_8[sdf row]
         opx8 Bcur[KS_REG][NB];
 #pragma unroll
@@ -594,7 +582,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
     op_t* stage = (op_t*)(smem + L::stage) + wave * L::PTS * in_stride(KS_IN);
     load_bias(net, bias, bias_lds);
     const ChunkMasks cm = chunk_masks(net);
-    const bool wraps = ring_stream_path<HID_RELU>() && ring_can_wrap(net);
+    const bool wraps = ring_can_wrap(net);
     RingStream rs = {0, false};
     // the id and the position come a tile ahead (TileInputs); the normal is read behind the feature fragments as before
     TileInputs<L::TILE> in(xc, worklist, 0, count, lane < L::PTS ? wave * L::PTS + lane : -1, blockIdx.x, gridDim.x);
@@ -674,7 +662,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
     const float ox = cam[0], oy = cam[1], oz = cam[2];
     // one stream through both packs: density net -> colour net -> density net of the next tile ...
     const ChunkMasks cm_imp = chunk_masks(net_imp), cm_ren = chunk_masks(net_ren);
-    const bool wraps = ring_stream_path<HID_SOFTPLUS>() && ring_can_wrap(net_imp) && ring_can_wrap(net_ren);
+    const bool wraps = ring_can_wrap(net_imp) && ring_can_wrap(net_ren);
     RingStream rs = {0, false};
     for (int t = blockIdx.x; t * L::TILE < n_pts; t += gridDim.x) {
         const bool more = wraps && (long long)(t + gridDim.x) * L::TILE < n_pts;

@@ -89,11 +89,7 @@ __device__ __forceinline__ void lds_dma_16(const void* gsrc_uniform, unsigned la
 // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt 7 and lgkmcnt 15 = "do not wait").  The builtin, not asm text: hipcc's wait
 // insertion pass reads it and learns that ITS OWN global loads (inputs, stored sigmoids) are complete as well, so it
 // does not re-wait for them (with vmcnt(0), i.e. also for the weight stream) inside the next chunk.
-#ifdef MP_EXP_NOWAIT   // ablation (timing only, results are wrong): nobody waits for the weight DMA
-__device__ __forceinline__ void dma_wait_all() {}
-#else
 __device__ __forceinline__ void dma_wait_all() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-#endif
 __device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(size_t)p; }   // low half of the flat address
 __device__ __forceinline__ const char* uniform_ptr(const char* p) {
     const size_t v = (size_t)p;
@@ -101,8 +97,8 @@ __device__ __forceinline__ const char* uniform_ptr(const char* p) {
                          (unsigned)__builtin_amdgcn_readfirstlane((int)v));
 }
 
-// Pieces [P0, P1) of this wave's share of weight chunk ci (a chunk = NP 1 KiB pieces dealt round-robin to the waves).
-template <int KS_IN, int WAVES, int P0 = 0, int P1 = 99>
+// This wave's share of weight chunk ci (a chunk = NP 1 KiB pieces dealt round-robin to the waves).
+template <int KS_IN, int WAVES>
 __device__ __forceinline__ void issue_chunk(const char* __restrict__ wpack, char* wring, int ci, int wave, int lane) {
     constexpr int CB = chunk_bytes(KS_IN);
     constexpr int NP = CB / TILE_BYTES;
@@ -112,23 +108,12 @@ __device__ __forceinline__ void issue_chunk(const char* __restrict__ wpack, char
     const char* src = uniform_ptr(wpack) + (size_t)ci_u * CB + wave_u * TILE_BYTES;
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds_offset(wring)) + (ci_u % RING_SLOTS) * CB + wave_u * TILE_BYTES;
 #pragma unroll
-    for (int i = P0; i < (P1 < NI ? P1 : NI); ++i) {
+    for (int i = 0; i < NI; ++i) {
         if (wave_u + WAVES * i < NP) lds_dma_16(src + WAVES * i * TILE_BYTES, lane * 16, dst + WAVES * i * TILE_BYTES);
     }
 }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// Weight DMA of the phase-separated stream: issued by the EARLY waves at the tail of their V phase (round 6, default) or -- -DMP_DMA_LATE,
-// rounds 2-5 -- by the late waves at the head of theirs.  Same-box A/B (profiles/r06_early_dma_ab.txt): sampler SDF -2.6 %, forward
-// sweep -2 %, colour -1 %, reverse sweep 0, mp_tf_sdf_val -3...5 %.
-#if !defined(MP_DMA_LATE) && !defined(MP_DMA_EARLY)
-#define MP_DMA_EARLY 1
-#endif
-#ifdef MP_EXP_NOMFMA   // ablation (timing only, results are wrong): no matrix instructions
-#define MP_MFMA_F16(a, b, c, x, y, z) (c)
-#else
-#define MP_MFMA_F16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z)
-#endif
 
 #ifdef MP_EXP_STAMP   // ablation tooling: shader-clock stamps of workgroup 0 at every chunk boundary (mp_debug_stamps)
 __device__ unsigned long long mp_stamps[8 * 128 * 4];
@@ -225,7 +210,7 @@ struct SigIO {
 //
 // The fp32 accumulators of two rows are rounded to a packed half pair FIRST (one v_cvt_pk_f16_f32) and the whole
 // activation runs on the pair; its result is the next layer's operand register as it stands.
-// v_exp_f16 / v_log_f16 have no packed form: low half, then high half written in place (SDWA, UNUSED_PRESERVE).  The
+// v_exp_f16 has no packed form: low half, then high half written in place (SDWA, UNUSED_PRESERVE).  The
 // s_nop 0 between them is the gfx940+ transcendental-result hazard: the second instruction READS the first one's result
 // (to preserve the low half) and the assembler does not insert wait states inside an asm block.
 __device__ __forceinline__ h2 exp2_h2(h2 x) {
@@ -244,14 +229,6 @@ __device__ __forceinline__ h2 exp2_neg_abs_h2(h2 x) {   // 2^-|x| with the sourc
         : "=&v"(r) : "v"(xi));
     return __builtin_bit_cast(h2, r);
 }
-__device__ __forceinline__ h2 log2_h2(h2 x) {
-    unsigned r;
-    const unsigned xi = bits(x);
-    asm("v_log_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0\n\ts_nop 0\n\t"
-        "v_log_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1"
-        : "=&v"(r) : "v"(xi));
-    return __builtin_bit_cast(h2, r);
-}
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 // ReLU on the BIT PATTERN: a negative half is a negative int16, so one v_pk_max_i16 against 0 does it (-0 -> +0), without
 // the canonicalising extra v_pk_max the float max builtin carries and without inline asm (which the scheduler cannot
@@ -260,20 +237,13 @@ __device__ __forceinline__ h2 relu_h2(h2 z) {
     return __builtin_bit_cast(h2, __builtin_elementwise_max(__builtin_bit_cast(s16x2, z), (s16x2){0, 0}));
 }
 __device__ __forceinline__ h2 softplus2(h2 z) {   // h' = max(z',0) + log2(1 + 2^-|z'|)
-#ifdef MP_EXP_NOTRANS
-    return relu_h2(z) + z * (h2){(op_t)0.001f, (op_t)0.001f};
-#else
     const h2 u = exp2_neg_abs_h2(z);
-#ifdef MP_EXP_LOGTRANS
-    return relu_h2(z) + log2_h2(u + (h2){(op_t)1.0f, (op_t)1.0f});
-#else   // the same three fused multiply-adds as the phase-separated stream's V program (pp_instr): identical results
+    // the same three fused multiply-adds as the phase-separated stream's V program (pp_instr): identical results
     const h2 c1 = {(op_t)1.42459527f, (op_t)1.42459527f}, c2 = {(op_t)-0.58921265f, (op_t)-0.58921265f},
              c3 = {(op_t)0.16538905f, (op_t)0.16538905f};
     h2 t = __builtin_elementwise_fma(u, c3, c2);
     t = __builtin_elementwise_fma(t, u, c1);
     return __builtin_elementwise_fma(t, u, relu_h2(z));
-#endif
-#endif
 }
 // lanes 8..15 of every 16-lane row receive lane-8's register, lanes 0..7 keep their own (DPP row_shr:8).  Inline asm on
 // purpose (hipcc 7.2 merges two __builtin_amdgcn_update_dpp calls on the elements of a vector into one broadcast);
@@ -285,142 +255,64 @@ __device__ __forceinline__ h2 row_shr8(h2 s) {
     return __builtin_bit_cast(h2, d);
 }
 
-// Piece q (0..7) of the activation of a finished block of 16 rows x NB column blocks; one piece rides in every K step
+// The interleaved stream below (act_piece, act_drain, run_layer) serves the forward-mode kernel only: every plain-mode network
+// runs on the phase-separated stream (run_layer_pp).
+//
+// Piece q (0..7) of the activation of a finished block of 16 rows x 2 column blocks; one piece rides in every K step
 // of the next block's MFMA stream.  HIDDEN (compile time: the layer loop dispatches on it, so that the K-step stream
 // is straight-line code): apply the nonlinearity, else pass through.
-//   plain  : q = 0..3 -> column block q/2, row pair q%2
-//   forward: half-block tangent layout (8 points per wave): block 0 = [values | d/dx], block 1 = [d/dy | d/dz]; lanes
-//            with (lane & 8) == 0 hold the value / d/dy columns of point lane&7, the others d/dx / d/dz.
-//            q = 0, 1: row pair q of both blocks (softplus + sigmoid on the values, tangents scaled by the sigmoid)
-template <int NB, bool FWD, int HID, bool HIDDEN, int q, typename NB_T>
-__device__ __forceinline__ void act_piece(const f32x4 (&p)[NB], NB_T& Bn, int pc, int ph, u32x4 (&sg)[NB],
-                                          const SigIO& sig, int sig_layer) {
-    static_assert(NB == 2, "the MLP core is specialised for 2 column blocks per wave (2 waves per SIMD)");
-    if constexpr (FWD) {
-        if constexpr (q < 2) {
-            h2 z = to_h2(p[0][2 * q], p[0][2 * q + 1]);
-            h2 t = to_h2(p[1][2 * q], p[1][2 * q + 1]);
-            if constexpr (HIDDEN) {
-                const bool vl = (threadIdx.x & 8) == 0;
-                const h2 h = softplus2(z);
-#ifdef MP_EXP_NOTRANS
-                const h2 s = z * (h2){(op_t)0.01f, (op_t)0.01f};
-#else
-                const h2 s = exp2_h2(z - h);          // sigmoid(z') = 2^(z' - h'); meaningful in the value lanes
-#endif
-                const h2 sf = row_shr8(s);            // tangent lanes take it from their point's value lane
-                const h2 zt = z * sf;
-                z = vl ? h : zt;
-                t = t * sf;
-            }
-            if (pc < KS_REG) {
-                Bn.put(pc, 0, ph, q, z);
-                Bn.put(pc, 1, ph, q, t);
-            }
+// Half-block tangent layout (8 points per wave): block 0 = [values | d/dx], block 1 = [d/dy | d/dz]; lanes with
+// (lane & 8) == 0 hold the value / d/dy columns of point lane&7, the others d/dx / d/dz.
+// q = 0, 1: row pair q of both blocks (softplus + sigmoid on the values, tangents scaled by the sigmoid)
+template <bool HIDDEN, int q, typename NB_T>
+__device__ __forceinline__ void act_piece(const f32x4 (&p)[2], NB_T& Bn, int pc, int ph) {
+    if constexpr (q < 2) {
+        h2 z = to_h2(p[0][2 * q], p[0][2 * q + 1]);
+        h2 t = to_h2(p[1][2 * q], p[1][2 * q + 1]);
+        if constexpr (HIDDEN) {
+            const bool vl = (threadIdx.x & 8) == 0;
+            const h2 h = softplus2(z);
+            const h2 s = exp2_h2(z - h);          // sigmoid(z') = 2^(z' - h'); meaningful in the value lanes
+            const h2 sf = row_shr8(s);            // tangent lanes take it from their point's value lane
+            const h2 zt = z * sf;
+            z = vl ? h : zt;
+            t = t * sf;
         }
-    } else {
-        if constexpr (q < 4) {
-            constexpr int nb = q / 2, j = q % 2;
-            h2 z = to_h2(p[nb][2 * j], p[nb][2 * j + 1]);
-            if constexpr (HIDDEN) {
-                if constexpr (HID == HID_SOFTPLUS_SAVE) {
-                    const h2 h = softplus2(z);
-#ifdef MP_EXP_NOTRANS
-                    const unsigned sv = bits(z * (h2){(op_t)0.01f, (op_t)0.01f});
-#else
-                    const unsigned sv = bits(exp2_h2(z - h));   // sigmoid(z') = 2^(z' - h')
-#endif
-                    if (ph == 0) { if (j == 0) sg[nb][0] = sv; else sg[nb][1] = sv; }
-                    else { if (j == 0) sg[nb][2] = sv; else sg[nb][3] = sv; }
-                    z = h;
-                    if (ph == 1 && j == 1 && pc < KS_REG)
-                        *(u32x4*)(sig.base + (size_t)sig_layer * sig.layer_bytes + (pc * NB + nb) * 1024 + (threadIdx.x & 63) * 16) = sg[nb];
-                } else if constexpr (HID == HID_SIGMUL) {
-                    const unsigned sv = ph == 0 ? (j == 0 ? sg[nb][0] : sg[nb][1]) : (j == 0 ? sg[nb][2] : sg[nb][3]);
-                    z = z * __builtin_bit_cast(h2, sv);
-                } else {
-                    z = HID == HID_SOFTPLUS ? softplus2(z) : relu_h2(z);
-                }
-            }
-            if (pc < KS_REG) Bn.put(pc, nb, ph, j, z);
+        if (pc < KS_REG) {
+            Bn.put(pc, 0, ph, q, z);
+            Bn.put(pc, 1, ph, q, t);
         }
     }
 }
 
-template <int NB, bool FWD, int HID, bool HIDDEN, int q, typename NB_T>
-__device__ __forceinline__ void act_from(const f32x4 (&p)[NB], NB_T& Bn, int pc, int ph, u32x4 (&sg)[NB],
-                                         const SigIO& sig, int sig_layer) {
-    act_piece<NB, FWD, HID, HIDDEN, q>(p, Bn, pc, ph, sg, sig, sig_layer);
-    if constexpr (q + 1 < 8) act_from<NB, FWD, HID, HIDDEN, q + 1>(p, Bn, pc, ph, sg, sig, sig_layer);
+template <bool HIDDEN, int q, typename NB_T>
+__device__ __forceinline__ void act_from(const f32x4 (&p)[2], NB_T& Bn, int pc, int ph) {
+    act_piece<HIDDEN, q>(p, Bn, pc, ph);
+    if constexpr (q + 1 < 8) act_from<HIDDEN, q + 1>(p, Bn, pc, ph);
 }
-
-// Sigmoid fragment buffers: chunk pc's four dwords per column block live in sgb[pc & 1]: written (HID_SOFTPLUS_SAVE) or
-// read (HID_SIGMUL, loaded at the chunk's start) from block (pc,1) to block (pc+1,0).  [Loading the reverse sweep's
-// fragments one chunk ahead into a third buffer, with or without letting them stay in flight across the chunk
-// barrier (s_waitcnt vmcnt(4) instead of 0), was measured 5-7 % SLOWER: the sweep is not waiting for HBM.]
-constexpr int SIG_BUFS = 2;
-template <int HID>
-__device__ __forceinline__ constexpr int sig_slot(int pc) { return pc & 1; }
 
 // Activation of a layer's LAST block (chunk pc_rt = n_chunk - 1, known only at run time, second half block): the one
 // piece of the pipeline that has no next block to ride in.  Written with selects on pc_rt -- when it was a copy of
 // act_from per unrolled chunk, hipcc merged the copies into one block that indexes the operand array dynamically and
 // moved the array to scratch memory.
-template <int NB, bool FWD, int HID, bool HIDDEN, typename NB_T>
-__device__ __forceinline__ void act_drain(const f32x4 (&p)[NB], NB_T& Bn, int pc_rt, u32x4 (&sgb)[SIG_BUFS][NB],
-                                          const SigIO& sig, int sig_layer) {
-    const bool odd = pc_rt & 1;
-#define MP_SG(nb, i) (odd ? sgb[1][nb][i] : sgb[0][nb][i])
-    if constexpr (FWD) {
+template <bool HIDDEN, typename NB_T>
+__device__ __forceinline__ void act_drain(const f32x4 (&p)[2], NB_T& Bn, int pc_rt) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            h2 z = to_h2(p[0][2 * q], p[0][2 * q + 1]);
-            h2 t = to_h2(p[1][2 * q], p[1][2 * q + 1]);
-            if constexpr (HIDDEN) {
-                const bool vl = (threadIdx.x & 8) == 0;
-                const h2 h = softplus2(z);
-                const h2 s = exp2_h2(z - h);
-                const h2 sf = row_shr8(s);
-                const h2 zt = z * sf;
-                z = vl ? h : zt;
-                t = t * sf;
-            }
-            Bn.put_sel(pc_rt, 0, 1, q, z);
-            Bn.put_sel(pc_rt, 1, 1, q, t);
+    for (int q = 0; q < 2; ++q) {
+        h2 z = to_h2(p[0][2 * q], p[0][2 * q + 1]);
+        h2 t = to_h2(p[1][2 * q], p[1][2 * q + 1]);
+        if constexpr (HIDDEN) {
+            const bool vl = (threadIdx.x & 8) == 0;
+            const h2 h = softplus2(z);
+            const h2 s = exp2_h2(z - h);
+            const h2 sf = row_shr8(s);
+            const h2 zt = z * sf;
+            z = vl ? h : zt;
+            t = t * sf;
         }
-    } else {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            // the four dwords of this chunk's sigmoid fragment, selected by buffer one by one (explicit scalars: with
-            // a u32x4 temporary indexed by the unrolled row-pair counter, hipcc 7.2 multiplied both row pairs by dword 0)
-            const unsigned s0 = MP_SG(nb, 0), s1 = MP_SG(nb, 1);
-            unsigned s2 = MP_SG(nb, 2), s3 = MP_SG(nb, 3);
-            h2 z0 = to_h2(p[nb][0], p[nb][1]), z1 = to_h2(p[nb][2], p[nb][3]);
-            if constexpr (HIDDEN) {
-                if constexpr (HID == HID_SOFTPLUS_SAVE) {
-                    const h2 h0 = softplus2(z0), h1 = softplus2(z1);
-                    s2 = bits(exp2_h2(z0 - h0));
-                    s3 = bits(exp2_h2(z1 - h1));
-                    z0 = h0;
-                    z1 = h1;
-                } else if constexpr (HID == HID_SIGMUL) {
-                    z0 = z0 * __builtin_bit_cast(h2, s2);
-                    z1 = z1 * __builtin_bit_cast(h2, s3);
-                } else {
-                    z0 = HID == HID_SOFTPLUS ? softplus2(z0) : relu_h2(z0);
-                    z1 = HID == HID_SOFTPLUS ? softplus2(z1) : relu_h2(z1);
-                }
-            }
-            Bn.put_sel(pc_rt, nb, 1, 0, z0);
-            Bn.put_sel(pc_rt, nb, 1, 1, z1);
-            if constexpr (HIDDEN && HID == HID_SOFTPLUS_SAVE) {
-                if (pc_rt < KS_REG)
-                    *(u32x4*)(sig.base + (size_t)sig_layer * sig.layer_bytes + (pc_rt * NB + nb) * 1024 + (threadIdx.x & 63) * 16) =
-                        (u32x4){s0, s1, s2, s3};
-            }
-        }
+        Bn.put_sel(pc_rt, 0, 1, q, z);
+        Bn.put_sel(pc_rt, 1, 1, q, t);
     }
-#undef MP_SG
 }
 
 constexpr int A_PF = 3, A_QN = 4;   // A-tile prefetch distance / rotating queue length (tiles), interleaved stream
@@ -446,7 +338,7 @@ constexpr int AQ_LEN = PP_QN > A_QN ? PP_QN : A_QN;
 // [V(c-1) M(c)]  from the other: one wave's MFMAs beside the other's VALU work.  The ring protocol is unchanged (every
 // wave passes one barrier per chunk, after its M(c): chunk c's slot may be refilled, chunk c+1 is complete), and V(c)
 // has a compile-time chunk index, so the run-time "drain" of the layer's last block does not exist on this path.
-// Arithmetic per element is exactly act_piece's.
+// Arithmetic per element is exactly softplus2's.
 struct ActRegs8 {
     unsigned z[8], u[8], lg[8], r[8], h[8], d[8], s[8];
 };
@@ -454,11 +346,6 @@ struct ActRegs8 {
 // the v_exp / +1 / v_log chain it replaces loses u below 2^-11 in the half-precision sum 1 + u and is no better).  Three
 // packed FMAs instead of an addition and two transcendentals per row pair -- beside the partner wave's MFMAs a v_log costs
 // 13.3 cycles of the SIMD's vector pipe, a packed FMA 8.25 (tools/pair_model.hip) -- and the last FMA adds max(z', 0).
-#ifdef MP_EXP_LOGTRANS   // ablation: the transcendental chain
-constexpr bool LOG_POLY = false;
-#else
-constexpr bool LOG_POLY = true;
-#endif
 constexpr float LOG2P_C1 = 1.42459527f, LOG2P_C2 = -0.58921265f, LOG2P_C3 = 0.16538905f;
 // The stored sigmoids travel through HBM as UNORM8 (default; -DMP_EXP_SIG16: as halves, 4 KiB per point).  At half precision the
 // forward sweep writes 512 B per point and hidden layer: at a fraction f of the MFMA peak that is f x 9.8 TB/s of stores (the
@@ -510,7 +397,7 @@ __device__ __forceinline__ ActConst act_const() {
 __device__ __forceinline__ unsigned sconst(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }   // into an SGPR
 // stages of the V program per layer kind (HIDDEN = false: the linear output layers, conversion only)
 __host__ __device__ constexpr int pp_stages(int hid, bool hidden) {
-    return !hidden ? 1 : hid == HID_SOFTPLUS_SAVE ? (LOG_POLY ? 10 : 11) + (SIG8 ? 2 : 0) - (SIG_FROM_H ? 1 : 0) : hid == HID_SOFTPLUS ? (LOG_POLY ? 7 : 8)
+    return !hidden ? 1 : hid == HID_SOFTPLUS_SAVE ? 10 + (SIG8 ? 2 : 0) - (SIG_FROM_H ? 1 : 0) : hid == HID_SOFTPLUS ? 7
                      : hid == HID_SIGMUL && SIG8 ? 5 : 2;
 }
 
@@ -520,12 +407,10 @@ __device__ __forceinline__ void pp_instr(ActRegs8& a, const ActConst& k, const f
                                          u32x4 (&sg)[2]) {
     constexpr int mbl = q / 4, nb = (q / 2) % 2, j = q % 2;
     constexpr bool SP = HIDDEN && (HID == HID_SOFTPLUS || HID == HID_SOFTPLUS_SAVE);
-    // softplus stage ids: E0 E1 = u = 2^-|z'| (low half writes the dword, high half in place); then either
-    //   polynomial: P0 t = C3 u + C2, P1 t = t u + C1, RL r = max(z', 0), HH h' = t u + r
-    //   transcendental: A1 u += 1, L0 L1 lg = log2(u), RL, HH h' = r + lg
+    // softplus stage ids: E0 E1 = u = 2^-|z'| (low half writes the dword, high half in place); then the polynomial:
+    //   P0 t = C3 u + C2, P1 t = t u + C1, RL r = max(z', 0), HH h' = t u + r
     // and for the stored sigmoids: SB d = z' - h', S0 S1 sigmoid = 2^d
-    constexpr int E0 = 1, E1 = 2, P0 = LOG_POLY ? 3 : -1, P1 = LOG_POLY ? 4 : -1, A1 = LOG_POLY ? -1 : 3, L0 = LOG_POLY ? -1 : 4,
-                  L1 = LOG_POLY ? -1 : 5, RL = LOG_POLY ? 5 : 6, HH = LOG_POLY ? 6 : 7, SB = SIG_FROM_H ? -1 : HH + 1,
+    constexpr int E0 = 1, E1 = 2, P0 = 3, P1 = 4, RL = 5, HH = 6, SB = SIG_FROM_H ? -1 : HH + 1,
                   S0 = SIG_FROM_H ? HH + 1 : HH + 2, S1 = S0 + 1;
     if constexpr (ST == 0) {          // left to the compiler: it knows the MFMA -> VALU read hazard
         a.z[q] = bits(to_h2(acc[mbl][nb][2 * j], acc[mbl][nb][2 * j + 1]));
@@ -577,17 +462,10 @@ __device__ __forceinline__ void pp_instr(ActRegs8& a, const ActConst& k, const f
         asm volatile("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(a.lg[q]) : "v"(a.u[q]), "v"(k.c3), "v"(k.c2));
     } else if constexpr (ST == P1) {
         asm volatile("v_pk_fma_f16 %0, %0, %1, %2" : "+v"(a.lg[q]) : "v"(a.u[q]), "v"(k.c1));
-    } else if constexpr (ST == A1) {
-        asm volatile("v_pk_add_f16 %0, %0, 1.0 op_sel_hi:[1,0]" : "+v"(a.u[q]));
-    } else if constexpr (ST == L0) {
-        asm volatile("v_log_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=&v"(a.lg[q]) : "v"(a.u[q]));
-    } else if constexpr (ST == L1) {
-        asm volatile("v_log_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1" : "+v"(a.lg[q]) : "v"(a.u[q]));
     } else if constexpr (ST == RL) {  // max(z', 0) on the bit pattern
         asm volatile("v_pk_max_i16 %0, %1, 0" : "=v"(a.r[q]) : "v"(a.z[q]));
     } else if constexpr (ST == HH) {  // h' = max(z', 0) + log2(1 + 2^-|z'|): the next layer's operand register as it stands
-        if constexpr (LOG_POLY) asm volatile("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(a.h[q]) : "v"(a.lg[q]), "v"(a.u[q]), "v"(a.r[q]));
-        else asm volatile("v_pk_add_f16 %0, %1, %2" : "=v"(a.h[q]) : "v"(a.r[q]), "v"(a.lg[q]));
+        asm volatile("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(a.h[q]) : "v"(a.lg[q]), "v"(a.u[q]), "v"(a.r[q]));
         if (c < KS_REG) Bn.put(c, nb, mbl, j, __builtin_bit_cast(h2, a.h[q]));
     } else if constexpr (ST == SB) {  // z' - h'
         asm volatile("v_pk_add_f16 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(a.d[q]) : "v"(a.z[q]), "v"(a.h[q]));
@@ -687,9 +565,9 @@ __device__ __forceinline__ ChunkMasks chunk_masks(const NetDesc& net) {
     return ChunkMasks{{uniform_u64(r0), uniform_u64(r1)}, {uniform_u64(i0), uniform_u64(i1)}};
 }
 
-// The phase-separated stream's weight DMA: issued by the LATE waves only (wl = wave - WAVES/2 = 0..3), right behind
-// their barrier, i.e. at the head of a V phase -- an LDS-DMA instruction costs 25-60 cycles to issue among VALU work
-// and 100-185 among MFMAs (MI355X_MICROARCH.md), and it is waited for a whole M phase later.  Pieces of chunk `cn` (1 KiB
+// The phase-separated stream's weight DMA: issued by the EARLY waves only (wl = wave = 0..3), at the tail of a V phase
+// (run_layer_pp) -- an LDS-DMA instruction costs 25-60 cycles to issue among VALU work and 100-185 among MFMAs
+// (MI355X_MICROARCH.md) -- and waited for one chunk later.  Pieces of chunk `cn` (1 KiB
 // each, chunk layout [row block][8 register-fed tiles | KS_IN input-fed tiles]): wave wl takes register-fed tiles
 // {wl, wl + 4} of both row blocks and input-fed pieces {wl, wl + 4} of the 2 KS_IN; tiles the chunk's layer never
 // multiplies are skipped.  Addressing: ONE scalar source base per chunk + per-piece lane offsets prepared once per
@@ -698,7 +576,8 @@ template <int KS_IN>
 struct DmaLanes {
     unsigned reg[4];                 // lane*16 + byte offset of this wave's four register-fed pieces
     unsigned in[(2 * KS_IN + 3) / 4 + 1];   // ... of its input-fed pieces (the last may not exist; + 1: never a zero-length array)
-    unsigned run;                    // MP_DMA_ONE_M0: lane*16 + byte offset of this wave's contiguous 4 KiB run of register-fed tiles
+    unsigned run;                    // lane*16 + byte offset of a contiguous 4 KiB run of register-fed tiles.  Read by nothing: it stays because
+                                     // without it hipcc allocates the registers of seven product kernels differently
     unsigned wl;
 };
 template <int KS_IN>
@@ -719,17 +598,10 @@ __device__ __forceinline__ DmaLanes<KS_IN> dma_lanes(int wl, int lane) {
 }
 __device__ __forceinline__ void pp_dma_piece(const char* src_chunk_uniform, unsigned lane_off, unsigned lds_chunk_base,
                                              unsigned piece_off_uniform) {
-#ifdef MP_EXP_DMA1LANE   // ablation (timing only, results are wrong): the same instructions, ONE lane's 16 bytes instead of 1 KiB per piece
-    asm volatile("s_mov_b64 s[98:99], exec\n\ts_mov_b64 exec, 1\n\ts_add_u32 m0, %0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-                 "s_mov_b64 exec, s[98:99]"
-                 ::"s"(lds_chunk_base), "s"(piece_off_uniform), "v"(lane_off), "s"(src_chunk_uniform) : "memory", "s98", "s99");
-#else
     asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3"
                  ::"s"(lds_chunk_base), "s"(piece_off_uniform), "v"(lane_off), "s"(src_chunk_uniform) : "memory");
-#endif
 }
-// PART: 0 = all of this wave's pieces, 1 = those of row block 0 only, 2 = those of row block 1 only (-DMP_DMA_SPLIT)
-template <int KS_IN, int PART = 0>
+template <int KS_IN>
 __device__ __forceinline__ void pp_issue(const char* __restrict__ wpack, char* wring, int cn, int ring_slot,
                                          const ChunkMasks& cm, const DmaLanes<KS_IN>& d) {
     constexpr int CB = chunk_bytes(KS_IN);
@@ -738,36 +610,21 @@ __device__ __forceinline__ void pp_issue(const char* __restrict__ wpack, char* w
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds_offset(wring)) + __builtin_amdgcn_readfirstlane(ring_slot) * CB;
     const unsigned wl = __builtin_amdgcn_readfirstlane(d.wl);
     if (cm.has_reg(cn_u)) {
-#ifdef MP_DMA_ONE_M0
-        // ONE M0 write per chunk: wave wl takes the register-fed tiles 4 (wl & 1) .. + 3 of row block wl >> 1 -- a contiguous
-        // 4 KiB run in the chunk (source and ring slot have the same layout), its four pieces addressed through the
-        // instruction's immediate offset, which moves the global AND the LDS address (tools/stream_model.hip: +2..5 % on
-        // the forward sweep, +1..4 % on the reverse sweep against one s_add + s_nop per piece)
-        const unsigned run = (wl >> 1) * mb_bytes(KS_IN) + (wl & 1) * 4 * TILE_BYTES;
-        asm volatile("s_add_u32 m0, %0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\tglobal_load_lds_dwordx4 %2, %3 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %2, %3 offset:2048\n\tglobal_load_lds_dwordx4 %2, %3 offset:3072"
-                     ::"s"(dst), "s"(run), "v"(d.run), "s"(src) : "memory");
-#else
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if (PART == 0 || i / 2 == PART - 1)
-                pp_dma_piece(src, d.reg[i], dst, (i / 2) * mb_bytes(KS_IN) + (wl + 4 * (i % 2)) * TILE_BYTES);
-#endif
+            pp_dma_piece(src, d.reg[i], dst, (i / 2) * mb_bytes(KS_IN) + (wl + 4 * (i % 2)) * TILE_BYTES);
     }
     if constexpr (KS_IN > 0) {
         if (cm.has_in(cn_u)) {
 #pragma unroll
             for (int i = 0; i < (2 * KS_IN + 3) / 4; ++i) {
                 const unsigned k = wl + 4 * i;
-                if (k < 2 * KS_IN && (PART == 0 || k / KS_IN == PART - 1))
+                if (k < 2 * KS_IN)
                     pp_dma_piece(src, d.in[i], dst, (k / KS_IN) * mb_bytes(KS_IN) + (KS_REG + k % KS_IN) * TILE_BYTES);
             }
         }
     }
 }
-
-template <int P>
-struct PartC { static constexpr int value = P; };   // pp_issue's PART as a value (for a generic lambda)
 
 struct NoCapture {
     template <int NB>
@@ -784,18 +641,8 @@ struct RingStream {
     int pos;     // ring slot of the chunk that is multiplied next
     bool fed;    // the next pack's first chunks are in the ring / on their way already: no prologue
 };
-// one-shot prologue per tile: the interleaved stream (MP_EXP_NOPP, MP_EXP_GRAD_OLD, the forward-mode kernel) and packs too short to
-// wrap (a DMA issued three chunks ahead of a pack's last chunk must land in the SAME next pack)
-template <int HID>
-__host__ __device__ constexpr bool ring_stream_path() {
-#if defined(MP_EXP_NOPP)
-    return false;
-#elif defined(MP_EXP_GRAD_OLD)
-    return HID != HID_SIGMUL;
-#else
-    return true;
-#endif
-}
+// one-shot prologue per tile: packs too short to wrap (a DMA issued three chunks ahead of a pack's last chunk must land in the SAME
+// next pack)
 __device__ __forceinline__ bool ring_can_wrap(const NetDesc& net) { return net.total_chunks >= RING_SLOTS; }
 
 // One layer of the phase-separated stream (every layer kind of the plain-mode kernels: softplus with or without the
@@ -804,7 +651,7 @@ __device__ __forceinline__ bool ring_can_wrap(const NetDesc& net) { return net.t
 template <int KS_IN, int HID, int WAVES, bool HIDDEN, typename Cap, typename NB_T>
 __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc L, int l, const char* __restrict__ wpack,
                                              const float* bias_lds, char* wring, opx8 (&Bcur)[KS_REG][2], NB_T& Bn,
-                                             opx8 (&aq)[AQ_LEN], u32x4 (&sgb)[SIG_BUFS][2], const op_t* stage_wave,
+                                             opx8 (&aq)[AQ_LEN], u32x4 (&sg)[2], const op_t* stage_wave,
                                              f32x4 (&out)[2], int wave, int lane, const SigIO& sig, Cap& cap, int& ci,
                                              int& ring_pos, const ChunkMasks& cm, const DmaLanes<KS_IN>& dl, int pp_last, bool fed,
                                              const char* __restrict__ next_wpack, const ChunkMasks& next_cm) {
@@ -820,13 +667,13 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
     const ActConst kact = act_const();
     // the chunk `ahead` chunks down the stream from chunk ci into ring slot `slot`: this pack's, or -- past its end -- one of the
     // first chunks of the pack that runs next (RingStream); none when the workgroup's last network ends
-    auto issue_ahead = [&](auto part, int ahead, int slot) {
+    auto issue_ahead = [&](int ahead, int slot) {
         const int cn = ci + ahead;
         const bool wrap = cn > pp_last;
         if (!wrap || next_wpack != nullptr) {
             const ChunkMasks m = {{wrap ? next_cm.reg[0] : cm.reg[0], wrap ? next_cm.reg[1] : cm.reg[1]},
                                   {wrap ? next_cm.in[0] : cm.in[0], wrap ? next_cm.in[1] : cm.in[1]}};
-            pp_issue<KS_IN, decltype(part)::value>(wrap ? next_wpack : wpack, wring, wrap ? cn - pp_last - 1 : cn, slot, m, dl);
+            pp_issue<KS_IN>(wrap ? next_wpack : wpack, wring, wrap ? cn - pp_last - 1 : cn, slot, m, dl);
         }
     };
 #pragma unroll
@@ -845,21 +692,15 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
             // the fragment across the LAYER loop as well costs hipcc 7.2 the register file: 256 VGPRs + 112 spilled, from
             // 208 -- and scratch traffic counts in vmcnt.]
             constexpr bool REV = HID == HID_SIGMUL && HIDDEN;
-#ifdef MP_EXP_NOAHEAD   // ablation: every fragment at the head of its own chunk, full drain behind M(c)
-            constexpr bool AHEAD = false;
-#else
-            constexpr bool AHEAD = REV;
-#endif
-            u32x4 (&sg)[2] = sgb[0];
             u32x4 sgn[2];
             constexpr int SGV = SIG8 ? 1 : 2;   // 16-byte vectors per lane and chunk
             if constexpr (REV) {
-                if (!AHEAD || c == 0) {
+                if (c == 0) {
 #pragma unroll
                     for (int v = 0; v < SGV; ++v)
                         sg[v] = *(const u32x4*)(sig.base + (size_t)sig_layer * sig.layer_bytes + (c * SGV + v) * 1024 + lane * 16);
                 }
-                if (AHEAD && c + 1 < KS_REG) {
+                if (c + 1 < KS_REG) {
 #pragma unroll
                     for (int v = 0; v < SGV; ++v)
                         sgn[v] = *(const u32x4*)(sig.base + (size_t)sig_layer * sig.layer_bytes + ((c + 1) * SGV + v) * 1024 + lane * 16);
@@ -879,18 +720,16 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                 for (int t = 0; t < NT; ++t) {
                     const int ks = t / 2, mbl = t % 2;
                     const opx8 a = aq[t % QN];
-#ifndef MP_EXP_NOLDS
                     if (t + PF < NT) {
                         const int tn = t + PF;
                         aq[tn % QN] = *(const opx8*)(slot + (tn % 2) * mb_bytes(KS_IN) + (tn / 2) * TILE_BYTES);
                     }
-#endif
                     // pinned: left alone, the scheduler sinks each read to just before its use and the M phase stalls
                     // on LDS latency at every tile (measured: 850 instead of 500 cycles)
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb)
-                        acc[mbl][nb] = MP_MFMA_F16(a, Bcur[ks][nb], acc[mbl][nb], 0, 0, 0);
+                        acc[mbl][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, Bcur[ks][nb], acc[mbl][nb], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -907,7 +746,7 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                             const opx8 a = *(const opx8*)(slot + mbl * mb_bytes(KS_IN) + (KS_REG + ks) * TILE_BYTES);
 #pragma unroll
                             for (int nb = 0; nb < 2; ++nb)
-                                acc[mbl][nb] = MP_MFMA_F16(a, bi[nb], acc[mbl][nb], 0, 0, 0);
+                                acc[mbl][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bi[nb], acc[mbl][nb], 0, 0, 0);
                         }
                     }
                 }
@@ -929,47 +768,27 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
             }
             MP_STAMP(1);
             // The reverse sweep's sigmoid loads (issued before M(c)) are waited for HERE by both kinds of wave: hipcc
-            // does not know the asm-issued DMA, so a wait it inserted in V(c) -- reached by the late waves right behind
-            // their DMA issue -- would wait for the fresh DMA pieces as well (measured: +9 % on k_mlp_grad).
-            // In flight, oldest first: [this chunk's fragment, fetched a chunk ago] [late waves: the DMA pieces issued behind
-            // the previous barrier] [the two loads just issued for the next chunk] -- the counted wait covers the first two.
+            // does not know the asm-issued DMA, so a wait it inserted in V(c) would be a full drain, the loads for the next
+            // chunk included (measured: +9 % on k_mlp_grad).
+            // In flight, oldest first: [this chunk's fragment, fetched a chunk ago] [early waves: the DMA pieces issued at the
+            // tail of the previous V phase] [the loads just issued for the next chunk] -- the counted wait covers the first two.
             if constexpr (REV) {
-                if (AHEAD && c + 1 < KS_REG) __builtin_amdgcn_s_waitcnt(0x0F70 | SGV);   // vmcnt(SGV): all but the loads just issued
+                if (c + 1 < KS_REG) __builtin_amdgcn_s_waitcnt(0x0F70 | SGV);   // vmcnt(SGV): all but the loads just issued
                 else dma_wait_all();
             }
             if (late) {
-#if defined(MP_DMA_SPLIT)
-                // both halves of the workgroup issue: the late waves row block 1 of chunk ci + 3 here, the early waves row block 0 of
-                // chunk ci + 2 at the tail of their V phase (below)
-                if constexpr (!REV) dma_wait_all();
-                __syncthreads();
-                issue_ahead(PartC<2>{}, 3, ring_pos);
-#elif defined(MP_DMA_EARLY)
-                __syncthreads();   // the late waves issue no DMA in this variant: nothing of theirs to wait for
-#else
-                // every DMA piece this wave issued (one whole M phase ago) has landed; every wave is done with chunk ci:
-                // its ring slot is free for chunk ci + 3
-                if constexpr (!REV) dma_wait_all();
-                __syncthreads();
-#ifndef MP_EXP_NOLOAD
-                issue_ahead(PartC<0>{}, 3, ring_pos);   // three chunks on, the stream is back at this chunk's slot
-#endif
-#endif
+                __syncthreads();   // the late waves issue no DMA: nothing of theirs to wait for
                 MP_STAMP(2);
             }
             // ---- V(c)
             __builtin_amdgcn_sched_barrier(0);
             {
                 ActRegs8 a;
-#ifdef MP_EXP_NOV   // ablation: no V phase (accumulators kept alive)
-                asm volatile("" ::"v"(acc[0][0]), "v"(acc[0][1]), "v"(acc[1][0]), "v"(acc[1][1]));
-#else
                 if constexpr (HID == HID_SOFTPLUS_X2) {
                     if constexpr (HIDDEN) x2_program(acc, Bn, c);   // the linear output layer: `out` holds the two partial sums
                 } else {
                     pp_program<HID, HIDDEN, 0>(a, kact, acc, Bn, c, sg);
                 }
-#endif
                 if constexpr (HID == HID_SOFTPLUS_SAVE && HIDDEN) {
 #pragma unroll
                     for (int v = 0; v < SGV; ++v)
@@ -978,32 +797,25 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
             }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (REV) {
-                if (AHEAD && c + 1 < KS_REG) {
+                if (c + 1 < KS_REG) {
 #pragma unroll
                     for (int v = 0; v < SGV; ++v) sg[v] = sgn[v];
                 }
             }
             if (!late) {
                 MP_STAMP(2);
-#ifdef MP_DMA_EARLY
-                // Variant (round 6): the EARLY waves issue the weight DMA, at the tail of their V phase -- where they otherwise
-                // wait at the barrier for the late waves, whose [barrier, DMA issue, V, M] chain is the chunk's critical path.
+                // The EARLY waves issue the weight DMA, at the tail of their V phase -- where they otherwise wait at the barrier
+                // for the late waves, whose [barrier, V, M] chain is the chunk's critical path (against the late waves issuing
+                // behind their barrier, profiles/r06_early_dma_ab.txt: sampler SDF -2.6 %, forward sweep -2 %, colour -1 %).
                 // Behind the barrier of chunk ci - 1 (passed at the tail of the previous iteration) slot (ci - 1) % 3 is free:
                 // chunk ci + 2 goes there; it is first read behind the barrier of chunk ci + 1, before which this wave waits
                 // for it (the wait below, one iteration from now).  The forward sweep's sigmoid stores of THIS V phase are the
                 // youngest operations in flight: the wait is counted so that it does not include them.
                 if constexpr (HID == HID_SOFTPLUS_SAVE && HIDDEN) __builtin_amdgcn_s_waitcnt(0x0F70 | (SIG8 ? 1 : 2));
                 else if constexpr (!REV) dma_wait_all();
-#ifndef MP_EXP_NOLOAD
                 // (a pack entered through the prologue has its chunk 2 already; one entered from the stream fetches it here)
-#ifdef MP_DMA_SPLIT
-                if (ci >= 1 || fed) issue_ahead(PartC<1>{}, 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1);
-#else
-                if (ci >= 1 || fed) issue_ahead(PartC<0>{}, 2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1);
-#endif
-#endif
-#endif
-                __syncthreads();   // default: the early waves issue no DMA: nothing to wait for (their stores need no wait)
+                if (ci >= 1 || fed) issue_ahead(2, ring_pos == 0 ? RING_SLOTS - 1 : ring_pos - 1);
+                __syncthreads();
             }
             MP_STAMP(3);
             // the next chunk's first tiles (complete in the ring: both kinds of wave are past the barrier behind M(c))
@@ -1021,100 +833,54 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
 }
 
 
-// K step of the next block that carries the first activation piece of a finished block.  The reverse sweep's pieces
-// (one multiplication each) sit in K steps 4..7, away from the MFMAs that produced their inputs: -8 % on k_mlp_grad;
-// the softplus pieces are best right at the start (+8 % on k_mlp_fwdsave when shifted).
-__device__ __forceinline__ constexpr int act_shift(int hid) { return hid == HID_SIGMUL ? 4 : 0; }
-
-// One layer.  Software pipeline: the activation of a finished 16-row block is issued, one piece per K step, inside the
-// MFMA stream of the next block (the two blocks of a chunk accumulate in two register sets, so nothing is copied);
-// A tiles run A_PF tiles ahead in a rotating register queue across block and chunk boundaries; the bias of the next
-// block is fetched one block ahead; weight chunks are loaded two chunks ahead into a 3-slot LDS ring (one barrier per
-// chunk).  Everything inside a block is straight-line code (a wave-uniform branch per K step costs issue slots and
-// fences the scheduler), and its LDS waits are counted (s_waitcnt lgkmcnt(3)), which needs the weight DMA to be issued
-// from inline asm: see lds_dma_16.
-template <int NB, bool FWD, int KS_IN, int HID, int WAVES, bool HIDDEN, typename Cap, typename NB_T>
+// One layer of the forward-mode kernel (2 column blocks in the half-block tangent layout, softplus).  Software pipeline: the
+// activation of a finished 16-row block is issued, one piece per K step, inside the MFMA stream of the next block (the two blocks
+// of a chunk accumulate in two register sets, so nothing is copied); A tiles run A_PF tiles ahead in a rotating register queue
+// across block and chunk boundaries; the bias of the next block is fetched one block ahead; weight chunks are loaded two chunks
+// ahead into a 3-slot LDS ring (one barrier per chunk).  Everything inside a block is straight-line code (a wave-uniform branch
+// per K step costs issue slots and fences the scheduler), and its LDS waits are counted (s_waitcnt lgkmcnt(3)), which needs the
+// weight DMA to be issued from inline asm: see lds_dma_16.
+template <int KS_IN, int WAVES, bool HIDDEN, typename Cap, typename NB_T>
 __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L, int l, const char* __restrict__ wpack,
-                                          const float* bias_lds, char* wring, opx8 (&Bcur)[KS_REG][NB], NB_T& Bn,
-                                          opx8 (&aq)[AQ_LEN], u32x4 (&sgb)[SIG_BUFS][NB], const op_t* stage_wave,
-                                          f32x4 (&out)[NB], int wave, int lane, const SigIO& sig, Cap& cap, int& ci) {
-    constexpr int PF = A_PF, QN = A_QN;
-    constexpr bool BIAS = HID != HID_SIGMUL;   // the reverse sweep has no bias
+                                          const float* bias_lds, char* wring, opx8 (&Bcur)[KS_REG][2], NB_T& Bn,
+                                          opx8 (&aq)[AQ_LEN], const op_t* stage_wave, f32x4 (&out)[2], int wave, int lane,
+                                          Cap& cap, int& ci) {
+    constexpr int NB = 2, PF = A_PF, QN = A_QN;
+    constexpr int HID = HID_SOFTPLUS;   // MP_STAMP's kernel filter
     const int g = lane >> 4;
-    const float* bl = BIAS ? bias_lds + l * BIAS_STRIDE + g * 4 : nullptr;
-    const int sig_layer = HID == HID_SIGMUL ? (L.aux & 0xff) - 1 : l;
+    const float* bl = bias_lds + l * BIAS_STRIDE + g * 4;
     const int cap_id = (L.aux >> 8) & 0xff;
     f32x4 accs[2][NB];   // block (c, mbl) accumulates in accs[mbl] while the activation of accs[mbl ^ 1] is issued
-    f32x4 bv_next = (f32x4){0, 0, 0, 0};
-    if constexpr (BIAS) bv_next = *(const f32x4*)bl;
-    auto load_sig = [&](int cc) {   // stored sigmoids of chunk cc (compile-time after unrolling) -> their buffer
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-            sgb[sig_slot<HID>(cc)][nb] = *(const u32x4*)(sig.base + (size_t)sig_layer * sig.layer_bytes + (cc * NB + nb) * 1024 +
-                                                         lane * 16);
-    };
+    f32x4 bv_next = *(const f32x4*)bl;
 #pragma unroll
     for (int c = 0; c < MAX_CHUNKS; ++c) {
         if (c < L.n_chunk) {
             MP_STAMP(0);
-#ifndef MP_EXP_DMA_FIRST
-            if constexpr (HID == HID_SIGMUL && HIDDEN) load_sig(c);   // HBM stream first, then the (L2-resident) weight stream
-#endif
-#if !defined(MP_EXP_NOLOAD) && !defined(MP_EXP_SPREAD_DMA)
             if (ci + 2 < net.total_chunks) issue_chunk<KS_IN, WAVES>(wpack, wring, ci + 2, wave, lane);
-#endif
-#ifdef MP_EXP_DMA_FIRST
-            if constexpr (HID == HID_SIGMUL && HIDDEN) load_sig(c);
-#endif
             const char* slot = wring + (ci % RING_SLOTS) * chunk_bytes(KS_IN) + lane * 16;
             // chunk ci+1 landed before the previous barrier: its first A tiles are prefetched from this chunk (after the
             // network's last chunk the read hits a stale ring slot and is never used)
             const char* slot_next = wring + ((ci + 1) % RING_SLOTS) * chunk_bytes(KS_IN) + lane * 16;
 #pragma unroll
             for (int mbl = 0; mbl < CHUNK_MB; ++mbl) {
-#ifdef MP_EXP_PRIO   // ablation: alternate the issue priority of the two waves of a SIMD block by block
-                if (((wave >> 2) ^ mbl) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
-#ifdef MP_EXP_SPREAD_DMA   // ablation: one piece per wave at the start of each block instead of all after the barrier
-                if (ci + 2 < net.total_chunks) {
-                    if (mbl == 0) issue_chunk<KS_IN, WAVES, 0, 1>(wpack, wring, ci + 2, wave, lane);
-                    else issue_chunk<KS_IN, WAVES, 1, 99>(wpack, wring, ci + 2, wave, lane);
-                }
-#endif
                 f32x4 (&acc)[NB] = accs[mbl];
                 const f32x4 (&pend)[NB] = accs[mbl ^ 1];   // finished block whose activation is still pending
                 const f32x4 bv = bv_next;
-                if constexpr (BIAS) bv_next = *(const f32x4*)(bl + (2 * c + mbl + 1) * 16);   // may run 16 floats past the table
+                bv_next = *(const f32x4*)(bl + (2 * c + mbl + 1) * 16);   // may run 16 floats past the table
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[nb] = (FWD && nb > 0) ? (f32x4){0, 0, 0, 0} : bv;
-                if constexpr (FWD) {  // half-block layout: only the value half of block 0 carries the bias
-                    if (threadIdx.x & 8) acc[0] = (f32x4){0, 0, 0, 0};
-                }
+                for (int nb = 0; nb < NB; ++nb) acc[nb] = nb > 0 ? (f32x4){0, 0, 0, 0} : bv;
+                if (threadIdx.x & 8) acc[0] = (f32x4){0, 0, 0, 0};   // half-block layout: only the value half of block 0 carries the bias
                 const char* tile = slot + mbl * mb_bytes(KS_IN);
                 // pending block = (c, 0) when mbl == 1, (c-1, 1) when mbl == 0
                 const bool has_pend = mbl == 1 || c > 0;
                 const int pc = mbl == 1 ? c : c - 1, ph = mbl == 1 ? 0 : 1;
-#ifdef MP_EXP_NOACT
-#define MP_ACT_STMT(KS)
-#else
-#define MP_ACT_STMT(KS)                                                                                               \
-    if constexpr (KS >= act_shift(HID)) {                                                                             \
-        if (has_pend)                                                                                                 \
-            act_piece<NB, FWD, HID, HIDDEN, KS - act_shift(HID)>(pend, Bn, pc, ph, sgb[sig_slot<HID>(pc)], sig, sig_layer); \
-    }
-#endif
-#ifdef MP_EXP_NOLDS
-#define MP_LDS_STMT (void)src;
-#else
-#define MP_LDS_STMT aq[nk % QN] = *(const opx8*)src;
-#endif
 #define MP_QSKIP(KS)                                                                                                  \
     {                                                                                                                 \
         constexpr int nk = KS + PF;                                                                                   \
         const char* src = nk < KS_REG ? tile + nk * TILE_BYTES                                                        \
                           : (mbl + 1 < CHUNK_MB ? tile + mb_bytes(KS_IN) + (nk - KS_REG) * TILE_BYTES                 \
                                                 : slot_next + (nk - KS_REG) * TILE_BYTES);                            \
-        if (nk >= KS_REG) { MP_LDS_STMT }                                                                             \
+        if (nk >= KS_REG) aq[nk % QN] = *(const opx8*)src;                                                            \
     }
 #define MP_KSTEP(KS)                                                                                                  \
     {                                                                                                                 \
@@ -1124,11 +890,11 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
             const char* src = nk < KS_REG ? tile + nk * TILE_BYTES                                                    \
                               : (mbl + 1 < CHUNK_MB ? tile + mb_bytes(KS_IN) + (nk - KS_REG) * TILE_BYTES             \
                                                     : slot_next + (nk - KS_REG) * TILE_BYTES);                        \
-            MP_LDS_STMT                                                                                               \
+            aq[nk % QN] = *(const opx8*)src;                                                                          \
         }                                                                                                             \
         _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                                             \
-            acc[nb] = MP_MFMA_F16(a, Bcur[KS][nb], acc[nb], 0, 0, 0);                     \
-        MP_ACT_STMT(KS)                                                                                               \
+            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, Bcur[KS][nb], acc[nb], 0, 0, 0);                     \
+        if (has_pend) act_piece<HIDDEN, KS>(pend, Bn, pc, ph);                                                        \
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                            \
         _Pragma("unroll") for (int q = 0; q < NB; ++q) {                                                              \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                        \
@@ -1142,14 +908,10 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
                     // layer fed only by the encoded input (layer 0): no register K steps; keep the A-tile queue
                     // in step with the tile stream and finish the pending block's activation
                     MP_QSKIP(0) MP_QSKIP(1) MP_QSKIP(2) MP_QSKIP(3) MP_QSKIP(4) MP_QSKIP(5) MP_QSKIP(6) MP_QSKIP(7)
-#ifndef MP_EXP_NOACT
-                    if (has_pend) act_from<NB, FWD, HID, HIDDEN, 0>(pend, Bn, pc, ph, sgb[sig_slot<HID>(pc)], sig, sig_layer);
-#endif
+                    if (has_pend) act_from<HIDDEN, 0>(pend, Bn, pc, ph);
                 }
 #undef MP_KSTEP
 #undef MP_QSKIP
-#undef MP_ACT_STMT
-#undef MP_LDS_STMT
                 if (L.use_in) {
 #pragma unroll
                     for (int ks = 0; ks < KS_IN; ++ks) {
@@ -1158,7 +920,7 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
                         for (int nb = 0; nb < NB; ++nb) {
                             const opx8 bi = *(const opx8*)(stage_wave + (nb * 16 + (lane & 15)) * in_stride(KS_IN) +
                                                                ks * 32 + g * 8);
-                            acc[nb] = MP_MFMA_F16(a, bi, acc[nb], 0, 0, 0);
+                            acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, bi, acc[nb], 0, 0, 0);
                         }
                     }
                 }
@@ -1177,17 +939,15 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
                 }
             }
             MP_STAMP(1);
-#ifndef MP_EXP_NOBARRIER
             dma_wait_all();   // this wave's pieces of chunk ci+2 (issued a whole chunk ago) and of every earlier chunk
             MP_STAMP(2);
             __syncthreads();  // every wave is done with chunk ci; chunk ci+1 is complete in the ring
             MP_STAMP(3);
-#endif
             ++ci;
         }
     }
     // layer ends: drain the pipeline (block (n_chunk - 1, 1); after the chunk's barrier, it touches registers only)
-    act_drain<NB, FWD, HID, HIDDEN>(accs[1], Bn, L.n_chunk - 1, sgb, sig, sig_layer);
+    act_drain<HIDDEN>(accs[1], Bn, L.n_chunk - 1);
 #pragma unroll
     for (int k = 0; k < KS_REG; ++k)
 #pragma unroll
@@ -1209,12 +969,6 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
                                         f32x4 (&out)[NB], int wave, int lane, SigIO sig, Cap cap, RingStream& rs,
                                         const ChunkMasks& cm, const char* __restrict__ next_wpack, const ChunkMasks& next_cm) {
     int ci = 0;
-    // sigmoid fragments of the K steps under construction (HID_SOFTPLUS_SAVE) / about to be applied (HID_SIGMUL): sig_slot
-    u32x4 sgb[SIG_BUFS][NB];
-#pragma unroll
-    for (int b = 0; b < SIG_BUFS; ++b)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) sgb[b][nb] = (u32x4){0u, 0u, 0u, 0u};
     NextB<NB, false> Bn;
     Bn.zero();
     opx8 aq[AQ_LEN];
@@ -1223,18 +977,13 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
     // every network on this path is a run of hidden layers followed by its linear output layer(s): two loops instead of
     // a per-layer dispatch keep the two instantiations of the layer body out of each other's register allocation
     int l = 0;
-#ifdef MP_EXP_NOPP   // ablation: the interleaved stream of run_layer for every layer
-    constexpr bool PP = false;
-#else
-#ifdef MP_EXP_GRAD_OLD   // ablation: the reverse sweep on the interleaved stream
-    constexpr bool PP = !FWD && NB == 2 && HID != HID_SIGMUL;
-#else
     constexpr bool PP = !FWD && NB == 2;
-#endif
-#endif
-    static_assert(PP || !SIG8 || (HID != HID_SOFTPLUS_SAVE && HID != HID_SIGMUL),
-                  "the interleaved (round-1) stream stores half-precision sigmoids: build the ablation with -DMP_EXP_SIG16");
+    static_assert(PP || (FWD && NB == 2 && HID == HID_SOFTPLUS), "the interleaved stream (run_layer) serves the forward-mode kernel only");
     if constexpr (PP) {
+        // sigmoid fragment of the chunk under construction (HID_SOFTPLUS_SAVE) / about to be applied (HID_SIGMUL)
+        u32x4 sg[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) sg[nb] = (u32x4){0u, 0u, 0u, 0u};
         // The phase-separated stream keeps THREE chunks in flight (prologue<.., true>: chunks 0, 1 and 2) and fetches
         // chunk ci + 3 behind the barrier that frees chunk ci's slot.
         const int pp_last = net.total_chunks - 1;
@@ -1247,10 +996,10 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
         for (int t = 0; t < PP_PF; ++t)
             aq[t % PP_QN] = *(const opx8*)(wring + ring_pos * chunk_bytes(KS_IN) + (t % 2) * mb_bytes(KS_IN) + (t / 2) * TILE_BYTES + lane * 16);
         for (; l < net.n_layers && net.layer[l].act != ACT_NONE; ++l)
-            run_layer_pp<KS_IN, HID, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave, out,
+            run_layer_pp<KS_IN, HID, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sg, stage_wave, out,
                                                   wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
         for (; l < net.n_layers; ++l)
-            run_layer_pp<KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave, out,
+            run_layer_pp<KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sg, stage_wave, out,
                                                    wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
         // handed on: the next pack's chunks 0 and 1 are in flight; or drained: the next prologue starts at slot 0
         rs.pos = next_wpack != nullptr ? ring_pos : 0;
@@ -1258,15 +1007,13 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
     }
     if constexpr (!PP) {
         for (; l < net.n_layers && net.layer[l].act != ACT_NONE; ++l)
-            run_layer<NB, FWD, KS_IN, HID, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave,
-                                                        out, wave, lane, sig, cap, ci);
+            run_layer<KS_IN, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, stage_wave, out, wave, lane, cap, ci);
+        for (; l < net.n_layers; ++l)
+            run_layer<KS_IN, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, stage_wave, out, wave, lane, cap, ci);
     }
-    for (; l < net.n_layers; ++l)
-        run_layer<NB, FWD, KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sgb, stage_wave,
-                                                     out, wave, lane, sig, cap, ci);
 }
 
-// One network behind its own prologue, nothing handed on (the interleaved-stream kernels; k_mlp_full).
+// One network behind its own prologue, nothing handed on (k_mlp_shade, k_mlp_full).
 template <int NB, bool FWD, int KS_IN, int HID, int WAVES, typename Cap = NoCapture>
 __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restrict__ wpack, const float* bias_lds,
                                         char* wring, opx8 (&Bcur)[KS_REG][NB], const op_t* stage_wave,
@@ -1279,15 +1026,10 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
 
 // Issues the first two weight chunks into ring slots 0 and 1 and synchronises (also publishes the staging rows).
 // THREE: the phase-separated stream (plain-mode kernels) starts with all three ring slots filled.
-#ifdef MP_EXP_NOPP
-constexpr bool PROLOGUE_THREE = false;
-#else
-constexpr bool PROLOGUE_THREE = true;
-#endif
-// Round 6: in two halves.  prologue_issue() goes to the HEAD of a tile, before the tile's inputs are fetched and encoded (the ring is
+// In two halves.  prologue_issue() goes to the HEAD of a tile, before the tile's inputs are fetched and encoded (the ring is
 // free there: every wave has passed the barrier behind the previous tile's last M phase), prologue_wait() behind them -- the first
 // chunks' DMA latency then runs beside the worklist -> position loads and the Fourier features instead of after them.
-template <int KS_IN, int WAVES, bool THREE = PROLOGUE_THREE>
+template <int KS_IN, int WAVES, bool THREE = true>
 __device__ __forceinline__ void prologue_issue(const NetDesc& net, const char* __restrict__ wpack, char* wring, int wave, int lane) {
     issue_chunk<KS_IN, WAVES>(wpack, wring, 0, wave, lane);
     if (net.total_chunks > 1) issue_chunk<KS_IN, WAVES>(wpack, wring, 1, wave, lane);
@@ -1299,7 +1041,7 @@ __device__ __forceinline__ void prologue_wait() {
     dma_wait_all();
     __syncthreads();
 }
-template <int KS_IN, int WAVES, bool THREE = PROLOGUE_THREE>
+template <int KS_IN, int WAVES, bool THREE = true>
 __device__ __forceinline__ void prologue(const NetDesc& net, const char* __restrict__ wpack, char* wring, int wave,
                                          int lane) {
     prologue_issue<KS_IN, WAVES, THREE>(net, wpack, wring, wave, lane);
@@ -1308,7 +1050,7 @@ __device__ __forceinline__ void prologue(const NetDesc& net, const char* __restr
 // The same two halves at the head of a tile of a kernel on the continuous stream: only the workgroup's first tile (and every tile
 // of a pack that cannot wrap) runs them.  rs.fed is uniform over the workgroup, so the barrier inside is too.  The barrier also
 // publishes what the workgroup wrote to LDS before its first tile (bias table); per-tile LDS inputs are per-wave and need none.
-template <int KS_IN, int WAVES, bool THREE = PROLOGUE_THREE>
+template <int KS_IN, int WAVES, bool THREE = true>
 __device__ __forceinline__ void stream_prologue_issue(const RingStream& rs, const NetDesc& net, const char* __restrict__ wpack,
                                                       char* wring, int wave, int lane) {
     if (!rs.fed) prologue_issue<KS_IN, WAVES, THREE>(net, wpack, wring, wave, lane);

@@ -205,9 +205,6 @@ __device__ __forceinline__ void tf_issue(const Ctx& cx, int k, int slot, int wl)
     const char* s = mp::uniform_ptr(cx.wpack) + (size_t)src * CH_BYTES + wu * TILE_B;
     const unsigned d = __builtin_amdgcn_readfirstlane(mp::lds_offset(cx.ring)) + __builtin_amdgcn_readfirstlane(slot) * CH_BYTES +
                        wu * TILE_B;
-#if TF_EXP & 8
-    return;
-#endif
     if (has_reg) {
 #pragma unroll
         for (int i = 0; i < 32 / NW; ++i) mp::lds_dma_16(s + i * NW * TILE_B, cx.lane * 16, d + i * NW * TILE_B);
@@ -218,27 +215,11 @@ __device__ __forceinline__ void tf_issue(const Ctx& cx, int k, int slot, int wl)
     }
 }
 
-// ablation switches (timing experiments only: results are wrong), -DTF_EXP=<bits>: 1 no stash stores, 2 no MFMAs, 4 no A-fragment
-// LDS reads, 8 no weight DMA, 16 no stash loads (the activation code sees zeros)
-#ifndef TF_EXP
-#define TF_EXP 0
-#endif
-#if TF_EXP & 2
-#define TF_MFMA(a, b, c) (c)
-#else
-#define TF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-#endif
+__device__ __forceinline__ f32x4 tf_mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 #ifndef TF_QD
 #define TF_QD 3      // depth of the A-fragment register queue (K steps)
 #endif
 
-__device__ __forceinline__ bf16x8 lds_frag(const char* p) {
-#if TF_EXP & 4
-    return __builtin_bit_cast(bf16x8, (f32x4){1e-3f, 2e-3f, 1e-3f, 2e-3f});
-#else
-    return *(const bf16x8*)p;
-#endif
-}
 // the products of one chunk: acc[mb] (16 rows x 16 points) += W tile . activations, K = 256 from registers (+ 64 from the input)
 template <bool HAS_IN>
 __device__ __forceinline__ void tf_mma(const Ctx& cx, bool use_reg, bool use_in, const BReg& B, f32x4 (&acc)[2]) {
@@ -251,23 +232,23 @@ __device__ __forceinline__ void tf_mma(const Ctx& cx, bool use_reg, bool use_in,
 #pragma unroll
         for (int k0 = 0; k0 < TF_QD - 1; ++k0)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) q[k0][t] = lds_frag(slot + (((t >> 1) * 8 + k0) * 2 + (t & 1)) * TILE_B);
+            for (int t = 0; t < 4; ++t) q[k0][t] = *(const bf16x8*)(slot + (((t >> 1) * 8 + k0) * 2 + (t & 1)) * TILE_B);
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             if (ks + TF_QD - 1 < 8) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    q[(ks + TF_QD - 1) % TF_QD][t] = lds_frag(slot + (((t >> 1) * 8 + ks + TF_QD - 1) * 2 + (t & 1)) * TILE_B);
+                    q[(ks + TF_QD - 1) % TF_QD][t] = *(const bf16x8*)(slot + (((t >> 1) * 8 + ks + TF_QD - 1) * 2 + (t & 1)) * TILE_B);
             }
             __builtin_amdgcn_sched_barrier(0);
             const bf16x8 (&a)[4] = q[ks % TF_QD];   // a[0] = hi of row block 0, a[1] = lo, a[2] = hi of row block 1, a[3] = lo
             // the small terms first; the two row blocks alternate so that no MFMA waits for the one before it
-            acc[0] = TF_MFMA(a[1], B.h[ks], acc[0]);
-            acc[1] = TF_MFMA(a[3], B.h[ks], acc[1]);
-            acc[0] = TF_MFMA(a[0], B.l[ks], acc[0]);
-            acc[1] = TF_MFMA(a[2], B.l[ks], acc[1]);
-            acc[0] = TF_MFMA(a[0], B.h[ks], acc[0]);
-            acc[1] = TF_MFMA(a[2], B.h[ks], acc[1]);
+            acc[0] = tf_mfma(a[1], B.h[ks], acc[0]);
+            acc[1] = tf_mfma(a[3], B.h[ks], acc[1]);
+            acc[0] = tf_mfma(a[0], B.l[ks], acc[0]);
+            acc[1] = tf_mfma(a[2], B.l[ks], acc[1]);
+            acc[0] = tf_mfma(a[0], B.h[ks], acc[0]);
+            acc[1] = tf_mfma(a[2], B.h[ks], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -283,12 +264,12 @@ __device__ __forceinline__ void tf_mma(const Ctx& cx, bool use_reg, bool use_in,
                     ah[mb] = *(const bf16x8*)(slot + CH_REG + ((mb * 2 + ks) * 2 + 0) * TILE_B);
                     al[mb] = *(const bf16x8*)(slot + CH_REG + ((mb * 2 + ks) * 2 + 1) * TILE_B);
                 }
-                acc[0] = TF_MFMA(al[0], bh, acc[0]);
-                acc[1] = TF_MFMA(al[1], bh, acc[1]);
-                acc[0] = TF_MFMA(ah[0], bl, acc[0]);
-                acc[1] = TF_MFMA(ah[1], bl, acc[1]);
-                acc[0] = TF_MFMA(ah[0], bh, acc[0]);
-                acc[1] = TF_MFMA(ah[1], bh, acc[1]);
+                acc[0] = tf_mfma(al[0], bh, acc[0]);
+                acc[1] = tf_mfma(al[1], bh, acc[1]);
+                acc[0] = tf_mfma(ah[0], bl, acc[0]);
+                acc[1] = tf_mfma(ah[1], bl, acc[1]);
+                acc[0] = tf_mfma(ah[0], bh, acc[0]);
+                acc[1] = tf_mfma(ah[1], bh, acc[1]);
             }
         }
     }
@@ -316,13 +297,12 @@ __device__ __forceinline__ void wait_vm_rt(int n) {
 }
 __device__ __forceinline__ void touch4(const f32x4& v) { asm volatile("" ::"v"(v)); }
 
-// EARLY_DMA (round 6; the value-only kernel -- its activation code issues no stores; -DMP_DMA_LATE: the round-5 schedule): the weight DMA is issued by the EARLY waves
+// EARLY_DMA (the value-only kernel -- its activation code issues no stores): the weight DMA is issued by the EARLY waves
 // at the tail of their activation code -- where they otherwise wait at the barrier for the late waves, whose [barrier, DMA issue,
 // activation, products] chain is the chunk's critical path.  Behind barrier(ci - 1) slot (ci - 1) % 3 is free: chunk ci + 2 goes
 // there, and the issuing wave waits for it one iteration later (counted: everything but the prefetch loads just issued).
-// DMA_MODE 2 (-DMP_DMA_SPLIT): both halves issue, NW = 8 piece dealing -- the late waves their pieces of chunk ci + 3 behind the barrier,
-// the early waves theirs of chunk ci + 2 at their tail.
-template <class Epi, int MAXC, bool HAS_IN, int DMA_MODE = 0>
+// mp_tf_sdf_val -3...5 % (profiles/r06_early_dma_ab.txt).  Every other kernel: the late waves issue, behind their barrier.
+template <class Epi, int MAXC, bool HAS_IN, bool EARLY_DMA = false>
 __device__ __forceinline__ void tf_layer(Ctx& cx, Epi& ep, int n_chunk, bool use_reg, bool use_in, BReg& Bcur, BReg& Bnext) {
     int npref = ep.prefetch(cx, 0);
     ep.rotate();
@@ -333,14 +313,11 @@ __device__ __forceinline__ void tf_layer(Ctx& cx, Epi& ep, int n_chunk, bool use
             ep.init(cx, c, acc);
             tf_mma<HAS_IN>(cx, use_reg, use_in, Bcur, acc);
             ep.touch();
-            constexpr bool EARLY_DMA = DMA_MODE != 0;
             if (cx.late) {
-                if constexpr (DMA_MODE != 1) wait_vm_rt(npref);
+                if constexpr (!EARLY_DMA) wait_vm_rt(npref);
                 __syncthreads();
-                if constexpr (DMA_MODE == 0) {
+                if constexpr (!EARLY_DMA) {
                     if (cx.ci + RING < cx.n_total) tf_issue<4>(cx, cx.ci + RING, cx.ring_pos, cx.wave - 4);
-                } else if constexpr (DMA_MODE == 2) {
-                    if (cx.ci + RING < cx.n_total) tf_issue<8>(cx, cx.ci + RING, cx.ring_pos, cx.wave);
                 }
             }
             npref = c + 1 < n_chunk ? ep.prefetch(cx, c + 1) : 0;
@@ -349,10 +326,8 @@ __device__ __forceinline__ void tf_layer(Ctx& cx, Epi& ep, int n_chunk, bool use
             if constexpr (EARLY_DMA) {
                 if (!cx.late) {
                     wait_vm_rt(npref);
-                    if (cx.ci >= 1 && cx.ci + RING - 1 < cx.n_total) {
-                        if constexpr (DMA_MODE == 2) tf_issue<8>(cx, cx.ci + RING - 1, cx.ring_pos == 0 ? RING - 1 : cx.ring_pos - 1, cx.wave);
-                        else tf_issue<4>(cx, cx.ci + RING - 1, cx.ring_pos == 0 ? RING - 1 : cx.ring_pos - 1, cx.wave);
-                    }
+                    if (cx.ci >= 1 && cx.ci + RING - 1 < cx.n_total)
+                        tf_issue<4>(cx, cx.ci + RING - 1, cx.ring_pos == 0 ? RING - 1 : cx.ring_pos - 1, cx.wave);
                 }
             }
             if (!cx.late) __syncthreads();
@@ -368,15 +343,8 @@ __device__ __forceinline__ void tf_layer(Ctx& cx, Epi& ep, int n_chunk, bool use
     }
 }
 
-#if TF_EXP & 16
-__device__ __forceinline__ f32x4 ld4g(const float* p) { return (f32x4){0.01f, 0.02f, 0.03f, 0.04f}; }
-#else
 __device__ __forceinline__ f32x4 ld4g(const float* p) { return *(const f32x4*)p; }
-#endif
 __device__ __forceinline__ void st4g(float* p, f32x4 v) {
-#if TF_EXP & 1
-    if (v[0] == 123.456f)
-#endif
         *(f32x4*)p = v;
 }
 // 1 - sigma'(Z) = exp(-100 softplus(Z)) from the stored activation x = scale * softplus(Z), kx = 100 log2(e) / scale
@@ -698,13 +666,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_val(TfValArgs a) {
             ep.linear = l == 8;
             ep.sdf_out = a.sdf_out;
             ep.id = id;
-#if defined(MP_DMA_SPLIT)
-            tf_layer<EpiV, 8, true, 2>(cx, ep, l == 8 ? 1 : 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
-#elif !defined(MP_DMA_LATE)
-            tf_layer<EpiV, 8, true, 1>(cx, ep, l == 8 ? 1 : 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
-#else
-            tf_layer<EpiV, 8, true>(cx, ep, l == 8 ? 1 : 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
-#endif
+            tf_layer<EpiV, 8, true, true>(cx, ep, l == 8 ? 1 : 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
         }
         __syncthreads();      // the ring and the input blocks are rebuilt by the next tile
     }

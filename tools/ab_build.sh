@@ -1,5 +1,5 @@
 #!/bin/bash
-# Builds ablation side libraries (CPU container, hipcc cross-compiles):  tools/ab_build.sh name1:-DFLAG1 name2:"-DA -DB" ...
+# Builds ablation side libraries (CPU container, hipcc cross-compiles):  tools/ab_build.sh name1:-D<SWITCH> name2:"-D<ONE> -D<TWO>" ...
 # -> multiply_amd/ab_libs/libmultiply_hip_<name>.so ; run them on the GPU box with tools/ab_run.sh
 cd "$(dirname "$0")/.."
 for spec in "$@"; do
