@@ -315,6 +315,20 @@ int mp_composite(int n_rays, int n_person, int n_z, const int* const* inv_index,
                  const float* const* sdf, const float* const* rgb, const float* const* normal, const float* beta,
                  const float* bg_rgb, float* rgb_values, float* fg_rgb_values, float* normal_values, float* acc_map,
                  float* acc_person, float* bg_T, void* stream);
+/* Geometry of the same merge, from the same tables (no rgb / normal): with ts, te the ends of a sample, tm their mean,
+ * fe = sigma (te - ts), E the free energy in front of it in merged order, w = (1-exp(-fe)) exp(-E), and E0 / w0 the same with
+ * the person's own samples only ("solo": the person as if rendered alone); L = -ln(1 - level), level in (0,1):
+ *   depth [R] = sum w tm (unnormalised, goes with acc_map)          depth_person [R][P] = sum_i w tm (with acc_person)
+ *   depth_level [R] = ts + (te-ts) clamp((L-E)/fe, 0, 1) of the FIRST sample in merged order with E + fe >= L (the minimum
+ *                     of the key (te, person) over the samples that satisfy it), -1 if none; front_person [R] its column, or -1
+ *   acc_solo [R][P] = sum_i w0    depth_solo [R][P] = sum_i w0 tm    depth_solo_level [R][P]: the level rule on person n alone
+ * Depths are distances along the ray in the units of z; rays a person does not hit give 0 / -1 in its column.  Any output
+ * pointer may be NULL (skipped).  No atomics, fixed summation order: bit-identical from run to run.
+ * Status: -1 n_person > 8, -2 LDS limit, -3 level outside (0,1) (no launch), 0 for n_rays <= 0. */
+int mp_composite_geometry(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                          const float* const* sdf, const float* beta, float level, float* depth, float* depth_person,
+                          float* depth_level, int* front_person, float* acc_solo, float* depth_solo,
+                          float* depth_solo_level, void* stream);
 
 
 /* ---- fp32 training path (layer-wise forward with stash + hand-written backward) ----------------------------------

@@ -158,14 +158,46 @@ def get_depth_order_loss(model, inputs, epoch, loss_opt=None, meshes=None, draws
     return order, sil, inter
 
 
-def frame_instance_masks(model, inputs, use_smpl_mesh, res_up=2):
+def volume_depth_maps(model, inputs, level=0.5):
+    """The per-person depth maps of one frame straight from the volume renderer, no mesh: ONE sampling + shading pass over the
+    frame's `uv` (all H*W pixels, row-major; the pass render_views makes) and one mp_composite_geometry launch.
+    -> (list of P (H,W) maps, (P,H,W) opacities): person p's UNOCCLUDED depth at which its own opacity reaches `level`
+    (depth_person_solo_level_list), -1 = empty like the z-buffers' maps, and its unoccluded opacity (acc_person_solo_list).
+    The depths are distances t along the pixel's ray in the model's units: along one pixel's ray they order like z-depths, so
+    front_depth / instance_masks / depth_order_loss take them as they are; the z-depth of the renderer's maps is
+    t * (d . camera axis) / scale with d the ray's unit direction, camera axis = inputs['pose'][0, :3, 2] and scale the
+    SMPL scale smpl_params[0, 0, 0] (get_renderer)."""
+    assert not model.training, "volume_depth_maps is an eval-mode entry point"
+    H, W = int(inputs["img_size"][0]), int(inputs["img_size"][1])
+    with torch.no_grad():
+        model._forward_eval(inputs, -1, False, composite=False)
+        cx = model._last["cx"]
+        assert cx["R"] == H * W, "inputs['uv'] must hold every pixel of the (H, W) frame"
+        geo = model._composite_geometry(cx, cx["persons"], level=level, solo_only=True)
+        P = len(cx["persons"])
+        depth = geo["depth_person_solo_level_list"].t().reshape(P, H, W)
+        acc = geo["acc_person_solo_list"].t().reshape(P, H, W).contiguous()
+    return [depth[p].contiguous() for p in range(P)], acc
+
+
+def frame_instance_masks(model, inputs, use_smpl_mesh, res_up=2, source="mesh", level=0.5):
     """One frame of get_instance_mask (multiply_model.py:790-898, :860-870): the per-person z-buffers of the SMPL meshes
     (epochs <= 190) or of the posed canonical meshes -> instance masks (P,H,W) bool, depth maps, and the 27 projected key
-    points per person (P,27,2) int32 that the SAM prompts are built from."""
+    points per person (P,27,2) int32 that the SAM prompts are built from.
+    source='volume': the per-person maps come from the volume renderer instead (volume_depth_maps at opacity `level`: depths
+    along the pixel's ray, which order like z-depths); no mesh is extracted, use_smpl_mesh / res_up are not read, and
+    inputs['uv'] must hold every pixel of the frame."""
+    assert source in ("mesh", "volume"), source
     with torch.no_grad():
-        renderer = get_renderer(inputs)
-        vs, fs, outs = posed_meshes(model, inputs, use_smpl_mesh=use_smpl_mesh, res_up=res_up)
-        depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(vs, fs)]
+        if source == "volume":
+            depth, _ = volume_depth_maps(model, inputs, level)
+            sp = inputs["smpl_params"]
+            outs = [server(sp[:, p, 0], inputs["smpl_trans"][:, p], inputs["smpl_pose"][:, p], inputs["smpl_shape"][:, p])
+                    for p, server in enumerate(model.smpl_server_list)]
+        else:
+            renderer = get_renderer(inputs)
+            vs, fs, outs = posed_meshes(model, inputs, use_smpl_mesh=use_smpl_mesh, res_up=res_up)
+            depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(vs, fs)]
         Pm = inputs["P"][0].double()
         kps = []
         for out in outs:

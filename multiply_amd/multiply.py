@@ -17,7 +17,10 @@ Extensions that do not exist in the reference (all optional, defaults reproduce 
     reference's trimesh box, multiply.py:208-214, 256-266, is third-party code);
   * self.convergence_group : number of consecutive rays that share the sampler's convergence vote
     (ray_sampler.py:137).  None = the whole call, exactly like the reference; set it to pixel_per_batch to render a
-    whole frame in one call with the results of the reference's chunked loop (multiply_model.py:1051-1055).
+    whole frame in one call with the results of the reference's chunked loop (multiply_model.py:1051-1055);
+  * self.render_geometry / self.geometry_level : eval mode only, the output dict also carries the volume-rendered depth maps
+    (depth_values, depth_person_list, depth_level_values, front_person, acc_person_solo_list, depth_person_solo_list,
+    depth_person_solo_level_list: _composite_geometry).  Off by default: exactly the reference's keys.
 """
 import ctypes as C
 import os
@@ -36,6 +39,11 @@ from .sampler import PointInSpace
 
 
 class Multiply(nn.Module):
+    # eval mode only: the output dict also carries the volume-rendered depth maps (_composite_geometry); geometry_level is the
+    # opacity in (0,1) at which depth_level_values / front_person / depth_person_solo_level_list are read off the ray
+    render_geometry = False
+    geometry_level = 0.5
+
     def __init__(self, opt, betas_path, smpl_tables=None, gender_list=None):
         super().__init__()
         hip.require_device()
@@ -541,14 +549,46 @@ class Multiply(nn.Module):
                            normal_values, acc_map, acc_person, bg_T, hip.stream())
         out = {"acc_map": acc_map, "acc_person_list": acc_person, "rgb_values": rgb_values,
                "fg_rgb_values": fg_rgb_values, "normal_values": normal_values}
+        if self.render_geometry and not self.training:
+            out.update(self._composite_geometry(cx, persons, (t_inv, t_z, t_sdf)))
         return out, bg_T, (t_inv, t_z, t_sdf, t_rgb, t_nrm)
+
+    def _composite_geometry(self, cx, persons, tables=None, level=None, solo_only=False):
+        """The depth outputs of the same merge (render_geometry; csrc/composite.hip k_composite_geometry), a second launch on
+        the compositing's tables: the merged depth sum Σ w t (unnormalised like acc_map) and its per-person split, the depth at
+        which the ray's opacity reaches `level` (geometry_level) with the column of the person that owns that point, and every
+        person's unoccluded ("solo": rendered alone) opacity, depth sum and level depth.  Depths are distances along the ray
+        in the units of the samples, -1 = the level is never reached; columns follow acc_person_list.  solo_only: the merged
+        outputs are not computed (NULL pointers)."""
+        dev, R, per, P = cx["dev"], cx["R"], cx["per"], len(persons)
+        f32 = dict(dtype=torch.float32, device=dev)
+        NZ = self.ray_sampler.N_samples + self.ray_sampler.N_samples_extra + 2
+        if tables is None:
+            tables = tuple(hip.device_ints([per[p][key].data_ptr() for p in persons], dev) for key in ("inv_index", "zfinal", "sdf"))
+        t_inv, t_z, t_sdf = tables
+        level = float(self.geometry_level if level is None else level)
+        acc_solo = torch.empty(R, P, **f32); depth_solo = torch.empty(R, P, **f32); depth_solo_level = torch.empty(R, P, **f32)
+        depth = depth_person = depth_level = front = None
+        if not solo_only:
+            depth = torch.empty(R, **f32); depth_person = torch.empty(R, P, **f32)
+            depth_level = torch.empty(R, **f32); front = torch.empty(R, dtype=torch.int32, device=dev)
+        with self._ph("composite_geometry"):
+            hip.lib().mp_composite_geometry(R, P, NZ, t_inv, t_z, t_sdf, cx["beta"], level, depth, depth_person, depth_level,
+                                            front, acc_solo, depth_solo, depth_solo_level, hip.stream())
+        out = {"acc_person_solo_list": acc_solo, "depth_person_solo_list": depth_solo,
+               "depth_person_solo_level_list": depth_solo_level}
+        if not solo_only:
+            out.update({"depth_values": depth, "depth_person_list": depth_person, "depth_level_values": depth_level,
+                        "front_person": front})
+        return out
 
     def render_views(self, input, ids=None, canonical_pose=False):
         """Every view the reference's caller renders of one frame -- all persons (id -1) and each person alone
         (multiply_model.py:982-989, 1183-1190: P + 1 full chunk loops of forward(s, id)) -- from ONE sampling + shading
         pass: a person's samples do not depend on who else is rendered (multiply.py:254-423 loops persons independently),
         so view `id` is a compositing pass over that person's arrays plus the shared background.
-        Returns {id: the eval output dict of forward(input, id)}; bit-identical to the separate calls."""
+        Returns {id: the eval output dict of forward(input, id)}; bit-identical to the separate calls.  With render_geometry every
+        view carries the depth keys too; view -1's solo columns are then what the single-person views composite."""
         assert not self.training, "render_views is an eval-mode entry point"
         with torch.no_grad():
             samples = self._forward_eval(input, -1, canonical_pose, composite=False)
