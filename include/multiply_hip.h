@@ -414,6 +414,23 @@ int mp_tr_composite_bwd(int n_rays, int n_person, int n_z, const int* const* inv
                         const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
                         const float* d_rgb_values, const float* d_acc, const float* d_acc_person, float* const* d_sdf,
                         float* const* d_rgb, float* d_bg_rgb, float* d_beta, void* stream);
+/* adjoint of mp_composite_geometry's differentiable outputs w.r.t. sdf and beta (z is a constant, as in mp_tr_composite_bwd):
+ * d_sdf[p] += , d_beta += .  Any upstream pointer may be NULL (term skipped); all NULL: returns 0, no launch.
+ * In mp_composite_geometry's notation (Es / w0 = E / w in the person's own list), for sample j of person p on ray r:
+ *   merged sums, dw_i = (d_depth[r] + d_depth_person[r][p(i)]) tm_i :  dfe_j += dw_j e^-E_j e^-fe_j - sum_{i behind j, merged} dw_i w_i
+ *   solo sums,  dws_i = d_acc_solo[r][p] + d_depth_solo[r][p] tm_i  :  dfe_j += dws_j e^-Es_j e^-fe_j - sum_{i>j, same person} dws_i w0_i
+ *   solo level depth, j* = the crossing sample the forward selects, f = (L-Es_j*)/fe_j*, g = d_depth_solo_level[r][p]; if fe_j* > 0
+ *   and 0 < f < 1:  dfe_i -= g (te-ts)_j* / fe_j* for i < j* of that person, dfe_j* -= g (te-ts)_j* / fe_j* f ; else nothing (no
+ *   crossing, clamped end).   d sigma_j = dfe_j (te-ts)_j -> d sdf, d beta through the Laplace density.
+ * depth_level / front_person (the merged crossing) have no adjoint.  The kernel accumulates: launch it after mp_tr_composite_bwd
+ * (which stores) on the same stream; rows of persons a ray misses and rows past the person's table are not touched.
+ * Status: -1 n_person > 8, -2 LDS limit, -3 level outside (0,1) (no launch), 0 for n_rays <= 0. */
+int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                                 const float* const* sdf, const float* beta, float level,
+                                 const float* d_depth /*[R]*/, const float* d_depth_person /*[R][P]*/,
+                                 const float* d_acc_solo /*[R][P]*/, const float* d_depth_solo /*[R][P]*/,
+                                 const float* d_depth_solo_level /*[R][P]*/,
+                                 float* const* d_sdf, float* d_beta, void* stream);
 /* background branch pieces (multiply.py:682-726) with per-ray depths zbg [R][NBG] */
 int mp_tr_bg_points(const float* dirs, const float* cam, const float* zbg, int R, int NBG, float radius, float* pts,
                     void* stream);

@@ -69,6 +69,23 @@ def depth_order_loss(depth_maps, org_sam_mask, epoch, depth_order_weight=0.005):
     return depth_order_weight * (1 - min(DEPTH_LOSS_MILESTONE, epoch) / DEPTH_LOSS_MILESTONE) * loss
 
 
+def ray_depth_order_loss(out, epoch, depth_order_weight=0.005, z_scale=None, sam_mask=None):
+    """depth_order_loss on the rays of one training forward instead of on (H,W) z-buffers: no mesh.  `out` is forward_train's dict
+    with Multiply.train_geometry on; person p's map is column p of out['depth_person_solo_level_list'] (R,P): its unoccluded depth
+    along the ray at which its own opacity reaches geometry_level, -1 = never (the z-buffers' empty value, so the -1 -> 999
+    convention, the validity rules, the soft-plus and the fade are depth_order_loss's, unchanged).  The labels are out['sam_mask']
+    (R,P) logits unless `sam_mask` is passed.  Autograd carries the gradient into the depths, and from there the training node's
+    adjoint carries it to the SDF weights, density.beta and the body inputs.
+    z_scale (R,), optional: multiplies the depths that are >= 0.  z_scale = (d . pose[:3, 2]) / smpl_scale, d the ray's unit
+    direction, turns distances along the ray into the z-buffer's units, which is what the soft-plus of the mesh
+    path sees; along one ray the order is the same with or without it."""
+    D = out["depth_person_solo_level_list"]
+    if z_scale is not None:
+        D = torch.where(D >= 0, D * z_scale[:, None], D)
+    labels = out["sam_mask"] if sam_mask is None else sam_mask
+    return depth_order_loss([D[:, p] for p in range(D.shape[1])], labels, epoch, depth_order_weight)
+
+
 def gt_instance_map(org_sam_mask, n_person):
     """multiply_model.py:656-666: (H,W,3) colour-coded arg-max of [sigmoid(sam), 1 - sum] (the silhouette target)"""
     sam = torch.sigmoid(org_sam_mask).reshape(*org_sam_mask.shape[-3:])
@@ -219,7 +236,7 @@ def body_model_inputs(body_model_list, frame_idx):
 
 
 def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, it_per_loop, lr, loss_opt=None, depth_pose=False,
-                    depth_cond_zero=False, res_up=2):
+                    depth_cond_zero=False, res_up=2, depth_source="mesh"):
     """One frame of the trainer's depth-refinement stage (multiply_model.py:230-486): the persons' canonical meshes are
     extracted once, then `it_per_loop` Adam steps on the frame's body-model rows -- the translations only, or every body
     parameter with depth_pose -- minimise  render loss (a 512-ray training forward of the scene model) + depth-order loss
@@ -228,9 +245,18 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
     inputs: the frame's test item on the device (P, C, intrinsics, pose, smpl_params, idx, img_size, org_sam_mask), batch
     dimension 1.  sample_fn() -> (dict with uv (1,n,2), index_outside, sam_mask (1,n,P); dict with rgb (1,n,3)): the frame's
     pixel samples of one iteration (the reference draws them with weighted_sampling; datasets.SceneStore.sample does the
-    same from the resident frame).  Returns the per-iteration {'render_loss','depth_order_loss','interpenetration_loss'}."""
+    same from the resident frame).  Returns the per-iteration {'render_loss','depth_order_loss','interpenetration_loss'}.
+
+    depth_source='volume': no canonical mesh is extracted and no z-buffer is rendered.  The order term is ray_depth_order_loss of
+    the iteration's own training forward (Multiply.train_geometry, set for the loop and restored), on the iteration's rays and
+    their sam_mask labels, with z_scale from the rays' directions; its gradient reaches the body rows through the volume
+    renderer's own adjoint.  The interpenetration term needs meshes: a non-zero interpenetration_loss_weight raises ValueError."""
     from .mesh import canonical_mesh
+    assert depth_source in ("mesh", "volume"), depth_source
     loss_opt = loss_opt or {}
+    volume = depth_source == "volume"
+    if volume and loss_opt.get("interpenetration_loss_weight", 0.0) != 0:
+        raise ValueError("depth_source='volume' extracts no meshes: the interpenetration term (interpenetration_loss_weight != 0) needs them")
     params = list(p for bm in body_model_list for p in bm.parameters()) if depth_pose else [bm.transl.weight for bm in body_model_list]
     saved = [p.requires_grad for p in params]
     for p in params:
@@ -238,17 +264,20 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
     opt = torch.optim.Adam([{"params": params, "lr": lr}], lr=lr, eps=1e-8)
     frame = inputs["idx"].reshape(-1).long()
     scale = inputs["smpl_params"][:, :, 0]
-    renderer = get_renderer(inputs)
-    with torch.no_grad():
-        _, _, pose0 = body_model_inputs(body_model_list, frame)
-        meshes = []
-        for p in range(len(model.smpl_server_list)):
-            cond = pose0[0, p, 3:] * 0.0 if depth_cond_zero else pose0[0, p, 3:] / np.pi
-            meshes.append(canonical_mesh(model, p, cond=cond, res_up=res_up))
+    meshes = []
+    if not volume:
+        renderer = get_renderer(inputs)
+        with torch.no_grad():
+            _, _, pose0 = body_model_inputs(body_model_list, frame)
+            for p in range(len(model.smpl_server_list)):
+                cond = pose0[0, p, 3:] * 0.0 if depth_cond_zero else pose0[0, p, 3:] / np.pi
+                meshes.append(canonical_mesh(model, p, cond=cond, res_up=res_up))
     faces = [m["faces"][None] for m in meshes]
     fade = 1 - min(DEPTH_LOSS_MILESTONE, epoch) / DEPTH_LOSS_MILESTONE
-    was_training = model.training
+    was_training, was_geometry = model.training, model.train_geometry
     model.train()
+    if volume:
+        model.train_geometry = True
     history = []
     for _ in range(it_per_loop):
         smp_in, smp_tg = sample_fn()
@@ -259,19 +288,26 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
                     smpl_params=inputs["smpl_params"], current_epoch=epoch, **smp_in)
         out = model(minp, cond_zero_shit=True) if depth_cond_zero else model(minp)
         render = loss_fn(out, smp_tg)["loss"]
-        verts = []
-        for p, server in enumerate(model.smpl_server_list):
-            so = server(scale[:, p], trans[:, p], pose[:, p], shape[:, p])
-            verts.append((1 / scale[:, p].squeeze()) * deformed_mesh_vertices(model, meshes[p]["vertices"][None], so["smpl_tfs"], p))
-        depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(verts, faces)]
-        inter = interpenetration_loss(verts, faces, mesh_index_mode=model.mesh_index_mode)
-        inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
-        order = depth_order_loss(depth, inputs["org_sam_mask"], epoch, loss_opt.get("depth_order_weight", 0.005))
+        if volume:
+            dirs = model._last_train.cx["dirs"]
+            z_scale = (dirs @ inputs["pose"][0, :3, 2].to(dirs)) / scale[0, 0]
+            order = ray_depth_order_loss(out, epoch, loss_opt.get("depth_order_weight", 0.005), z_scale=z_scale)
+            inter = torch.zeros(1, device=dirs.device)
+        else:
+            verts = []
+            for p, server in enumerate(model.smpl_server_list):
+                so = server(scale[:, p], trans[:, p], pose[:, p], shape[:, p])
+                verts.append((1 / scale[:, p].squeeze()) * deformed_mesh_vertices(model, meshes[p]["vertices"][None], so["smpl_tfs"], p))
+            depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(verts, faces)]
+            inter = interpenetration_loss(verts, faces, mesh_index_mode=model.mesh_index_mode)
+            inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
+            order = depth_order_loss(depth, inputs["org_sam_mask"], epoch, loss_opt.get("depth_order_weight", 0.005))
         (inter.sum() + order + render.sum()).backward()
         opt.step()
         history.append({"render_loss": render.detach().reshape(()), "depth_order_loss": order.detach().reshape(()),
                         "interpenetration_loss": inter.detach().reshape(())})
     for p, r in zip(params, saved):
         p.requires_grad_(r)
+    model.train_geometry = was_geometry
     model.train(was_training)
     return history

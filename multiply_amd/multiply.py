@@ -20,7 +20,9 @@ Extensions that do not exist in the reference (all optional, defaults reproduce 
     whole frame in one call with the results of the reference's chunked loop (multiply_model.py:1051-1055);
   * self.render_geometry / self.geometry_level : eval mode only, the output dict also carries the volume-rendered depth maps
     (depth_values, depth_person_list, depth_level_values, front_person, acc_person_solo_list, depth_person_solo_list,
-    depth_person_solo_level_list: _composite_geometry).  Off by default: exactly the reference's keys.
+    depth_person_solo_level_list: _composite_geometry).  Off by default: exactly the reference's keys;
+  * self.train_geometry : training mode only, the same seven keys on the training forward's rays, differentiable except
+    depth_level_values / front_person (train.TrainGraph, mp_tr_composite_geometry_bwd).  Off by default.
 """
 import ctypes as C
 import os
@@ -43,6 +45,10 @@ class Multiply(nn.Module):
     # opacity in (0,1) at which depth_level_values / front_person / depth_person_solo_level_list are read off the ray
     render_geometry = False
     geometry_level = 0.5
+    # training mode only: forward_train's dict carries the same seven keys for the iteration's rays, on the training node: the sums
+    # and the per-person solo level depth are differentiable (sdf weights, density.beta, and the body inputs through the pose path);
+    # depth_level_values / front_person are not.  geometry_level is shared.  Not built for person-sharded training.
+    train_geometry = False
 
     def __init__(self, opt, betas_path, smpl_tables=None, gender_list=None):
         super().__init__()

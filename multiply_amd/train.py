@@ -1057,6 +1057,8 @@ class TrainGraph:
         self.reg_items, self.reg_losses = [], (None, None)
         self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the regularisers (pose optimisation)
         self.reg_surf = {}              # person -> (d tfs [24][16], d posed vertices [V][3]) of the surface term (pose optimisation)
+        # Multiply.train_geometry: the node also returns the volume-rendered depths of its rays (GEOMETRY_KEYS), with an adjoint
+        self.geometry = bool(model.training and getattr(model, "train_geometry", False))
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def run(self):
@@ -1275,9 +1277,26 @@ class TrainGraph:
                        normal_values, acc_map, acc_person, bg_T, hip.stream())
         grad_theta = torch.cat([rec["gth"] for rec in self.composited], 0)[None]               # multiply.py:565
         self.bg_T = bg_T
+        outs = (rgb_values, normal_values, acc_map, acc_person, grad_theta)
         if self.reg_items:
-            return (rgb_values, normal_values, acc_map, acc_person, grad_theta) + self.reg_losses
-        return rgb_values, normal_values, acc_map, acc_person, grad_theta
+            outs = outs + self.reg_losses
+        if self.geometry:
+            outs = outs + self._composite_geometry()
+        return outs
+
+    def _composite_geometry(self):
+        """train_geometry: mp_composite_geometry on the compositing's own tables -> the tensors of GEOMETRY_KEYS, in that order"""
+        cx = self.cx
+        dev, R, P = cx["dev"], cx["R"], len(self.composited)
+        f32 = dict(dtype=F32, device=dev)
+        self.level = float(self.model.geometry_level)
+        depth = torch.empty(R, **f32); depth_person = torch.empty(R, P, **f32); acc_solo = torch.empty(R, P, **f32)
+        depth_solo = torch.empty(R, P, **f32); depth_solo_level = torch.empty(R, P, **f32)
+        depth_level = torch.empty(R, **f32); front = torch.empty(R, dtype=torch.int32, device=dev)
+        t_inv, t_z, t_sdf = self.tabs[:3]
+        hip.lib().mp_composite_geometry(R, P, self.NZ, t_inv, t_z, t_sdf, cx["beta"], self.level, depth, depth_person, depth_level,
+                                        front, acc_solo, depth_solo, depth_solo_level, hip.stream())
+        return depth, depth_person, acc_solo, depth_solo, depth_solo_level, depth_level, front
 
     # ---- the two optional regularisers (multiply.py:336-394) -----------------------------------------------------------------
     def _regularisers_forward(self):
@@ -1375,14 +1394,14 @@ class TrainGraph:
                     self.reg_dcond[q] = dcond if q not in self.reg_dcond else self.reg_dcond[q] + dcond
 
     # ---- backward -----------------------------------------------------------------------------------------------
-    def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None):
-        """-> {id(parameter): gradient}"""
+    def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None, d_geometry=None):
+        """-> {id(parameter): gradient}.  d_geometry: the upstream gradients of GEOMETRY_KEYS[:5] (train_geometry), None = no term"""
         m, dev = self.model, self.cx["dev"]
         self.ts.start_backward()                  # this sweep's own accumulators / gradient buffer (TrainState.start_backward)
         if self.reg_items:                        # before any finish_group retires a network's accumulators
             self._regularisers_backward(d_ssl, d_zpl)
         self.zp = _ZP[0] = hip.ZeroPool(dev)      # this sweep's zero-initialised tensors: views of one zero-filled block
-        dsdf_l, drgb_l, d_bg_rgb, d_beta = self._composite_backward(d_rgb_values, d_acc_map, d_acc_person)
+        dsdf_l, drgb_l, d_bg_rgb, d_beta = self._composite_backward(d_rgb_values, d_acc_map, d_acc_person, d_geometry)
         self.grads, self.pose_grads = {}, {}
         # data-parallel training: buckets of retired gradients are all-reduced while the sweep goes on (parallel.BucketedGradientSync)
         sync = self.sync = getattr(m, "grad_bucket_sync", None)
@@ -1421,8 +1440,9 @@ class TrainGraph:
             prms = [prm for o in objs for prm in o.params()]
             self.sync.retire(prms, [grads[id(prm)] for prm in prms])
 
-    def _composite_backward(self, d_rgb_values, d_acc_map, d_acc_person):
-        """adjoint of mp_composite -> per composited person d sdf and d rgb, d bg_rgb [R][3], d beta"""
+    def _composite_backward(self, d_rgb_values, d_acc_map, d_acc_person, d_geometry=None):
+        """adjoint of mp_composite (and, train_geometry, of mp_composite_geometry: accumulated onto the same d sdf / d beta)
+        -> per composited person d sdf and d rgb, d bg_rgb [R][3], d beta"""
         cx, zp = self.cx, self.zp
         dev, R = cx["dev"], cx["R"]
         P = len(self.composited)
@@ -1438,6 +1458,12 @@ class TrainGraph:
         t_dsdf, t_drgb = _table(dsdf_l, dev), _table(drgb_l, dev)
         hip.lib().mp_tr_composite_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, cx["beta"], self.bg_rgb, d_rgb_values, d_acc_map,
                                       d_acc_person, t_dsdf, t_drgb, d_bg_rgb, d_beta, hip.stream())
+        if d_geometry is not None and any(g is not None for g in d_geometry):
+            # after the store above, on the same stream: the kernel adds (a missing upstream gradient is a NULL pointer)
+            d_depth, d_depth_person, d_acc_solo, d_depth_solo, d_depth_solo_level = (
+                None if g is None else g.contiguous().float() for g in d_geometry)
+            hip.lib().mp_tr_composite_geometry_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, cx["beta"], self.level, d_depth, d_depth_person,
+                                                   d_acc_solo, d_depth_solo, d_depth_solo_level, t_dsdf, d_beta, hip.stream())
         return dsdf_l, drgb_l, d_bg_rgb, d_beta
 
     def _person_backward(self, p, dsdf, drgb, dgth):
@@ -1516,13 +1542,22 @@ class _TrainFn(torch.autograd.Function):
         ctx.graph, ctx.params = graph, params
         ctx.body = (smpl_pose, smpl_trans, smpl_shape)
         outs = graph.run()
-        ctx.mark_non_differentiable(outs[1])          # normal_values: no loss term reads it (loss.py:108-177)
+        if graph.geometry:
+            # the unused ones of the geometry outputs must arrive as None (a NULL pointer skips the term), not as zero tensors
+            ctx.set_materialize_grads(False)
+            ctx.mark_non_differentiable(outs[1], *outs[-2:])      # + depth_level_values, front_person: no adjoint
+        else:
+            ctx.mark_non_differentiable(outs[1])      # normal_values: no loss term reads it (loss.py:108-177)
         return outs
 
     @staticmethod
-    def backward(ctx, d_rgb, d_nrm, d_acc, d_accp, d_gth, d_ssl=None, d_zpl=None):
+    def backward(ctx, d_rgb, d_nrm, d_acc, d_accp, d_gth, *rest):
         graph = ctx.graph
-        g = graph.backward(d_rgb, d_acc, d_accp, d_gth, d_ssl, d_zpl)
+        d_geo = None
+        if graph.geometry:
+            rest, d_geo = rest[:-len(GEOMETRY_KEYS)], rest[-len(GEOMETRY_KEYS):-2]
+        d_ssl, d_zpl = rest if rest else (None, None)
+        g = graph.backward(d_rgb, d_acc, d_accp, d_gth, d_ssl, d_zpl, d_geo)
         body = [None, None, None]
         if graph.pose_grad:
             sl = ((4, 76), (1, 4), (76, 86))
@@ -1535,11 +1570,20 @@ class _TrainFn(torch.autograd.Function):
         return (None, *body) + tuple(g.get(id(p)) for p in ctx.params)
 
 
+# Multiply.train_geometry: the keys of Multiply._composite_geometry in the order the training node returns them -- the five
+# differentiable ones, then the merged crossing (no adjoint)
+GEOMETRY_KEYS = ("depth_values", "depth_person_list", "acc_person_solo_list", "depth_person_solo_list",
+                 "depth_person_solo_level_list", "depth_level_values", "front_person")
+
+
 def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=False, draws=None, shard=None):
     """Multiply.forward with self.training == True.  Returns the reference's 19-key dict (multiply.py:566-588); the five
     tensors rgb_values / acc_map / acc_person_list / grad_theta (/ normal_values, not differentiable) hang off ONE autograd
-    node whose backward is the hand-written adjoint sweep."""
+    node whose backward is the hand-written adjoint sweep.  With model.train_geometry the dict also carries GEOMETRY_KEYS
+    (Multiply._composite_geometry's names and shapes, columns = acc_person_list's) off the same node."""
     epoch = int(input["current_epoch"])
+    if shard is not None and model.training and getattr(model, "train_geometry", False):
+        raise NotImplementedError("train_geometry is not built for person-sharded training (shard=)")
     if (model.smpl_surface_weight > 0 or model.zero_pose_weight > 0) and shard is not None:
         raise NotImplementedError("the smpl_surface / zero_pose regularisers (multiply.py:336-394) are not built for person-sharded training")
     if model.zero_pose_weight > 0 and not (isinstance(id, int) and id == -1):
@@ -1564,6 +1608,9 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
     with torch.enable_grad():                                                       # multiply.py:176
         outs = _TrainFn.apply(graph, *body, *params)
         rgb_values, normal_values, acc_map, acc_person, grad_theta = outs[:5]
+        geometry = ()
+        if graph.geometry:
+            outs, geometry = outs[:-len(GEOMETRY_KEYS)], outs[-len(GEOMETRY_KEYS):]
         smpl_surface_loss, zero_pose_loss = (outs[5], outs[6]) if len(outs) == 7 else (None, None)
         temporal_loss = torch.zeros(1, device=dev)
         if epoch > 250:                                                             # multiply.py:242-243
@@ -1603,6 +1650,7 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
     }
     if "sam_mask" in input:
         out["sam_mask"] = input["sam_mask"].squeeze()
+    out.update(zip(GEOMETRY_KEYS, geometry))
     model._last_train = graph
     model.last_stats = {"n_hit": cx["n_hit"], "iters": [graph.fg[p]["iters"] for p in cx["persons"]],
                         "n_sdf_evals": [graph.fg[p]["wcount"] for p in cx["persons"]],
