@@ -11,6 +11,15 @@ __device__ __forceinline__ float laplace_density(float sdf, float beta) {
     return (1.0f / beta) * (0.5f + 0.5f * sgn * expm1f(-fabsf(sdf) / beta));
 }
 
+// its adjoint: dsdf = d sigma / d sdf, dbeta = d sigma / d beta
+__device__ __forceinline__ void laplace_density_adjoint(float s, float beta, float& dsdf, float& dbeta) {
+    const float eab = expf(-fabsf(s) / beta);
+    dsdf = -(0.5f / (beta * beta)) * eab;
+    if (s > 0.f) dbeta = (0.5f / (beta * beta)) * eab * (s / beta - 1.0f);
+    else if (s < 0.f) dbeta = -1.0f / (beta * beta) + (0.5f / (beta * beta)) * eab * (1.0f + s / beta);
+    else dbeta = -0.5f / (beta * beta);
+}
+
 // alpha of one sample exactly as the compositing kernel computes it (multiply.py:455 via nerfacc):
 //   alpha = 1 - exp(-sigma * dt)
 __device__ __forceinline__ float alpha_of(float sdf, float beta, float dt) {

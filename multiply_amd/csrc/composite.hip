@@ -1,22 +1,39 @@
-// Multi-person compositing (reference code/lib/model/multiply.py:425-480, 544-545, 590).
+// Multi-person compositing (reference code/lib/model/multiply.py:425-480, 544-545, 590), its geometry outputs and their adjoints.
 // The reference packs every person's samples into one list, radix-sorts it twice (by t_end, then stably by ray) and
-// calls nerfacc's packed scan; the arithmetic per sample is nerfacc's render_weight_from_density:
-//   alpha = 1 - exp(-sigma dt),  T = exp(-sum_{earlier samples of the ray} sigma dt),  w = alpha T.
-// Here ONE WAVE owns one ray.  Each person's samples are already sorted, so "earlier in the merged order" needs no
-// merge: the free energy in front of sample (p,i) is person p's own exclusive prefix sum plus, for every other person q,
-// q's prefix sum at the rank of t_end(p,i) among q's t_ends (binary search; ties: lower person first, like the stable
-// sorts).  Rows are read with coalesced 64-lane loads (the first version, one thread per ray walking its rows, moved
-// 15x the algorithmic bytes through HBM: profiles/r01_pmc_traffic.txt), prefix sums are wave scans.
+// calls nerfacc's packed scan; the arithmetic per sample is nerfacc's render_weight_from_density: with fe = sigma dt the free
+// energy of a sample and E the sum of fe over the samples in front of it in the merged order,
+//   alpha = 1 - exp(-fe),  T = exp(-E),  w = alpha T.
+// Here ONE WAVE owns one ray and nothing is merged: mp::RayMerge (ray_merge.hpp) holds the per-person LDS arrays, their fill
+// (phase 1), the rank search with its tie rule, the free energy in front of a sample and the last-sample rule.  Rows are read
+// with coalesced 64-lane loads (the first version, one thread per ray walking its rows, moved 15x the algorithmic bytes through
+// HBM: profiles/r01_pmc_traffic.txt), prefix sums are wave scans.  The four kernels and what each adds to that core:
+//   k_composite               sums w rgb, w normal, w (merged and per person); T_bg from the last-sample rule.  No LDS extras:
+//                             3S+1 floats per person.
+//   k_composite_geometry      sums w t_mid (merged and per person), the person's own ("solo") opacity and depth, and the depth at
+//                             which the free energy reaches a level, merged and solo.  No LDS extras: 3S+1.
+//   k_composite_bwd           adjoint of k_composite into sdf, rgb, bg_rgb and beta.  Extras: gp [S+1], the prefix sums of dw w,
+//                             and w [S]: 5S+2.
+//   k_composite_geometry_bwd  adjoint of k_composite_geometry's differentiable outputs into sdf and beta.  Extras: gm [S+1], the
+//                             prefix sums of dw w in the merged order, and gs [S+1], those of dws w0 in the person's own: 5S+3.
+// The forward kernels run 4 waves per block; the adjoints halve that until their larger LDS fits (launch_shape).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include "../../include/multiply_hip.h"
 #include "common.hpp"
+#include "ray_merge.hpp"
 
 namespace {
 
-constexpr int MAX_P = 8;
+using mp::MAX_P;
+using mp::RayMerge;
 
-constexpr int WPB = 4;   // rays (waves) per workgroup
+constexpr int WPB = 4;   // rays (waves) per workgroup, at most
+constexpr int LDS_MAX = 160 * 1024;
+
+// floats per person in LDS, per kernel
+constexpr int fwd_stride(int S) { return RayMerge::prefix_floats(S); }
+constexpr int bwd_stride(int S) { return RayMerge::prefix_floats(S) + (S + 1) + S; }
+constexpr int geometry_bwd_stride(int S) { return RayMerge::prefix_floats(S) + 2 * (S + 1); }
 
 __global__ __launch_bounds__(64 * WPB) void k_composite(int n_rays, int P, int n_z, const int* const* __restrict__ inv_index,
                                                        const float* const* __restrict__ z,
@@ -31,43 +48,9 @@ __global__ __launch_bounds__(64 * WPB) void k_composite(int n_rays, int P, int n
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * WPB + wave;
     const int S = n_z - 1;
-    // per wave, per person: te [S] (t_end), fe [S] (free energy sigma dt), pf [S+1] (prefix sums, pf[0] = 0)
-    const int per_person = 3 * S + 1;
-    float* base = smem + (size_t)wave * P * per_person;
-    const float beta = *beta_p;
     const bool live = r < n_rays;
-    int k[MAX_P];
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) k[p] = (live && p < P) ? inv_index[p][r] : -1;
-
-    // ---- phase 1: free energies and per-person prefix sums
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            const float* sr = sdf[p] + (size_t)k[p] * S;
-            float carry = 0.f;
-            if (lane == 0) pf_l[0] = 0.f;
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float fe = 0.f;
-                if (i < S) {
-                    const float ts = zr[i], te = zr[i + 1];
-                    fe = mp::laplace_density(sr[i], beta) * (te - ts);
-                    te_l[i] = te;
-                    fe_l[i] = fe;
-                }
-                float tot;
-                const float ex = mp::wave_excl_scan(fe, tot);
-                if (i < S) pf_l[i + 1] = carry + ex + fe;
-                carry += tot;
-            }
-        }
-    }
-    __syncthreads();
+    const RayMerge m(smem, wave, S, fwd_stride(S), P, live, r, inv_index);
+    m.fill(z, sdf, *beta_p);
 
     // ---- phase 2: weights and accumulation
     float c[3] = {0.f, 0.f, 0.f}, nn[3] = {0.f, 0.f, 0.f}, acc = 0.f, accp[MAX_P];
@@ -75,32 +58,14 @@ __global__ __launch_bounds__(64 * WPB) void k_composite(int n_rays, int P, int n
     for (int p = 0; p < MAX_P; ++p) accp[p] = 0.f;
 #pragma unroll
     for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            const float* te_l = base + p * per_person;
-            const float* fe_l = te_l + S;
-            const float* pf_l = fe_l + S;
+        if (m.has(p)) {
+            const float* fe_l = m.fe(p);
             for (int i = lane; i < S; i += 64) {
-                const float te = te_l[i], fe = fe_l[i];
-                float E = pf_l[i];
-#pragma unroll
-                for (int q = 0; q < MAX_P; ++q) {
-                    if (q < P && q != p && k[q] >= 0) {
-                        const float* te_q = base + q * per_person;
-                        // number of q's samples in front: t_end < te (q > p) or <= te (q < p)
-                        int lo = 0, hi = S;
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            const float t = te_q[mid];
-                            const bool before = q < p ? t <= te : t < te;
-                            if (before) lo = mid + 1; else hi = mid;
-                        }
-                        E += (te_q + 2 * S)[lo];
-                    }
-                }
-                const float T = expf(-E);
+                const float fe = fe_l[i];
+                const float T = expf(-m.energy_in_front(p, i));
                 const float w = (1.0f - expf(-fe)) * T;
                 if (w != 0.0f) {  // skipped samples carry undefined colour/normal but exactly zero weight
-                    const size_t qi = (size_t)k[p] * S + i;
+                    const size_t qi = (size_t)m.k[p] * S + i;
                     c[0] += w * rgb[p][3 * qi]; c[1] += w * rgb[p][3 * qi + 1]; c[2] += w * rgb[p][3 * qi + 2];
                     nn[0] += w * normal[p][3 * qi]; nn[1] += w * normal[p][3 * qi + 1]; nn[2] += w * normal[p][3 * qi + 2];
                 }
@@ -114,17 +79,8 @@ __global__ __launch_bounds__(64 * WPB) void k_composite(int n_rays, int P, int n
 #pragma unroll
     for (int p = 0; p < MAX_P; ++p) accp[p] = mp::wsum(accp[p]);
     if (!live || lane != 0) return;
-    // exclusive transmittance of the LAST packed sample (multiply.py:457-463): the last sample of the person whose final
-    // t_end is the largest (ties: higher person); 1 for rays without samples
-    int p_last = -1;
-    float tm = -FLT_MAX;
-    for (int p = 0; p < P; ++p)
-        if (k[p] >= 0 && (base + p * per_person)[S - 1] >= tm) { tm = (base + p * per_person)[S - 1]; p_last = p; }
-    const bool any = p_last >= 0;
-    float E_front = 0.f;   // everything in front of the last sample = all of the other persons + the last person's first S-1
-    for (int p = 0; p < P; ++p)
-        if (k[p] >= 0) E_front += (base + p * per_person + 2 * S)[p == p_last ? S - 1 : S];
-    const float T_last = any ? expf(-E_front) : 1.0f;
+    float T_last;
+    m.last_sample(T_last);
     bg_T[r] = T_last;
     acc_map[r] = acc;
     for (int p = 0; p < P; ++p) acc_person[(size_t)r * P + p] = accp[p];
@@ -137,15 +93,13 @@ __global__ __launch_bounds__(64 * WPB) void k_composite(int n_rays, int P, int n
     }
 }
 
-// Geometry of the same merge: where along the ray the volume is, instead of what colour it has.  Phase 1 and the LDS layout
-// are k_composite's; phase 2 looks up the same ranks and sums w * t_mid (merged and per person), the person's own
-// ("solo": as if rendered alone, E = its own prefix sum) opacity and depth, and finds the depth at which the free energy
-// reaches L = -ln(1 - level): the FIRST sample in merged order with E + fe >= L, found as the minimum of the key
-// (t_end, person, sample) over every sample that satisfies the inequality (in fp32 the per-person sums of E do not tile the
-// axis, the minimum is defined regardless), linearly interpolated inside that sample.  Every lane keeps its best candidate;
-// the wave reduces on t_end, then on the person among the lanes holding the minimum, then on the sample index.
+// Geometry of the same merge: where along the ray the volume is, instead of what colour it has.  Phase 2 sums w * t_mid (merged
+// and per person), the person's own ("solo": as if rendered alone, E = its own prefix sum) opacity and depth, and finds the
+// depth at which the free energy reaches L = -ln(1 - level): the FIRST sample in merged order with E + fe >= L, found as the
+// minimum of the key (t_end, person, sample) over every sample that satisfies the inequality (in fp32 the per-person sums of E
+// do not tile the axis, the minimum is defined regardless), linearly interpolated inside that sample.  Every lane keeps its best
+// candidate; the wave reduces on t_end, then on the person among the lanes holding the minimum, then on the sample index.
 // No atomics, fixed summation order: bit-identical from run to run.  Any output pointer may be null.
-// The fill and the rank search repeat k_composite's text on purpose: as shared __device__ helpers they change k_composite's ISA.
 __device__ __forceinline__ float level_depth(float ts, float te, float E, float fe, float L) {
     const float f = fe > 0.f ? fminf(fmaxf((L - E) / fe, 0.f), 1.f) : 0.f;
     return ts + (te - ts) * f;
@@ -163,43 +117,9 @@ __global__ __launch_bounds__(64 * WPB) void k_composite_geometry(int n_rays, int
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * WPB + wave;
     const int S = n_z - 1;
-    // per wave, per person: te [S] (t_end), fe [S] (free energy sigma dt), pf [S+1] (prefix sums, pf[0] = 0)
-    const int per_person = 3 * S + 1;
-    float* base = smem + (size_t)wave * P * per_person;
-    const float beta = *beta_p;
     const bool live = r < n_rays;
-    int k[MAX_P];
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) k[p] = (live && p < P) ? inv_index[p][r] : -1;
-
-    // ---- phase 1: free energies and per-person prefix sums
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            const float* sr = sdf[p] + (size_t)k[p] * S;
-            float carry = 0.f;
-            if (lane == 0) pf_l[0] = 0.f;
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float fe = 0.f;
-                if (i < S) {
-                    const float ts = zr[i], te = zr[i + 1];
-                    fe = mp::laplace_density(sr[i], beta) * (te - ts);
-                    te_l[i] = te;
-                    fe_l[i] = fe;
-                }
-                float tot;
-                const float ex = mp::wave_excl_scan(fe, tot);
-                if (i < S) pf_l[i + 1] = carry + ex + fe;
-                carry += tot;
-            }
-        }
-    }
-    __syncthreads();
+    const RayMerge m(smem, wave, S, fwd_stride(S), P, live, r, inv_index);
+    m.fill(z, sdf, *beta_p);
 
     // ---- phase 2: weights, depth sums and the level candidates
     const bool out0 = live && lane == 0;
@@ -209,11 +129,11 @@ __global__ __launch_bounds__(64 * WPB) void k_composite_geometry(int n_rays, int
     for (int p = 0; p < MAX_P; ++p) {
         if (p >= P) continue;
         float d_p = 0.f, a_s = 0.f, d_s = 0.f, lvl = -1.f;
-        if (k[p] >= 0) {
-            const float* te_l = base + p * per_person;
-            const float* fe_l = te_l + S;
-            const float* pf_l = fe_l + S;
-            const float t0 = z[p][(size_t)k[p] * n_z];
+        if (m.k[p] >= 0) {
+            const float* te_l = m.te(p);
+            const float* fe_l = m.fe(p);
+            const float* pf_l = m.pf(p);
+            const float t0 = z[p][(size_t)m.k[p] * n_z];
             float s_te = FLT_MAX, s_i = FLT_MAX, s_d = 0.f;              // this lane's solo candidate, key (te, sample)
             for (int i0 = 0; i0 < S; i0 += 64) {
                 const int i = i0 + lane;
@@ -221,22 +141,7 @@ __global__ __launch_bounds__(64 * WPB) void k_composite_geometry(int n_rays, int
                     const float te = te_l[i], fe = fe_l[i];
                     const float ts = i > 0 ? te_l[i - 1] : t0;
                     const float Es = pf_l[i];
-                    float E = Es;
-#pragma unroll
-                    for (int q = 0; q < MAX_P; ++q) {
-                        if (q < P && q != p && k[q] >= 0) {
-                            const float* te_q = base + q * per_person;
-                            // number of q's samples in front: t_end < te (q > p) or <= te (q < p)
-                            int lo = 0, hi = S;
-                            while (lo < hi) {
-                                const int mid = (lo + hi) >> 1;
-                                const float t = te_q[mid];
-                                const bool before = q < p ? t <= te : t < te;
-                                if (before) lo = mid + 1; else hi = mid;
-                            }
-                            E += (te_q + 2 * S)[lo];
-                        }
-                    }
+                    const float E = m.energy_in_front(p, i);
                     const float a = 1.0f - expf(-fe);
                     const float tm = 0.5f * (ts + te);
                     const float w = a * expf(-E), ws = a * expf(-Es);
@@ -286,20 +191,241 @@ __global__ __launch_bounds__(64 * WPB) void k_composite_geometry(int n_rays, int
     if (front_person) front_person[r] = front;
 }
 
+// ---- compositing backward: with dw = dC . rgb + dA + dA_p, the adjoint of fe_j is
+//     dw_j T_j exp(-fe_j)  -  sum_{i behind j} dw_i w_i  -  [j is not the very last sample] dT_bg T_bg
+// E and the sum behind are per-person prefix sums looked up at the ranks.  (The first version walked the merged list with one
+// THREAD per ray: 512 threads on the whole device, ~1 ms.)
+__global__ __launch_bounds__(256) void k_composite_bwd(
+    int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
+    const float* const* __restrict__ sdf, const float* const* __restrict__ rgb, const float* __restrict__ beta_p,
+    const float* __restrict__ bg_rgb, const float* __restrict__ d_rgb_values, const float* __restrict__ d_acc,
+    const float* __restrict__ d_acc_person, float* const* __restrict__ d_sdf, float* const* __restrict__ d_rgb,
+    float* __restrict__ d_bg_rgb, float* __restrict__ d_beta) {
+    extern __shared__ float smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    const int r = blockIdx.x * wpb + wave;
+    const int S = n_z - 1;
+    const float beta = *beta_p;
+    const bool live = r < n_rays;
+    const RayMerge m(smem, wave, S, bwd_stride(S), P, live, r, inv_index);   // extras: 0 gp [S+1] (prefix of dw w), 1 w [S]
+    float dC[3] = {0.f, 0.f, 0.f}, dA = 0.f;
+    if (live) {
+        for (int a = 0; a < 3; ++a) dC[a] = d_rgb_values[3 * r + a];
+        dA = d_acc ? d_acc[r] : 0.0f;
+    }
+    m.fill(z, sdf, beta);
+    // ---- phase 2: weights, dw w and its per-person prefix sums
+#pragma unroll
+    for (int p = 0; p < MAX_P; ++p) {
+        if (m.has(p)) {
+            const float* fe_l = m.fe(p);
+            float* gp_l = m.extra(p, 0);
+            float* w_l = m.extra(p, 1);
+            const float dAp = d_acc_person ? d_acc_person[(size_t)r * P + p] : 0.0f;
+            float carry = 0.f;
+            if (lane == 0) gp_l[0] = 0.f;
+            for (int i0 = 0; i0 < S; i0 += 64) {
+                const int i = i0 + lane;
+                float g = 0.f;
+                if (i < S) {
+                    const float T = expf(-m.energy_in_front(p, i));
+                    const float w = (1.0f - expf(-fe_l[i])) * T;
+                    const size_t qi = (size_t)m.k[p] * S + i;
+                    const float dw = dC[0] * rgb[p][3 * qi] + dC[1] * rgb[p][3 * qi + 1] + dC[2] * rgb[p][3 * qi + 2] + dA + dAp;
+                    w_l[i] = w;
+                    g = dw * w;
+                    d_rgb[p][3 * qi] = w * dC[0]; d_rgb[p][3 * qi + 1] = w * dC[1]; d_rgb[p][3 * qi + 2] = w * dC[2];
+                }
+                float tot;
+                const float ex = mp::wave_excl_scan(g, tot);
+                if (i < S) gp_l[i + 1] = carry + ex + g;
+                carry += tot;
+            }
+        }
+    }
+    __syncthreads();
+    float Tbg;
+    const int p_last = m.last_sample(Tbg);
+    float dTbg = 0.f;
+    for (int a = 0; a < 3; ++a) dTbg += dC[a] * (bg_rgb && live ? bg_rgb[3 * r + a] : 1.0f);
+    if (live && lane < 3 && d_bg_rgb) d_bg_rgb[3 * r + lane] = dC[lane] * Tbg;
+    // ---- phase 3: adjoints of the free energies -> sdf and beta
+    float dbeta_local = 0.0f;
+#pragma unroll
+    for (int p = 0; p < MAX_P; ++p) {
+        if (m.has(p)) {
+            const float* te_l = m.te(p);
+            const float* fe_l = m.fe(p);
+            const float* pf_l = m.pf(p);
+            const float* gp_l = m.extra(p, 0);
+            const float* zr = z[p] + (size_t)m.k[p] * n_z;
+            for (int i = lane; i < S; i += 64) {
+                const float te = te_l[i], fe = fe_l[i];
+                float E = pf_l[i], suffix = gp_l[S] - gp_l[i + 1];     // free energy in front, dw w behind
+                m.others_in_front(p, te, [&](int q, int lo) {
+                    E += m.pf(q)[lo];
+                    suffix += m.extra(q, 0)[S] - m.extra(q, 0)[lo];
+                });
+                const float T = expf(-E), ex = expf(-fe);
+                const size_t qi = (size_t)m.k[p] * S + i;
+                const float dw = dC[0] * rgb[p][3 * qi] + dC[1] * rgb[p][3 * qi + 1] + dC[2] * rgb[p][3 * qi + 2] + dA +
+                                 (d_acc_person ? d_acc_person[(size_t)r * P + p] : 0.0f);
+                float dfe = dw * T * ex - suffix;
+                if (!(p == p_last && i == S - 1)) dfe -= dTbg * Tbg;   // T_bg depends on every sample but the last
+                const float dsig = dfe * (te - zr[i]);
+                float dsdf, dbe;
+                mp::laplace_density_adjoint(sdf[p][qi], beta, dsdf, dbe);
+                d_sdf[p][qi] = dsig * dsdf;
+                dbeta_local += dsig * dbe;
+            }
+        }
+    }
+    dbeta_local = mp::wsum(dbeta_local);
+    if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
+}
+
+// ---- adjoint of the geometry outputs: d depth / d depth_person (merged sums of w tm), d acc_solo / d depth_solo (the person's
+// own list: E = its own prefix sum) and d depth_solo_level.  Phase 2 fills TWO per-person prefix arrays (dw w in merged order,
+// dws w0 in the person's own order) and finds the person's crossing sample j* by the forward's rule (minimum of (te, sample) over
+// the samples with Es + fe >= L); phase 3 turns
+//     dfe_j = dw_j e^-E e^-fe - sum_{behind j, merged} dw w  +  dws_j e^-Es e^-fe - sum_{i>j, own} dws w0  -  c [j < j*]  -  c f [j == j*]
+// (c = d level (te-ts)/fe of sample j*, f = (L-Es)/fe there; nothing where the forward clamps or finds no crossing) into d sdf and
+// d beta.  It ACCUMULATES (d_sdf +=: each element belongs to one lane), after k_composite_bwd's `=` on the same stream.
+__global__ __launch_bounds__(256) void k_composite_geometry_bwd(
+    int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
+    const float* const* __restrict__ sdf, const float* __restrict__ beta_p, float L, const float* __restrict__ d_depth,
+    const float* __restrict__ d_depth_person, const float* __restrict__ d_acc_solo, const float* __restrict__ d_depth_solo,
+    const float* __restrict__ d_depth_solo_level, float* const* __restrict__ d_sdf, float* __restrict__ d_beta) {
+    extern __shared__ float smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    const int r = blockIdx.x * wpb + wave;
+    const int S = n_z - 1;
+    const float beta = *beta_p;
+    const bool live = r < n_rays;
+    const bool merged = d_depth || d_depth_person;          // (uniform) without them no rank is looked up
+    // extras: 0 gm [S+1] (prefix of dw w), 1 gs [S+1] (prefix of dws w0)
+    const RayMerge m(smem, wave, S, geometry_bwd_stride(S), P, live, r, inv_index);
+    const float dD = (live && d_depth) ? d_depth[r] : 0.0f;
+    m.fill(z, sdf, beta);
+    // ---- phase 2: dw w (merged) and dws w0 (solo) with their prefix sums; the person's crossing sample
+    float dwm[MAX_P], dAs[MAX_P], dDs[MAX_P], lc[MAX_P], lf[MAX_P];
+    int jst[MAX_P];
+#pragma unroll
+    for (int p = 0; p < MAX_P; ++p) {
+        dwm[p] = dAs[p] = dDs[p] = lc[p] = lf[p] = 0.0f;
+        jst[p] = -1;
+        if (m.has(p)) {
+            const float* te_l = m.te(p);
+            const float* fe_l = m.fe(p);
+            const float* pf_l = m.pf(p);
+            float* gm_l = m.extra(p, 0);
+            float* gs_l = m.extra(p, 1);
+            const size_t o = (size_t)r * P + p;
+            const float t0 = z[p][(size_t)m.k[p] * n_z];
+            dwm[p] = dD + (d_depth_person ? d_depth_person[o] : 0.0f);
+            dAs[p] = d_acc_solo ? d_acc_solo[o] : 0.0f;
+            dDs[p] = d_depth_solo ? d_depth_solo[o] : 0.0f;
+            float carry_m = 0.f, carry_s = 0.f;
+            if (lane == 0) gm_l[0] = gs_l[0] = 0.f;
+            float s_te = FLT_MAX, s_i = FLT_MAX;               // this lane's solo candidate, key (te, sample)
+            for (int i0 = 0; i0 < S; i0 += 64) {
+                const int i = i0 + lane;
+                float gm = 0.f, gs = 0.f;
+                if (i < S) {
+                    const float te = te_l[i], fe = fe_l[i];
+                    const float ts = i > 0 ? te_l[i - 1] : t0;
+                    const float Es = pf_l[i];
+                    const float a = 1.0f - expf(-fe), tm = 0.5f * (ts + te);
+                    if (merged) gm = dwm[p] * tm * a * expf(-m.energy_in_front(p, i));
+                    gs = (dAs[p] + dDs[p] * tm) * a * expf(-Es);
+                    if (Es + fe >= L && te < s_te) { s_te = te; s_i = (float)i; }
+                }
+                float tot;
+                float ex = mp::wave_excl_scan(gm, tot);
+                if (i < S) gm_l[i + 1] = carry_m + ex + gm;
+                carry_m += tot;
+                ex = mp::wave_excl_scan(gs, tot);
+                if (i < S) gs_l[i + 1] = carry_s + ex + gs;
+                carry_s += tot;
+            }
+            const float g = d_depth_solo_level ? d_depth_solo_level[o] : 0.0f;
+            const float b_te = mp::wmin(s_te);
+            if (g != 0.0f && b_te < FLT_MAX) {
+                const int j = (int)mp::wmin(s_te == b_te ? s_i : FLT_MAX);
+                const float fe = fe_l[j];
+                const float f = fe > 0.f ? (L - pf_l[j]) / fe : 0.f;
+                if (f > 0.f && f < 1.f) {
+                    jst[p] = j;
+                    lc[p] = g * (te_l[j] - (j > 0 ? te_l[j - 1] : t0)) / fe;
+                    lf[p] = f;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 3: adjoints of the free energies -> sdf and beta
+    float dbeta_local = 0.0f;
+#pragma unroll
+    for (int p = 0; p < MAX_P; ++p) {
+        if (m.has(p)) {
+            const float* te_l = m.te(p);
+            const float* fe_l = m.fe(p);
+            const float* pf_l = m.pf(p);
+            const float* gm_l = m.extra(p, 0);
+            const float* gs_l = m.extra(p, 1);
+            const float* zr = z[p] + (size_t)m.k[p] * n_z;
+            for (int i = lane; i < S; i += 64) {
+                const float te = te_l[i], fe = fe_l[i], ts = zr[i];
+                const float Es = pf_l[i], ex = expf(-fe), tm = 0.5f * (ts + te);
+                float dfe = (dAs[p] + dDs[p] * tm) * expf(-Es) * ex - (gs_l[S] - gs_l[i + 1]);
+                if (merged) {
+                    float E = Es, suffix = gm_l[S] - gm_l[i + 1];      // free energy in front, dw w behind
+                    m.others_in_front(p, te, [&](int q, int lo) {
+                        E += m.pf(q)[lo];
+                        suffix += m.extra(q, 0)[S] - m.extra(q, 0)[lo];
+                    });
+                    dfe += dwm[p] * tm * expf(-E) * ex - suffix;
+                }
+                if (i < jst[p]) dfe -= lc[p];
+                else if (i == jst[p]) dfe -= lc[p] * lf[p];
+                const size_t qi = (size_t)m.k[p] * S + i;
+                const float dsig = dfe * (te - ts);
+                float dsdf, dbe;
+                mp::laplace_density_adjoint(sdf[p][qi], beta, dsdf, dbe);
+                d_sdf[p][qi] += dsig * dsdf;
+                dbeta_local += dsig * dbe;
+            }
+        }
+    }
+    dbeta_local = mp::wsum(dbeta_local);
+    if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
+}
+
+// Launch shape of the family for `per_person` floats of LDS per person and wave.  rc -1: n_person outside [0, MAX_P]; rc -2: the
+// block does not fit 160 KiB of LDS.  A fixed shape has WPB waves per block; an adaptive one halves them, down to one, until
+// they fit.
+struct LaunchShape { int rc, wpb, lds; };
+LaunchShape launch_shape(int n_person, int per_person, bool adaptive) {
+    if (n_person > MAX_P || n_person < 0) return {-1, 0, 0};
+    const int per_wave = n_person * per_person * (int)sizeof(float);
+    int wpb = WPB;
+    while (adaptive && wpb > 1 && wpb * per_wave > LDS_MAX) wpb >>= 1;
+    return {wpb * per_wave > LDS_MAX ? -2 : 0, wpb, wpb * per_wave};
+}
+
 }  // namespace
 
 extern "C" int mp_composite(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
                             const float* const* sdf, const float* const* rgb, const float* const* normal,
                             const float* beta, const float* bg_rgb, float* rgb_values, float* fg_rgb_values,
                             float* normal_values, float* acc_map, float* acc_person, float* bg_T, void* stream) {
-    if (n_person > MAX_P || n_person < 0) return -1;
+    const LaunchShape sh = launch_shape(n_person, fwd_stride(n_z - 1), false);
+    if (sh.rc == -1) return -1;
     if (n_rays <= 0) return 0;
-    const int S = n_z - 1;
-    const int lds = WPB * n_person * (3 * S + 1) * (int)sizeof(float);
-    if (lds > 160 * 1024) return -2;
-    MP_LDS_ATTR((k_composite), 160 * 1024);
-    hipLaunchKernelGGL(k_composite, dim3((n_rays + WPB - 1) / WPB), dim3(64 * WPB), lds, (hipStream_t)stream, n_rays, n_person, n_z,
-                       inv_index, z, sdf, rgb, normal, beta, bg_rgb, rgb_values, fg_rgb_values, normal_values, acc_map,
+    if (sh.rc) return sh.rc;
+    MP_LDS_ATTR((k_composite), LDS_MAX);
+    hipLaunchKernelGGL(k_composite, dim3((n_rays + WPB - 1) / WPB), dim3(64 * WPB), sh.lds, (hipStream_t)stream, n_rays, n_person,
+                       n_z, inv_index, z, sdf, rgb, normal, beta, bg_rgb, rgb_values, fg_rgb_values, normal_values, acc_map,
                        acc_person, bg_T);
     return (int)hipGetLastError();
 }
@@ -308,16 +434,49 @@ extern "C" int mp_composite_geometry(int n_rays, int n_person, int n_z, const in
                                      const float* const* sdf, const float* beta, float level, float* depth,
                                      float* depth_person, float* depth_level, int* front_person, float* acc_solo,
                                      float* depth_solo, float* depth_solo_level, void* stream) {
-    if (n_person > MAX_P || n_person < 0) return -1;
+    const LaunchShape sh = launch_shape(n_person, fwd_stride(n_z - 1), false);
+    if (sh.rc == -1) return -1;
     if (!(level > 0.f && level < 1.f)) return -3;
     if (n_rays <= 0) return 0;
-    const int S = n_z - 1;
-    const int lds = WPB * n_person * (3 * S + 1) * (int)sizeof(float);
-    if (lds > 160 * 1024) return -2;
-    MP_LDS_ATTR((k_composite_geometry), 160 * 1024);
+    if (sh.rc) return sh.rc;
+    MP_LDS_ATTR((k_composite_geometry), LDS_MAX);
     const float L = (float)-log1p(-(double)level);
-    hipLaunchKernelGGL(k_composite_geometry, dim3((n_rays + WPB - 1) / WPB), dim3(64 * WPB), lds, (hipStream_t)stream, n_rays,
+    hipLaunchKernelGGL(k_composite_geometry, dim3((n_rays + WPB - 1) / WPB), dim3(64 * WPB), sh.lds, (hipStream_t)stream, n_rays,
                        n_person, n_z, inv_index, z, sdf, beta, L, depth, depth_person, depth_level, front_person, acc_solo,
                        depth_solo, depth_solo_level);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_tr_composite_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                                   const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
+                                   const float* d_rgb_values, const float* d_acc, const float* d_acc_person,
+                                   float* const* d_sdf, float* const* d_rgb, float* d_bg_rgb, float* d_beta, void* stream) {
+    const LaunchShape sh = launch_shape(n_person, bwd_stride(n_z - 1), true);
+    if (sh.rc == -1) return -1;
+    if (n_rays <= 0) return 0;
+    if (sh.rc) return sh.rc;
+    MP_LDS_ATTR((k_composite_bwd), LDS_MAX);
+    hipLaunchKernelGGL(k_composite_bwd, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream, n_rays,
+                       n_person, n_z, inv_index, z, sdf, rgb, beta, bg_rgb, d_rgb_values, d_acc, d_acc_person, d_sdf, d_rgb,
+                       d_bg_rgb, d_beta);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index,
+                                            const float* const* z, const float* const* sdf, const float* beta, float level,
+                                            const float* d_depth, const float* d_depth_person, const float* d_acc_solo,
+                                            const float* d_depth_solo, const float* d_depth_solo_level, float* const* d_sdf,
+                                            float* d_beta, void* stream) {
+    const LaunchShape sh = launch_shape(n_person, geometry_bwd_stride(n_z - 1), true);
+    if (sh.rc == -1) return -1;
+    if (!(level > 0.f && level < 1.f)) return -3;
+    if (n_rays <= 0) return 0;
+    if (!d_depth && !d_depth_person && !d_acc_solo && !d_depth_solo && !d_depth_solo_level) return 0;
+    if (sh.rc) return sh.rc;
+    MP_LDS_ATTR((k_composite_geometry_bwd), LDS_MAX);
+    const float L = (float)-log1p(-(double)level);
+    hipLaunchKernelGGL(k_composite_geometry_bwd, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream,
+                       n_rays, n_person, n_z, inv_index, z, sdf, beta, L, d_depth, d_depth_person, d_acc_solo, d_depth_solo,
+                       d_depth_solo_level, d_sdf, d_beta);
     return (int)hipGetLastError();
 }

@@ -5,7 +5,6 @@
 // reference obtains with create_graph=True (normals: multiply.py:620-661, eikonal term: :328-330).
 // Entry points: include/multiply_hip.h (mp_tr_*).
 #include <hip/hip_runtime.h>
-#include <float.h>
 #include "../../include/multiply_hip.h"
 #include "common.hpp"
 
@@ -323,351 +322,6 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dZ, in
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) db[c] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// ---- compositing backward.  Like the forward (composite.hip) ONE WAVE owns one ray and nothing is merged: with fe the free
-// energy sigma dt of a sample, E its exclusive sum in the merged order, T = exp(-E), w = (1 - exp(-fe)) T and
-// dw = dC . rgb + dA + dA_p, the adjoint of fe_j is
-//     dw_j T_j exp(-fe_j)  -  sum_{i behind j} dw_i w_i  -  [j is not the very last sample] dT_bg T_bg
-// "In front of / behind (p, j)" in another person q's sorted list is a rank (binary search on t_end; ties: lower person
-// first, the order of the reference's stable sorts), so E and the suffix sum are per-person prefix sums looked up at those
-// ranks.  (The first version walked the merged list with one THREAD per ray: 512 threads on the whole device, ~1 ms.)
-constexpr int MAX_P = 8;
-__global__ __launch_bounds__(256) void k_composite_bwd(
-    int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
-    const float* const* __restrict__ sdf, const float* const* __restrict__ rgb, const float* __restrict__ beta_p,
-    const float* __restrict__ bg_rgb, const float* __restrict__ d_rgb_values, const float* __restrict__ d_acc,
-    const float* __restrict__ d_acc_person, float* const* __restrict__ d_sdf, float* const* __restrict__ d_rgb,
-    float* __restrict__ d_bg_rgb, float* __restrict__ d_beta) {
-    extern __shared__ float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int r = blockIdx.x * wpb + wave;
-    const int S = n_z - 1;
-    // per wave, per person: te [S], fe [S], pf [S+1] (prefix of fe), w [S], gp [S+1] (prefix of dw w)
-    const int per_person = 5 * S + 2;
-    float* base = smem + (size_t)wave * P * per_person;
-    const float beta = *beta_p;
-    const bool live = r < n_rays;
-    int k[MAX_P];
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) k[p] = (live && p < P) ? inv_index[p][r] : -1;
-    float dC[3] = {0.f, 0.f, 0.f}, dA = 0.f;
-    if (live) {
-        for (int a = 0; a < 3; ++a) dC[a] = d_rgb_values[3 * r + a];
-        dA = d_acc ? d_acc[r] : 0.0f;
-    }
-    // ---- phase 1: free energies and their per-person prefix sums
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            const float* sr = sdf[p] + (size_t)k[p] * S;
-            float carry = 0.f;
-            if (lane == 0) pf_l[0] = 0.f;
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float fe = 0.f;
-                if (i < S) {
-                    const float ts = zr[i], te = zr[i + 1];
-                    fe = mp::laplace_density(sr[i], beta) * (te - ts);
-                    te_l[i] = te;
-                    fe_l[i] = fe;
-                }
-                float tot;
-                const float ex = mp::wave_excl_scan(fe, tot);
-                if (i < S) pf_l[i + 1] = carry + ex + fe;
-                carry += tot;
-            }
-        }
-    }
-    __syncthreads();
-    // rank of t_end `te` of person p's sample among person q's samples (q != p)
-    auto rank_in = [&](int q, int p, float te) {
-        const float* te_q = base + q * per_person;
-        int lo = 0, hi = S;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            const float t = te_q[mid];
-            const bool before = q < p ? t <= te : t < te;
-            if (before) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-    };
-    // ---- phase 2: weights, dw w and its per-person prefix sums
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            float* w_l = pf_l + S + 1;
-            float* gp_l = w_l + S;
-            const float dAp = d_acc_person ? d_acc_person[(size_t)r * P + p] : 0.0f;
-            float carry = 0.f;
-            if (lane == 0) gp_l[0] = 0.f;
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float g = 0.f;
-                if (i < S) {
-                    const float te = te_l[i];
-                    float E = pf_l[i];
-#pragma unroll
-                    for (int q = 0; q < MAX_P; ++q)
-                        if (q < P && q != p && k[q] >= 0) E += (base + q * per_person + 2 * S)[rank_in(q, p, te)];
-                    const float T = expf(-E);
-                    const float w = (1.0f - expf(-fe_l[i])) * T;
-                    const size_t qi = (size_t)k[p] * S + i;
-                    const float dw = dC[0] * rgb[p][3 * qi] + dC[1] * rgb[p][3 * qi + 1] + dC[2] * rgb[p][3 * qi + 2] + dA + dAp;
-                    w_l[i] = w;
-                    g = dw * w;
-                    d_rgb[p][3 * qi] = w * dC[0]; d_rgb[p][3 * qi + 1] = w * dC[1]; d_rgb[p][3 * qi + 2] = w * dC[2];
-                }
-                float tot;
-                const float ex = mp::wave_excl_scan(g, tot);
-                if (i < S) gp_l[i + 1] = carry + ex + g;
-                carry += tot;
-            }
-        }
-    }
-    __syncthreads();
-    // the very last sample of the merged order, and T_bg = its exclusive transmittance (multiply.py:457-463)
-    int p_last = -1;
-    float tm = -FLT_MAX;
-    for (int p = 0; p < P; ++p)
-        if (k[p] >= 0 && (base + p * per_person)[S - 1] >= tm) { tm = (base + p * per_person)[S - 1]; p_last = p; }
-    float E_front = 0.f;
-    for (int p = 0; p < P; ++p)
-        if (k[p] >= 0) E_front += (base + p * per_person + 2 * S)[p == p_last ? S - 1 : S];
-    const float Tbg = p_last >= 0 ? expf(-E_front) : 1.0f;
-    float dTbg = 0.f;
-    for (int a = 0; a < 3; ++a) dTbg += dC[a] * (bg_rgb && live ? bg_rgb[3 * r + a] : 1.0f);
-    if (live && lane < 3 && d_bg_rgb) d_bg_rgb[3 * r + lane] = dC[lane] * Tbg;
-    // ---- phase 3: adjoints of the free energies -> sdf and beta
-    float dbeta_local = 0.0f;
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            const float* te_l = base + p * per_person;
-            const float* fe_l = te_l + S;
-            const float* pf_l = fe_l + S;
-            const float* w_l = pf_l + S + 1;
-            const float* gp_l = w_l + S;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            for (int i = lane; i < S; i += 64) {
-                const float te = te_l[i], fe = fe_l[i];
-                float E = pf_l[i];
-                float suffix = gp_l[S] - gp_l[i + 1];
-#pragma unroll
-                for (int q = 0; q < MAX_P; ++q)
-                    if (q < P && q != p && k[q] >= 0) {
-                        const int lo = rank_in(q, p, te);
-                        const float* pq = base + q * per_person + 2 * S;
-                        E += pq[lo];
-                        suffix += (pq + 2 * S + 1)[S] - (pq + 2 * S + 1)[lo];
-                    }
-                const float T = expf(-E), ex = expf(-fe);
-                const size_t qi = (size_t)k[p] * S + i;
-                const float dw = dC[0] * rgb[p][3 * qi] + dC[1] * rgb[p][3 * qi + 1] + dC[2] * rgb[p][3 * qi + 2] + dA +
-                                 (d_acc_person ? d_acc_person[(size_t)r * P + p] : 0.0f);
-                float dfe = dw * T * ex - suffix;
-                if (!(p == p_last && i == S - 1)) dfe -= dTbg * Tbg;   // T_bg depends on every sample but the last
-                const float s = sdf[p][qi];
-                const float dsig = dfe * (te - zr[i]);
-                // d sigma / d sdf and d sigma / d beta (density.py:20-29)
-                const float eab = expf(-fabsf(s) / beta);
-                const float dsdf = -(0.5f / (beta * beta)) * eab;
-                float dbe;
-                if (s > 0.f) dbe = (0.5f / (beta * beta)) * eab * (s / beta - 1.0f);
-                else if (s < 0.f) dbe = -1.0f / (beta * beta) + (0.5f / (beta * beta)) * eab * (1.0f + s / beta);
-                else dbe = -0.5f / (beta * beta);
-                d_sdf[p][qi] = dsig * dsdf;
-                dbeta_local += dsig * dbe;
-            }
-        }
-    }
-    dbeta_local = mp::wsum(dbeta_local);
-    if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
-}
-
-// ---- adjoint of the geometry outputs of the same merge (composite.hip k_composite_geometry): d depth / d depth_person (merged
-// sums of w tm), d acc_solo / d depth_solo (the person's own list: E = its own prefix sum) and d depth_solo_level.  Shaped like
-// k_composite_bwd: phase 1 and the rank search are its text; phase 2 fills TWO per-person prefix arrays (dw w in merged order,
-// dws w0 in the person's own order) and finds the person's crossing sample j* by the forward's rule (minimum of (te, sample) over
-// the samples with Es + fe >= L); phase 3 turns
-//     dfe_j = dw_j e^-E e^-fe - sum_{behind j, merged} dw w  +  dws_j e^-Es e^-fe - sum_{i>j, own} dws w0  -  c [j < j*]  -  c f [j == j*]
-// (c = d level (te-ts)/fe of sample j*, f = (L-Es)/fe there; nothing where the forward clamps or finds no crossing) into d sdf and
-// d beta.  It ACCUMULATES (d_sdf +=: each element belongs to one lane), after k_composite_bwd's `=` on the same stream.
-__global__ __launch_bounds__(256) void k_composite_geometry_bwd(
-    int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
-    const float* const* __restrict__ sdf, const float* __restrict__ beta_p, float L, const float* __restrict__ d_depth,
-    const float* __restrict__ d_depth_person, const float* __restrict__ d_acc_solo, const float* __restrict__ d_depth_solo,
-    const float* __restrict__ d_depth_solo_level, float* const* __restrict__ d_sdf, float* __restrict__ d_beta) {
-    extern __shared__ float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    const int r = blockIdx.x * wpb + wave;
-    const int S = n_z - 1;
-    // per wave, per person: te [S], fe [S], pf [S+1] (prefix of fe), gm [S+1] (prefix of dw w), gs [S+1] (prefix of dws w0)
-    const int per_person = 5 * S + 3;
-    float* base = smem + (size_t)wave * P * per_person;
-    const float beta = *beta_p;
-    const bool live = r < n_rays;
-    const bool merged = d_depth || d_depth_person;          // (uniform) without them no rank is looked up
-    int k[MAX_P];
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) k[p] = (live && p < P) ? inv_index[p][r] : -1;
-    const float dD = (live && d_depth) ? d_depth[r] : 0.0f;
-    // ---- phase 1: free energies and their per-person prefix sums
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            const float* sr = sdf[p] + (size_t)k[p] * S;
-            float carry = 0.f;
-            if (lane == 0) pf_l[0] = 0.f;
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float fe = 0.f;
-                if (i < S) {
-                    const float ts = zr[i], te = zr[i + 1];
-                    fe = mp::laplace_density(sr[i], beta) * (te - ts);
-                    te_l[i] = te;
-                    fe_l[i] = fe;
-                }
-                float tot;
-                const float ex = mp::wave_excl_scan(fe, tot);
-                if (i < S) pf_l[i + 1] = carry + ex + fe;
-                carry += tot;
-            }
-        }
-    }
-    __syncthreads();
-    // rank of t_end `te` of person p's sample among person q's samples (q != p)
-    auto rank_in = [&](int q, int p, float te) {
-        const float* te_q = base + q * per_person;
-        int lo = 0, hi = S;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            const float t = te_q[mid];
-            const bool before = q < p ? t <= te : t < te;
-            if (before) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-    };
-    // ---- phase 2: dw w (merged) and dws w0 (solo) with their prefix sums; the person's crossing sample
-    float dwm[MAX_P], dAs[MAX_P], dDs[MAX_P], lc[MAX_P], lf[MAX_P];
-    int jst[MAX_P];
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        dwm[p] = dAs[p] = dDs[p] = lc[p] = lf[p] = 0.0f;
-        jst[p] = -1;
-        if (p < P && k[p] >= 0) {
-            float* te_l = base + p * per_person;
-            float* fe_l = te_l + S;
-            float* pf_l = fe_l + S;
-            float* gm_l = pf_l + S + 1;
-            float* gs_l = gm_l + S + 1;
-            const size_t o = (size_t)r * P + p;
-            const float t0 = z[p][(size_t)k[p] * n_z];
-            dwm[p] = dD + (d_depth_person ? d_depth_person[o] : 0.0f);
-            dAs[p] = d_acc_solo ? d_acc_solo[o] : 0.0f;
-            dDs[p] = d_depth_solo ? d_depth_solo[o] : 0.0f;
-            float carry_m = 0.f, carry_s = 0.f;
-            if (lane == 0) gm_l[0] = gs_l[0] = 0.f;
-            float s_te = FLT_MAX, s_i = FLT_MAX;               // this lane's solo candidate, key (te, sample)
-            for (int i0 = 0; i0 < S; i0 += 64) {
-                const int i = i0 + lane;
-                float gm = 0.f, gs = 0.f;
-                if (i < S) {
-                    const float te = te_l[i], fe = fe_l[i];
-                    const float ts = i > 0 ? te_l[i - 1] : t0;
-                    const float Es = pf_l[i];
-                    const float a = 1.0f - expf(-fe), tm = 0.5f * (ts + te);
-                    if (merged) {
-                        float E = Es;
-#pragma unroll
-                        for (int q = 0; q < MAX_P; ++q)
-                            if (q < P && q != p && k[q] >= 0) E += (base + q * per_person + 2 * S)[rank_in(q, p, te)];
-                        gm = dwm[p] * tm * a * expf(-E);
-                    }
-                    gs = (dAs[p] + dDs[p] * tm) * a * expf(-Es);
-                    if (Es + fe >= L && te < s_te) { s_te = te; s_i = (float)i; }
-                }
-                float tot;
-                float ex = mp::wave_excl_scan(gm, tot);
-                if (i < S) gm_l[i + 1] = carry_m + ex + gm;
-                carry_m += tot;
-                ex = mp::wave_excl_scan(gs, tot);
-                if (i < S) gs_l[i + 1] = carry_s + ex + gs;
-                carry_s += tot;
-            }
-            const float g = d_depth_solo_level ? d_depth_solo_level[o] : 0.0f;
-            const float b_te = mp::wmin(s_te);
-            if (g != 0.0f && b_te < FLT_MAX) {
-                const int j = (int)mp::wmin(s_te == b_te ? s_i : FLT_MAX);
-                const float fe = fe_l[j];
-                const float f = fe > 0.f ? (L - pf_l[j]) / fe : 0.f;
-                if (f > 0.f && f < 1.f) {
-                    jst[p] = j;
-                    lc[p] = g * (te_l[j] - (j > 0 ? te_l[j - 1] : t0)) / fe;
-                    lf[p] = f;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase 3: adjoints of the free energies -> sdf and beta
-    float dbeta_local = 0.0f;
-#pragma unroll
-    for (int p = 0; p < MAX_P; ++p) {
-        if (p < P && k[p] >= 0) {
-            const float* te_l = base + p * per_person;
-            const float* fe_l = te_l + S;
-            const float* pf_l = fe_l + S;
-            const float* gm_l = pf_l + S + 1;
-            const float* gs_l = gm_l + S + 1;
-            const float* zr = z[p] + (size_t)k[p] * n_z;
-            for (int i = lane; i < S; i += 64) {
-                const float te = te_l[i], fe = fe_l[i], ts = zr[i];
-                const float Es = pf_l[i], ex = expf(-fe), tm = 0.5f * (ts + te);
-                float dfe = (dAs[p] + dDs[p] * tm) * expf(-Es) * ex - (gs_l[S] - gs_l[i + 1]);
-                if (merged) {
-                    float E = Es;
-                    float suffix = gm_l[S] - gm_l[i + 1];
-#pragma unroll
-                    for (int q = 0; q < MAX_P; ++q)
-                        if (q < P && q != p && k[q] >= 0) {
-                            const int lo = rank_in(q, p, te);
-                            const float* pq = base + q * per_person + 2 * S;
-                            E += pq[lo];
-                            suffix += (pq + S + 1)[S] - (pq + S + 1)[lo];
-                        }
-                    dfe += dwm[p] * tm * expf(-E) * ex - suffix;
-                }
-                if (i < jst[p]) dfe -= lc[p];
-                else if (i == jst[p]) dfe -= lc[p] * lf[p];
-                const size_t qi = (size_t)k[p] * S + i;
-                const float s = sdf[p][qi];
-                const float dsig = dfe * (te - ts);
-                // d sigma / d sdf and d sigma / d beta (density.py:20-29), as in k_composite_bwd
-                const float eab = expf(-fabsf(s) / beta);
-                const float dsdf = -(0.5f / (beta * beta)) * eab;
-                float dbe;
-                if (s > 0.f) dbe = (0.5f / (beta * beta)) * eab * (s / beta - 1.0f);
-                else if (s < 0.f) dbe = -1.0f / (beta * beta) + (0.5f / (beta * beta)) * eab * (1.0f + s / beta);
-                else dbe = -0.5f / (beta * beta);
-                d_sdf[p][qi] += dsig * dsdf;
-                dbeta_local += dsig * dbe;
-            }
-        }
-    }
-    dbeta_local = mp::wsum(dbeta_local);
-    if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
 }
 
 // ---- background compositing (multiply.py:682-696) forward with stash-free backward; one thread per ray
@@ -1118,40 +772,6 @@ int mp_tr_hoist_bwd(const float* db2, int out_dim, int in_dim, int c0, int n, co
 }
 int mp_tr_colsum(const float* dZ, int ld, int rows, int C, float* db, void* stream) {
     hipLaunchKernelGGL(k_colsum, dim3(C), dim3(256), 0, ST, dZ, ld, rows, C, db);
-    return (int)hipGetLastError();
-}
-int mp_tr_composite_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
-                        const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
-                        const float* d_rgb_values, const float* d_acc, const float* d_acc_person, float* const* d_sdf,
-                        float* const* d_rgb, float* d_bg_rgb, float* d_beta, void* stream) {
-    if (n_person > MAX_P) return -1;
-    if (n_rays <= 0) return 0;
-    const int per_wave = n_person * (5 * (n_z - 1) + 2) * (int)sizeof(float);
-    if (per_wave > 160 * 1024) return -2;
-    int wpb = 4;
-    while (wpb > 1 && wpb * per_wave > 160 * 1024) wpb >>= 1;
-    MP_LDS_ATTR((k_composite_bwd), 160 * 1024);
-    hipLaunchKernelGGL(k_composite_bwd, dim3((n_rays + wpb - 1) / wpb), dim3(64 * wpb), wpb * per_wave, ST, n_rays, n_person, n_z,
-                       inv_index, z, sdf, rgb, beta, bg_rgb, d_rgb_values, d_acc, d_acc_person, d_sdf, d_rgb, d_bg_rgb, d_beta);
-    return (int)hipGetLastError();
-}
-int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
-                                 const float* const* sdf, const float* beta, float level, const float* d_depth,
-                                 const float* d_depth_person, const float* d_acc_solo, const float* d_depth_solo,
-                                 const float* d_depth_solo_level, float* const* d_sdf, float* d_beta, void* stream) {
-    if (n_person > MAX_P || n_person < 0) return -1;
-    if (!(level > 0.f && level < 1.f)) return -3;
-    if (n_rays <= 0) return 0;
-    if (!d_depth && !d_depth_person && !d_acc_solo && !d_depth_solo && !d_depth_solo_level) return 0;
-    const int per_wave = n_person * (5 * (n_z - 1) + 3) * (int)sizeof(float);
-    if (per_wave > 160 * 1024) return -2;
-    int wpb = 4;
-    while (wpb > 1 && wpb * per_wave > 160 * 1024) wpb >>= 1;
-    MP_LDS_ATTR((k_composite_geometry_bwd), 160 * 1024);
-    const float L = (float)-log1p(-(double)level);
-    hipLaunchKernelGGL(k_composite_geometry_bwd, dim3((n_rays + wpb - 1) / wpb), dim3(64 * wpb), wpb * per_wave, ST, n_rays,
-                       n_person, n_z, inv_index, z, sdf, beta, L, d_depth, d_depth_person, d_acc_solo, d_depth_solo,
-                       d_depth_solo_level, d_sdf, d_beta);
     return (int)hipGetLastError();
 }
 int mp_tr_bg_points(const float* dirs, const float* cam, const float* zbg, int R, int NBG, float radius, float* pts,

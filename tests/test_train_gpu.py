@@ -327,15 +327,25 @@ def test_fused_background_kernels_against_autograd(P, monkeypatch):
         assert rel(n + " vs autograd", got[id(p)].reshape(ww.shape), ww) < 5e-4, n
 
 
-def test_composite_backward():
-    """mp_composite / mp_tr_composite_bwd vs the oracle's packed compositing under autograd (two persons, rays hit by
-    both, one or none; includes the exclusive background transmittance and d beta)."""
+def _composite_hits(n_person, R):
+    """two persons: rays hit by both, one or none; three: geometry_reference.RAGGED_HITS (0 / 1 / 2 / 3 persons per ray); eight: the
+    person limit, geometry_train_reference.case_hits"""
+    from tests import geometry_reference as G, geometry_train_reference as GT
+    if n_person == 2:
+        return [torch.arange(0, 50), torch.arange(30, 65)]
+    return [torch.as_tensor(np.asarray(h)) for h in (G.RAGGED_HITS if n_person == 3 else GT.case_hits(R, n_person))]
+
+
+@pytest.mark.parametrize("n_person,R,NZ", [(2, 70, 98), (3, 70, 98), (8, 13, 130)])
+def test_composite_backward(n_person, R, NZ):
+    """mp_composite / mp_tr_composite_bwd vs the oracle's packed compositing under autograd (includes the exclusive background
+    transmittance and d beta).  Two and three persons with S = 97 samples: two 64-lane passes; eight persons, the limit, with
+    S = 129: three passes."""
     from multiply_amd import train as T
     L = T.hip.lib()
     torch.manual_seed(4)
-    R, NZ = 70, 98
     S = NZ - 1
-    hit = [torch.arange(0, 50), torch.arange(30, 65)]
+    hit = _composite_hits(n_person, R)
     z = [torch.sort(torch.rand(len(h), NZ) * 2.0 + 1.0, dim=1)[0] for h in hit]
     sdf = [torch.randn(len(h), S) * 0.05 for h in hit]
     rgb = [torch.rand(len(h), S, 3) for h in hit]
@@ -353,31 +363,31 @@ def test_composite_backward():
     beta = cu(beta_p.reshape(1))
     tabs = [T._table(ts, "cuda") for ts in (inv, zc, sc, rc, nc)]
     f = lambda *s: torch.empty(*s, device="cuda")
-    rgb_v, fg_v, nrm_v, acc, accp, bgT = f(R, 3), f(R, 3), f(R, 3), f(R), f(R, 2), f(R)
-    T._chk(L.mp_composite(R, 2, NZ, *[T._p(t) for t in tabs], T._p(beta), T._p(bgc), T._p(rgb_v), T._p(fg_v), T._p(nrm_v),
+    rgb_v, fg_v, nrm_v, acc, accp, bgT = f(R, 3), f(R, 3), f(R, 3), f(R), f(R, n_person), f(R)
+    T._chk(L.mp_composite(R, n_person, NZ, *[T._p(t) for t in tabs], T._p(beta), T._p(bgc), T._p(rgb_v), T._p(fg_v), T._p(nrm_v),
                           T._p(acc), T._p(accp), T._p(bgT), T.hip.stream()), "composite")
     # oracle
     sdf_g = [t.clone().requires_grad_(True) for t in sdf]
     rgb_g = [t.clone().requires_grad_(True) for t in rgb]
     bg_g, beta_g = bg.clone().requires_grad_(True), beta_p.clone().requires_grad_(True)
     fg_o, nrm_o, acc_o, accp_o, bgT_o = O.packed_composite(R, hit, [t[:, :-1] for t in z], [t[:, -1] for t in z], sdf_g, rgb_g,
-                                                           nrm, beta_g, [0, 1])
+                                                           nrm, beta_g, list(range(n_person)))
     rgb_o = fg_o + bgT_o[:, None] * bg_g
     assert rel("rgb_values", rgb_v, rgb_o.detach()) < 1e-5
     assert rel("acc", acc, acc_o.detach()) < 1e-5 and rel("acc_person", accp, accp_o.detach()) < 1e-5
     assert rel("bg_T", bgT, bgT_o.detach()) < 1e-5 and rel("normal_values", nrm_v, nrm_o.detach()) < 1e-5
-    a_rgb, a_acc, a_accp = torch.randn(R, 3), torch.randn(R), torch.randn(R, 2)
+    a_rgb, a_acc, a_accp = torch.randn(R, 3), torch.randn(R), torch.randn(R, n_person)
     want = torch.autograd.grad((rgb_o * a_rgb).sum() + (acc_o * a_acc).sum() + (accp_o * a_accp).sum(),
                                sdf_g + rgb_g + [bg_g, beta_g])
     dsdf = [torch.zeros_like(t) for t in sc]; drgb = [torch.zeros_like(t) for t in rc]
     dbg, dbeta = torch.zeros(R, 3, device="cuda"), torch.zeros(1, device="cuda")
     td, tr = T._table(dsdf, "cuda"), T._table(drgb, "cuda")
     g_rgb, g_acc, g_accp = cu(a_rgb), cu(a_acc), cu(a_accp)      # keep the device copies alive across the launch
-    T._chk(L.mp_tr_composite_bwd(R, 2, NZ, T._p(tabs[0]), T._p(tabs[1]), T._p(tabs[2]), T._p(tabs[3]), T._p(beta), T._p(bgc),
+    T._chk(L.mp_tr_composite_bwd(R, n_person, NZ, T._p(tabs[0]), T._p(tabs[1]), T._p(tabs[2]), T._p(tabs[3]), T._p(beta), T._p(bgc),
                                  T._p(g_rgb), T._p(g_acc), T._p(g_accp), T._p(td), T._p(tr), T._p(dbg), T._p(dbeta),
                                  T.hip.stream()), "composite_bwd")
-    for p in range(2):
+    for p in range(n_person):
         assert rel(f"d sdf[{p}]", dsdf[p].reshape(-1, S), want[p]) < 1e-4
-        assert rel(f"d rgb[{p}]", drgb[p].reshape(-1, S, 3), want[2 + p]) < 1e-5
-    assert rel("d bg_rgb", dbg, want[4]) < 1e-5
-    assert rel("d beta", dbeta.reshape(()), want[5]) < 1e-4
+        assert rel(f"d rgb[{p}]", drgb[p].reshape(-1, S, 3), want[n_person + p]) < 1e-5
+    assert rel("d bg_rgb", dbg, want[2 * n_person]) < 1e-5
+    assert rel("d beta", dbeta.reshape(()), want[2 * n_person + 1]) < 1e-4
