@@ -677,6 +677,35 @@ int mp_fit_loss(const float* sdf, const float* grad, const float* normals, const
                 float w_surface, float w_normal, float w_distance, float w_eikonal, float truncation, float* terms,
                 float* d_sdf, float* d_grad, void* stream);
 
+/* ---- mesh-free interpenetration term on the persons' SDF fields (csrc/penetration.hip; multiply_amd/train.py Interpenetration;
+ * the reference's mesh term: multiply_model.py:521-551).  Person p's n probe points (posed SMPL vertices) are warped into
+ * partner q's canonical space and penalised by q's signed distance where it is negative.  Every call covers ALL ordered pairs
+ * (p, q), p != q, of n_person persons (2 .. 8, the compositing limit); pair index p * n_person + q.  Per-person inputs are device
+ * arrays of n_person device pointers; per-pair arrays are [n_person^2][n] rows.  Diagonal pairs are never read or written.
+ * Status -1 without a launch: n < 0, n_person outside 2 .. 8, a NULL argument; 0 without a launch: n == 0.  No atomics anywhere:
+ * every result is bit-identical from call to call.
+ *   mp_pen_probe       : pts[p] [n][3]; vsorted[q] / cbound[q] (mp_knn_build) and blend_table[q] (mp_blend_table) of q's POSED
+ *                        vertices.  Exact nearest vertex of q within the outlier radius (the capped search and the rule of
+ *                        mp_warp_inverse in eval mode: outlier = sqrtf(fminf(d^2, 4)) > 0.1f, ties -> lowest vertex id) ->
+ *                        probed [pair][n] (1 = not an outlier; written for every point), and for the probed points only
+ *                        nn [pair][n] (the vertex) and xc [pair][n][3] = I_nn (x - c_nn); list [pair][0 .. count[pair]) = the
+ *                        probed point ids in ASCENDING order, count [pair] on the device.
+ *   mp_pen_loss        : sdf[pair] = q's signed distance at the list's entries ([count[pair]] floats; NULL allowed where the
+ *                        count is 0) -> loss [pair] = sum of s^2 over {s < 0} (summed in double in a fixed order), active [pair]
+ *                        = how many, seed[pair] [count[pair]] = 2 s [s < 0]; loss and active of the diagonal are written as 0.
+ *                        n = the row length count[] is clamped to.
+ *   mp_pen_scatter_bwd : dverts[p] [n_verts][3] += sum over q (ascending) and over the entries e (ascending) of pair (p, q) whose
+ *                        point was drawn from vertex v (pen_idx[p][list[pair][e]] == v) of I_nn^T dxc[pair][e]; I_nn from
+ *                        blend_table[q] by nn.  One thread per vertex; the draw may repeat a vertex. */
+int mp_pen_probe(const float* const* pts, const float* const* vsorted, const float* const* cbound,
+                 const float* const* blend_table, int n_person, int n, unsigned char* probed, int* nn, float* xc, int* list,
+                 int* count, void* stream);
+int mp_pen_loss(const float* const* sdf, const int* count, int n_person, int n, float* loss, int* active, float* const* seed,
+                void* stream);
+int mp_pen_scatter_bwd(const int* const* pen_idx, const int* list, const int* count, const int* nn,
+                       const float* const* blend_table, const float* const* dxc, int n_person, int n, int n_verts,
+                       float* const* dverts, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

@@ -129,6 +129,32 @@ def interpenetration_loss(vertex_list, face_list, num_points=5120, draws=None, m
     return total
 
 
+def field_interpenetration(model, inputs, draws=None):
+    """The mesh-free interpenetration term of one frame as a diagnostic (eval mode, no gradients): train.Interpenetration on the
+    persons' SDF fields -- one setup, the probe / loss launches and the value query, no mesh, no host read.  inputs: a forward's dict (uv,
+    intrinsics, pose, smpl_*).  draws: {'person': {p: {'pen_idx': vertex ids}}}; None = model.interpenetration_points random
+    vertices per person.  -> {'loss' (1,), 'pair_loss' (P,P), 'probed' (P,P) int, 'active' (P,P) int}, row p = the probing person,
+    column q = the person whose field is probed.  The total is symmetric under swapping the roles; the matrix is not."""
+    from . import train as T
+    assert not model.training, "field_interpenetration is an eval-mode entry point"
+    with torch.no_grad():
+        cx = model._setup(inputs, -1, False)
+        persons, dev = cx["persons"], cx["dev"]
+        P = len(persons)
+        if P < 2:
+            z = torch.zeros(P, P, device=dev)
+            return {"loss": torch.zeros(1, device=dev), "pair_loss": z, "probed": z.int(), "active": z.int()}
+        if draws is None:
+            nvs = [model.smpl_server_list[p].verts_c.reshape(-1, 3).shape[0] for p in persons]
+            pen = T._random_prefixes(nvs, min(int(model.interpenetration_points), min(nvs)), dev, None)
+            idx = {p: pen[n] for n, p in enumerate(persons)}
+        else:
+            idx = {p: draws["person"][p]["pen_idx"] for p in persons}
+        term = T.Interpenetration(model, cx, idx)
+        return {"loss": term.loss, "pair_loss": term.pair_loss.reshape(P, P), "active": term.active.reshape(P, P),
+                "probed": term.count.reshape(P, P)}
+
+
 def posed_meshes(model, inputs, use_smpl_mesh=False, res_up=2, meshes=None):
     """The per-person meshes of one frame in the renderer's units (divided by the SMPL scale): the SMPL surface
     (multiply_model.py:823-829, epochs <= 190) or the person's canonical zero level set, posed (:586-620, :831-848).
@@ -236,7 +262,7 @@ def body_model_inputs(body_model_list, frame_idx):
 
 
 def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, it_per_loop, lr, loss_opt=None, depth_pose=False,
-                    depth_cond_zero=False, res_up=2, depth_source="mesh"):
+                    depth_cond_zero=False, res_up=2, depth_source="mesh", interpenetration_source="mesh"):
     """One frame of the trainer's depth-refinement stage (multiply_model.py:230-486): the persons' canonical meshes are
     extracted once, then `it_per_loop` Adam steps on the frame's body-model rows -- the translations only, or every body
     parameter with depth_pose -- minimise  render loss (a 512-ray training forward of the scene model) + depth-order loss
@@ -250,13 +276,20 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
     depth_source='volume': no canonical mesh is extracted and no z-buffer is rendered.  The order term is ray_depth_order_loss of
     the iteration's own training forward (Multiply.train_geometry, set for the loop and restored), on the iteration's rays and
     their sam_mask labels, with z_scale from the rays' directions; its gradient reaches the body rows through the volume
-    renderer's own adjoint.  The interpenetration term needs meshes: a non-zero interpenetration_loss_weight raises ValueError."""
+    renderer's own adjoint.  The mesh interpenetration term needs meshes: with interpenetration_source='mesh' a non-zero
+    interpenetration_loss_weight raises ValueError.
+
+    interpenetration_source='field' (either depth_source): the term is the training forward's own 'interpenetration_loss'
+    (Multiply.train_interpenetration, set for the loop and restored: the persons' posed SMPL vertices probed against each other's
+    SDF fields, no mesh), times interpenetration_loss_weight and the epoch fade; its gradient reaches the body rows only."""
     from .mesh import canonical_mesh
     assert depth_source in ("mesh", "volume"), depth_source
+    assert interpenetration_source in ("mesh", "field"), interpenetration_source
     loss_opt = loss_opt or {}
-    volume = depth_source == "volume"
-    if volume and loss_opt.get("interpenetration_loss_weight", 0.0) != 0:
-        raise ValueError("depth_source='volume' extracts no meshes: the interpenetration term (interpenetration_loss_weight != 0) needs them")
+    volume, field = depth_source == "volume", interpenetration_source == "field"
+    if volume and not field and loss_opt.get("interpenetration_loss_weight", 0.0) != 0:
+        raise ValueError("depth_source='volume' extracts no meshes: the mesh interpenetration term (interpenetration_loss_weight != 0) "
+                         "needs them; interpenetration_source='field' does not")
     params = list(p for bm in body_model_list for p in bm.parameters()) if depth_pose else [bm.transl.weight for bm in body_model_list]
     saved = [p.requires_grad for p in params]
     for p in params:
@@ -274,10 +307,12 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
                 meshes.append(canonical_mesh(model, p, cond=cond, res_up=res_up))
     faces = [m["faces"][None] for m in meshes]
     fade = 1 - min(DEPTH_LOSS_MILESTONE, epoch) / DEPTH_LOSS_MILESTONE
-    was_training, was_geometry = model.training, model.train_geometry
+    was_training, was_geometry, was_pen = model.training, model.train_geometry, model.train_interpenetration
     model.train()
     if volume:
         model.train_geometry = True
+    if field:
+        model.train_interpenetration = True
     history = []
     for _ in range(it_per_loop):
         smp_in, smp_tg = sample_fn()
@@ -299,15 +334,18 @@ def opt_depth_frame(model, body_model_list, loss_fn, inputs, sample_fn, epoch, i
                 so = server(scale[:, p], trans[:, p], pose[:, p], shape[:, p])
                 verts.append((1 / scale[:, p].squeeze()) * deformed_mesh_vertices(model, meshes[p]["vertices"][None], so["smpl_tfs"], p))
             depth = [d[0, :, :, 0] for d in renderer.render_multiple_depth_map(verts, faces)]
-            inter = interpenetration_loss(verts, faces, mesh_index_mode=model.mesh_index_mode)
-            inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
+            if not field:
+                inter = interpenetration_loss(verts, faces, mesh_index_mode=model.mesh_index_mode)
+                inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * inter
             order = depth_order_loss(depth, inputs["org_sam_mask"], epoch, loss_opt.get("depth_order_weight", 0.005))
+        if field:
+            inter = loss_opt.get("interpenetration_loss_weight", 0.0) * fade * out["interpenetration_loss"]
         (inter.sum() + order + render.sum()).backward()
         opt.step()
         history.append({"render_loss": render.detach().reshape(()), "depth_order_loss": order.detach().reshape(()),
                         "interpenetration_loss": inter.detach().reshape(())})
     for p, r in zip(params, saved):
         p.requires_grad_(r)
-    model.train_geometry = was_geometry
+    model.train_geometry, model.train_interpenetration = was_geometry, was_pen
     model.train(was_training)
     return history

@@ -22,7 +22,10 @@ Extensions that do not exist in the reference (all optional, defaults reproduce 
     (depth_values, depth_person_list, depth_level_values, front_person, acc_person_solo_list, depth_person_solo_list,
     depth_person_solo_level_list: _composite_geometry).  Off by default: exactly the reference's keys;
   * self.train_geometry : training mode only, the same seven keys on the training forward's rays, differentiable except
-    depth_level_values / front_person (train.TrainGraph, mp_tr_composite_geometry_bwd).  Off by default.
+    depth_level_values / front_person (train.TrainGraph, mp_tr_composite_geometry_bwd).  Off by default;
+  * self.train_interpenetration / self.interpenetration_points : training mode only, the dict's 'interpenetration_loss' (a
+    dead zeros(1) slot in the reference, multiply.py:237,581) carries the mesh-free interpenetration term on the persons' SDF
+    fields (train.Interpenetration, csrc/penetration.hip).  Off by default.
 """
 import ctypes as C
 import os
@@ -49,6 +52,12 @@ class Multiply(nn.Module):
     # and the per-person solo level depth are differentiable (sdf weights, density.beta, and the body inputs through the pose path);
     # depth_level_values / front_person are not.  geometry_level is shared.  Not built for person-sharded training.
     train_geometry = False
+    # training mode only: forward_train's 'interpenetration_loss' carries the mesh-free interpenetration term of the call's persons
+    # (train.Interpenetration: posed SMPL vertices of p probed against q's SDF field), raw, differentiable w.r.t. the body inputs
+    # only; interpenetration_points vertices per person are drawn (the reference's num_pixels).  Off: zeros(1), no launch, no draw.
+    # Not built for person-sharded training.
+    train_interpenetration = False
+    interpenetration_points = 5120
 
     def __init__(self, opt, betas_path, smpl_tables=None, gender_list=None):
         super().__init__()

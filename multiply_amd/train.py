@@ -773,6 +773,22 @@ class ImplicitTrainFused(_FusedImplicit):
             L.mp_tf_sdf_dx(A, P, lw0.W, lw0.in_dim, lw4.W, lw4.in_dim, self.x, self.dx, st)
         return self._weight_grads(dfeat, tn_groups, gradient_sweep=True)
 
+    def points_adjoint(self, dsdf):
+        """d x [P][3] of a term that reads the sdf column alone (dsdf [P] its adjoint) with the network held CONSTANT: the adjoint
+        w.r.t. the activations on zero dfeat / dG (mp_tf_sdf_bwd; the sdf row's own gradient goes to scratch), then the points'
+        adjoint from its stash (mp_tf_sdf_dx).  No weight-gradient contraction runs and no accumulator of the iteration is
+        touched (the interpenetration term: the partner's net must not answer it by shrinking)."""
+        L, st = hip.lib(), hip.stream()
+        P, E, A = self.P, self.E, self.arena
+        f32 = dict(dtype=F32, device=self.x.device)
+        A[self.o_dG:self.o_dG + E * P].zero_()          # the gradient sweep has no upstream here
+        scratch = torch.zeros(257, **f32)               # d w8 [256], d b8 [1]
+        L.mp_tf_sdf_bwd(self.fs.wpack, self.w8, A, P, torch.zeros(P, 256, **f32), dsdf, scratch, off(scratch, 256), st)
+        dx = torch.zeros(P, 3, **f32)
+        lw0, lw4 = self.lins[0], self.lins[4]
+        L.mp_tf_sdf_dx(A, P, lw0.W, lw0.in_dim, lw4.W, lw4.in_dim, self.x, dx, st)
+        return dx
+
 
 class ImplicitTrainFusedBG(_FusedImplicit):
     """ImplicitTrain(fwd=False)'s arithmetic for the background ImplicitNet on the layer-fused kernels (csrc/tfuse.hip
@@ -1011,6 +1027,12 @@ def make_draws(model, cx, gen=None):
         nv_all = [v.shape[1] for v in model.mesh_v_cano_list]
         zp = _random_prefixes(nv_all * len(persons), min(ZERO_POSE_SAMPLES, min(nv_all)), dev, gen).reshape(len(persons), len(nv_all), -1)
         draws["zp_idx"] = {(q, p): zp[n, p] for n, q in enumerate(persons) for p in range(len(nv_all))}
+    # the interpenetration term's probe vertices (Multiply.train_interpenetration): the LAST draw, and only with the flag on -- a
+    # seeded run with the flag off consumes the generator exactly as before the term existed
+    if model.training and getattr(model, "train_interpenetration", False) and len(persons) > 1:
+        pen = _random_prefixes(nvs, min(int(model.interpenetration_points), min(nvs)), dev, gen)
+        for n, p in enumerate(persons):
+            draws["person"][p]["pen_idx"] = pen[n]
     return draws
 
 
@@ -1044,6 +1066,96 @@ def colour_evaluator(net, XA, it, n, cond_vec, lins):
     return (RenderTrainFused if fused else RenderTrain)(net, XA, it.feat_ptr, it.feat_ld, n, cond_vec, lins=lins)
 
 
+class Interpenetration:
+    """The mesh-free interpenetration term of one call (the reference's mesh term: multiply_model.py:521-551).
+    For every ORDERED pair (p, q), p != q, of the call's persons: person p's posed SMPL vertices pen_idx[p] are probe points; a
+    point whose exact nearest posed vertex of q lies within the 0.1 outlier radius (mp_pen_probe: the rule and the capped search of
+    mp_warp_inverse in eval mode) is warped into q's canonical space, x_c = I_nn (x - c_nn), and costs s^2 where q's signed
+    distance s = sdf_q(x_c; cond_q) is negative.  .loss (1,) = the RAW sum over all pairs; .pair_loss / .active / .count [P*P]
+    (device; count = the probed points per pair).
+    The SDF runs on the fused training kernels (split-bf16, fp32 accumulation): ImplicitTrainFused on the compact entries of all
+    p != q, one slot of n rows per p, concatenated per q and PADDED to capacity with points at the origin (their seed is zero, so
+    is their adjoint): no host read of the counts, the same (P - 1) n rows in every iteration.  keep: the evaluators' stashes
+    stay alive for backward(), which returns per person the term's share (d tfs [24][16], d posed vertices [V][3]) -- the warp
+    path through q's transforms (mp_tr_warp_bwd) and the vertex path d x = I_nn^T d x_c on p's drawn vertices
+    (mp_pen_scatter_bwd).  Networks and conditionings are constants of the term."""
+
+    def __init__(self, model, cx, pen_idx, lins_of=None, keep=False):
+        """pen_idx {person: vertex ids (n,)}; lins_of(net) -> the shared LinP list of a TrainState (None: standalone layers)"""
+        L, st = hip.lib(), hip.stream()
+        self.model, self.cx = model, cx
+        self.persons = persons = list(cx["persons"])
+        self.P = P = len(persons)
+        dev = cx["dev"]
+        f32, i32 = dict(dtype=F32, device=dev), dict(dtype=torch.int32, device=dev)
+        nets = [model.foreground_implicit_network_list[q] for q in persons]
+        if TRAIN_PRECISION != "bf16x3" or not all(fused_sdf_supported(net) for net in nets):
+            raise NotImplementedError("the interpenetration term evaluates the SDF on the fused training kernels (csrc/tfuse.hip): "
+                                      "split-bf16 arithmetic (MP_TRAIN_PRECISION=bf16x3) and the shipped ImplicitNet shape only")
+        per = [cx["per"][p] for p in persons]
+        idx64 = [pen_idx[p].to(dev).long().reshape(-1) for p in persons]
+        self.n = n = int(idx64[0].numel())
+        assert all(int(i.numel()) == n for i in idx64), "every person probes with the same number of vertices"
+        self.idx = [i.to(torch.int32).contiguous() for i in idx64]
+        PP = P * P
+        self.count = torch.zeros(PP, **i32)                      # (the diagonal is never written)
+        self.pair_loss, self.active = torch.zeros(PP, **f32), torch.zeros(PP, **i32)
+        self.items = []
+        if n == 0:
+            self.loss = torch.zeros(1, **f32)
+            return
+        pts = [pp["verts"].index_select(0, i).contiguous() for pp, i in zip(per, idx64)]
+        self.btabs = [pp["btab"] for pp in per]
+        self.nn = torch.empty(PP, n, **i32)
+        self.list = torch.zeros(PP, n, **i32)                    # zero-filled: a row's padding names point 0, masked below
+        probed = torch.empty(PP, n, dtype=torch.uint8, device=dev)
+        xc = torch.empty(PP, n, 3, **f32)
+        L.mp_pen_probe(_table(pts, dev), _table([pp["vsorted"] for pp in per], dev), _table([pp["cbound"] for pp in per], dev),
+                       _table(self.btabs, dev), P, n, probed, self.nn, xc, self.list, self.count, st)
+        ar = torch.arange(n, device=dev)
+        but = lambda t, b: torch.cat([t[:b, b], t[b + 1:, b]])   # column b of a [P][P][..] array without the diagonal: the slots of q
+        sdf_at, seed_at = [0] * PP, [0] * PP
+        for b, q in enumerate(persons):
+            sel = but(self.list.view(P, P, n), b).long()                                         # (P - 1, n) point ids
+            valid = ar[None, :] < but(self.count.view(P, P), b)[:, None]
+            X = torch.gather(but(xc.view(P, P, n, 3), b), 1, sel[..., None].expand(-1, -1, 3))
+            X = torch.where(valid[..., None], X, X.new_zeros(())).reshape(-1, 3).contiguous()    # (unwritten rows never get through)
+            nnq = torch.where(valid, torch.gather(but(self.nn.view(P, P, n), b), 1, sel), 0).to(torch.int32).reshape(-1).contiguous()
+            it = ImplicitTrainFused(nets[b], X, cx["per"][q]["cond"], lins=None if lins_of is None else lins_of(nets[b]))
+            seed = torch.zeros(X.shape[0], **f32)
+            for slot, a in enumerate(a for a in range(P) if a != b):
+                sdf_at[a * P + b], seed_at[a * P + b] = it.sdf.data_ptr() + 4 * slot * n, seed.data_ptr() + 4 * slot * n
+            self.items.append((q, b, it, X, nnq, seed))
+        L.mp_pen_loss(hip.device_ints(sdf_at, dev), self.count, P, n, self.pair_loss, self.active, hip.device_ints(seed_at, dev), st)
+        self.loss = self.pair_loss.sum().reshape(1)
+        if not keep:                                             # value only: no stash outlives the forward
+            self.items = []
+
+    def backward(self, d_loss):
+        """-> {person: (d tfs [24][16], d posed vertices [V][3])}: the adjoint with the seed 2 s [s < 0], scaled once by d_loss"""
+        L, st = hip.lib(), hip.stream()
+        m, cx, P, n = self.model, self.cx, self.P, self.n
+        dev = cx["dev"]
+        f32 = dict(dtype=F32, device=dev)
+        scale = d_loss.reshape(()).to(dev, F32)
+        V = m.smpl_server_list[self.persons[0]].verts_c.reshape(-1, 3).shape[0]
+        shares = {p: [torch.zeros(24, 16, **f32), torch.zeros(V, 3, **f32)] for p in self.persons}
+        if not self.items:
+            return {p: tuple(s) for p, s in shares.items()}
+        dxc_at, held = [0] * (P * P), []
+        for q, b, it, X, nnq, seed in self.items:
+            dxc = it.points_adjoint(seed)                        # (exact zeros on the padding and on the inactive entries)
+            L.mp_tr_warp_bwd(X, dxc, None, None, nnq, None, X.shape[0], m.smpl_server_list[q].tables.lbs_weights, cx["per"][q]["tfs"],
+                             shares[q][0], st)
+            for slot, a in enumerate(a for a in range(P) if a != b):
+                dxc_at[a * P + b] = dxc.data_ptr() + 12 * slot * n
+            held.append(dxc)
+        dverts = [shares[p][1] for p in self.persons]
+        L.mp_pen_scatter_bwd(_table(self.idx, dev), self.list, self.count, self.nn, _table(self.btabs, dev), hip.device_ints(dxc_at, dev),
+                             P, n, V, _table(dverts, dev), st)
+        return {p: (s[0] * scale, s[1] * scale) for p, s in shares.items()}
+
+
 class TrainGraph:
     """Everything one training forward keeps for its backward."""
 
@@ -1059,6 +1171,10 @@ class TrainGraph:
         self.reg_surf = {}              # person -> (d tfs [24][16], d posed vertices [V][3]) of the surface term (pose optimisation)
         # Multiply.train_geometry: the node also returns the volume-rendered depths of its rays (GEOMETRY_KEYS), with an adjoint
         self.geometry = bool(model.training and getattr(model, "train_geometry", False))
+        # Multiply.train_interpenetration: the node also returns the mesh-free interpenetration term (Interpenetration), whose
+        # adjoint reaches the body-model inputs and nothing else
+        self.pen_on = bool(model.training and getattr(model, "train_interpenetration", False))
+        self.pen, self.pen_loss = None, None
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def run(self):
@@ -1079,6 +1195,8 @@ class TrainGraph:
         local = [self._person_forward(n, p, sampled.get(p)) for n, p in enumerate(persons)]
         if m.smpl_surface_weight > 0 or m.zero_pose_weight > 0:
             self._regularisers_forward()
+        if self.pen_on:
+            self._interpenetration_forward()
         # the composited persons, in person order: one record each, the same fields whether this rank evaluated the person or not
         self.all_persons, self.composited, self.ray_slice = list(persons), local, (0, cx["R"])
         if self.shard is not None:
@@ -1280,6 +1398,8 @@ class TrainGraph:
         outs = (rgb_values, normal_values, acc_map, acc_person, grad_theta)
         if self.reg_items:
             outs = outs + self.reg_losses
+        if self.pen_on:
+            outs, self.pen_loss = outs + (self.pen_loss,), None
         if self.geometry:
             outs = outs + self._composite_geometry()
         return outs
@@ -1393,13 +1513,41 @@ class TrainGraph:
                     # person q's conditioning = smpl_pose[q, 3:] / pi (multiply.py:270): the term's only path to the body-model inputs
                     self.reg_dcond[q] = dcond if q not in self.reg_dcond else self.reg_dcond[q] + dcond
 
+    # ---- the interpenetration term (Multiply.train_interpenetration) ---------------------------------------------------------
+    def _interpenetration_forward(self):
+        """the term of this call's persons on the iteration's shared weights; a single person has no pairs: zeros, no launch.
+        With no body input under optimisation the term is value-only and keeps no stash."""
+        cx = self.cx
+        if len(cx["persons"]) < 2:
+            self.pen_loss = torch.zeros(1, dtype=F32, device=cx["dev"])
+            return
+        missing = [p for p in cx["persons"] if "pen_idx" not in self.draws["person"][p]]
+        if missing:
+            raise KeyError(f"train_interpenetration: the draws of persons {missing} carry no 'pen_idx' (make_draws draws it with the flag on)")
+        pen = Interpenetration(self.model, cx, {p: self.draws["person"][p]["pen_idx"] for p in cx["persons"]},
+                               lins_of=lambda net: self.ts.lins[id(net)], keep=self.pose_grad)
+        # the loss becomes an output of the autograd node, which holds this graph: neither the graph nor the term may keep it
+        # (a reference cycle would keep the iteration's stashes alive until the garbage collector runs); _composite hands it over
+        self.pen_loss, pen.loss = pen.loss, None
+        self.pen = pen if self.pose_grad else None
+
+    def _interpenetration_backward(self, d_pen):
+        """the term's shares of d tfs / d posed vertices join the smpl_surface term's: ONE server.pose_backward per person"""
+        for p, (dtfs, dverts) in self.pen.backward(d_pen).items():
+            prev = self.reg_surf.get(p)
+            self.reg_surf[p] = (dtfs, dverts) if prev is None else (prev[0] + dtfs, prev[1] + dverts)
+
     # ---- backward -----------------------------------------------------------------------------------------------
-    def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None, d_geometry=None):
-        """-> {id(parameter): gradient}.  d_geometry: the upstream gradients of GEOMETRY_KEYS[:5] (train_geometry), None = no term"""
+    def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None, d_geometry=None, d_pen=None):
+        """-> {id(parameter): gradient}.  d_geometry: the upstream gradients of GEOMETRY_KEYS[:5] (train_geometry), None = no term;
+        d_pen: the upstream gradient of the interpenetration term (train_interpenetration), None = unused"""
         m, dev = self.model, self.cx["dev"]
         self.ts.start_backward()                  # this sweep's own accumulators / gradient buffer (TrainState.start_backward)
+        self.reg_dcond, self.reg_surf = {}, {}
         if self.reg_items:                        # before any finish_group retires a network's accumulators
             self._regularisers_backward(d_ssl, d_zpl)
+        if self.pen is not None and d_pen is not None:
+            self._interpenetration_backward(d_pen)
         self.zp = _ZP[0] = hip.ZeroPool(dev)      # this sweep's zero-initialised tensors: views of one zero-filled block
         dsdf_l, drgb_l, d_bg_rgb, d_beta = self._composite_backward(d_rgb_values, d_acc_map, d_acc_person, d_geometry)
         self.grads, self.pose_grads = {}, {}
@@ -1542,9 +1690,11 @@ class _TrainFn(torch.autograd.Function):
         ctx.graph, ctx.params = graph, params
         ctx.body = (smpl_pose, smpl_trans, smpl_shape)
         outs = graph.run()
-        if graph.geometry:
-            # the unused ones of the geometry outputs must arrive as None (a NULL pointer skips the term), not as zero tensors
+        if graph.geometry or graph.pen_on:
+            # the unused ones of the geometry outputs must arrive as None (a NULL pointer skips the term), not as zero tensors;
+            # an unused interpenetration term likewise (None: its adjoint sweep does not run)
             ctx.set_materialize_grads(False)
+        if graph.geometry:
             ctx.mark_non_differentiable(outs[1], *outs[-2:])      # + depth_level_values, front_person: no adjoint
         else:
             ctx.mark_non_differentiable(outs[1])      # normal_values: no loss term reads it (loss.py:108-177)
@@ -1553,11 +1703,13 @@ class _TrainFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_rgb, d_nrm, d_acc, d_accp, d_gth, *rest):
         graph = ctx.graph
-        d_geo = None
+        d_geo = d_pen = None
         if graph.geometry:
             rest, d_geo = rest[:-len(GEOMETRY_KEYS)], rest[-len(GEOMETRY_KEYS):-2]
+        if graph.pen_on:
+            rest, d_pen = rest[:-1], rest[-1]
         d_ssl, d_zpl = rest if rest else (None, None)
-        g = graph.backward(d_rgb, d_acc, d_accp, d_gth, d_ssl, d_zpl, d_geo)
+        g = graph.backward(d_rgb, d_acc, d_accp, d_gth, d_ssl, d_zpl, d_geo, d_pen)
         body = [None, None, None]
         if graph.pose_grad:
             sl = ((4, 76), (1, 4), (76, 86))
@@ -1584,6 +1736,9 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
     epoch = int(input["current_epoch"])
     if shard is not None and model.training and getattr(model, "train_geometry", False):
         raise NotImplementedError("train_geometry is not built for person-sharded training (shard=)")
+    if shard is not None and model.training and getattr(model, "train_interpenetration", False):
+        raise NotImplementedError("train_interpenetration is not built for person-sharded training (shard=): a rank holds only its own "
+                                  "persons' fields")
     if (model.smpl_surface_weight > 0 or model.zero_pose_weight > 0) and shard is not None:
         raise NotImplementedError("the smpl_surface / zero_pose regularisers (multiply.py:336-394) are not built for person-sharded training")
     if model.zero_pose_weight > 0 and not (isinstance(id, int) and id == -1):
@@ -1611,6 +1766,9 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
         geometry = ()
         if graph.geometry:
             outs, geometry = outs[:-len(GEOMETRY_KEYS)], outs[-len(GEOMETRY_KEYS):]
+        interpenetration_loss = None
+        if graph.pen_on:
+            outs, interpenetration_loss = outs[:-1], outs[-1]
         smpl_surface_loss, zero_pose_loss = (outs[5], outs[6]) if len(outs) == 7 else (None, None)
         temporal_loss = torch.zeros(1, device=dev)
         if epoch > 250:                                                             # multiply.py:242-243
@@ -1644,7 +1802,8 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
         "points": points, "rgb_values": rgb_values, "normal_values": normal_values,
         "index_outside": input.get("index_outside"), "index_off_surface": index_off_surface,
         "index_in_surface": index_in_surface,
-        "acc_map": acc_map, "grad_theta": grad_theta, "interpenetration_loss": zeros1(), "temporal_loss": temporal_loss,
+        "acc_map": acc_map, "grad_theta": grad_theta,
+        "interpenetration_loss": interpenetration_loss if interpenetration_loss is not None else zeros1(), "temporal_loss": temporal_loss,
         "acc_person_list": acc_person, "smpl_surface_loss": smpl_surface_loss if smpl_surface_loss is not None else zeros1(),
         "epoch": input["current_epoch"],
     }
