@@ -580,6 +580,33 @@ int mp_mesh_index_build(const float* face_verts, int n_faces, const long long* o
 int mp_mesh_index_signed_distance(const float* pts, int n, const void* index, int n_faces, float* sdist, int* visits,
                                   void* stream);
 
+/* ---- closest face of a triangle mesh and the metrics between two meshes (csrc/mesh_closest.hip, csrc/mesh_index.hip;
+ * multiply_amd/metrics.py).  The reference has no such code: its evaluation protocol is restated, see DESIGN 6g.  Per point:
+ * d2 [n] = the smallest squared distance to a face, face [n] (optional) = the face attaining it, q [n][3] (optional) = the
+ * closest point on that face.  Selection: the lexicographic minimum of (d2, face id); a face of zero area ((b-a) x (c-a) == 0)
+ * gives NaN and is never selected.  A point with a non-finite coordinate, or a mesh without a face of non-zero area, gives
+ * face -1, d2 +inf, q NaN.  Both forms evaluate a face with the same contraction-free arithmetic and return the same bits.
+ * Status -1 without a launch: a NULL required argument, n < 0, n_faces <= 0; 0 without a launch: n == 0.  No atomics:
+ * bit-identical from call to call.
+ *   mp_mesh_closest          : brute force over face_verts [F][3][3]
+ *   mp_mesh_index_closest    : through the index of mp_mesh_index_build (layout unchanged); order [n_faces] = the permutation
+ *                              given to that build (sorted slot s is face order[s]; the tie rule is on these ids), NULL = the
+ *                              sorted slots are reported; visits (optional) as in mp_mesh_index_signed_distance
+ *   mp_mesh_index_point_keys : keys [n] = the Hilbert-curve key of each point in the box of the index (points outside fall
+ *                              into the border cells): queries sorted by it keep the lanes of a wave on neighbouring walks
+ *   mp_mesh_metric_reduce    : d2 [n], face [n] of such a query, normals [n][3] = the samples' own unit normals, face_normals
+ *                              [n_faces][3] of the queried mesh (mp_fit_area_cdf), thresholds [n_thresholds <= 8] -> out
+ *                              [7 + n_thresholds] DOUBLES: mean sqrt(d2), mean d2, max sqrt(d2), mean n.n', mean |n.n'|, the
+ *                              number of samples counted, the number left out (face outside 0 .. n_faces - 1), then per
+ *                              threshold the count of sqrt(d2) < threshold.  An empty set's means and max are 0; n == 0
+ *                              launches and writes that.  One workgroup, sums in double in a fixed order. */
+int mp_mesh_closest(const float* pts, int n, const float* face_verts, int n_faces, float* d2, int* face, float* q, void* stream);
+int mp_mesh_index_closest(const float* pts, int n, const void* index, int n_faces, const long long* order, float* d2, int* face,
+                          float* q, int* visits, void* stream);
+int mp_mesh_index_point_keys(const float* pts, int n, const void* index, int* keys, void* stream);
+int mp_mesh_metric_reduce(const float* d2, const int* face, const float* normals, const float* face_normals, int n, int n_faces,
+                          const float* thresholds, int n_thresholds, double* out, void* stream);
+
 /* ---- general deformer queries (deformer.py:19-50, 72-88) for K <= 8 nearest vertices; the render / training path uses
  * the fused K = 1 kernels above.  weights [n][24] = sum_k conf_k skin_w[idx_k], conf = exp(-min(d^2,4)) normalised;
  * outlier (optional) = sqrt(min(d_0^2, 4)) > 0.1.  mp_skinning: x' = (sum_j w_j tfs_j) x, or its inverse. */

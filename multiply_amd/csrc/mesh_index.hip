@@ -2,6 +2,8 @@
 // mp_mesh_signed_distance (mesh.hip) returns, without visiting the faces that cannot matter.  Both kernels evaluate a face with
 // the same tri_dist2 / ray_x_crosses (mesh_prims.hpp); the minimum over faces and the parity of the crossings do not depend on the
 // order of the faces, so the result is equal as long as no skipped face could have lowered the minimum or crossed the ray.
+// The same index answers the closest-face query (mp_mesh_index_closest = the bits of mp_mesh_closest, mesh_closest.hip) with a
+// kernel and a primitive of its own, k_index_closest and tri_closest; the signed path does not share arithmetic with it.
 //
 // The index is an implicit complete binary tree of axis-aligned boxes over the faces in Hilbert-curve order of their centroids:
 //   leaf l  = faces 8 l .. 8 l + 7 of the sorted list (the last leaf may be partial), NL = ceil(F / 8) leaves;
@@ -70,16 +72,13 @@ __device__ __forceinline__ unsigned spread10(unsigned v) {   // 10 bits -> every
 // jumps, and a leaf across a jump gets a box that every point enters: on a 20 480-face sphere a point near the surface evaluated
 // 330 faces in Morton order and 150 in this one.  An axis of zero extent (a planar mesh) gets cell 0: the scale is set to 0 there
 // instead of dividing by the extent.
-__global__ void k_index_keys(const float* __restrict__ fv, int F, const float* __restrict__ hdr, int* __restrict__ keys) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    unsigned X[3];
-    for (int a = 0; a < 3; ++a) {
-        const float lo = hdr[a], ext = hdr[4 + a] - lo;
-        const float scale = ext > 0.f ? 1024.f / ext : 0.f;
-        const float c = (fv[9 * (size_t)f + a] + fv[9 * (size_t)f + 3 + a] + fv[9 * (size_t)f + 6 + a]) * (1.f / 3.f);
-        X[a] = (unsigned)(int)fminf(fmaxf((c - lo) * scale, 0.f), 1023.f);      // (NaN -> 0 by fmaxf)
-    }
+__device__ __forceinline__ unsigned curve_cell(float c, float lo, float hi) {
+    const float ext = hi - lo;
+    const float scale = ext > 0.f ? 1024.f / ext : 0.f;
+    return (unsigned)(int)fminf(fmaxf((c - lo) * scale, 0.f), 1023.f);          // (NaN -> 0 by fmaxf)
+}
+
+__device__ __forceinline__ int hilbert_key(unsigned X[3]) {
     for (unsigned Q = 512; Q > 1; Q >>= 1) {
         const unsigned P = Q - 1;
         for (int a = 0; a < 3; ++a) {
@@ -92,7 +91,28 @@ __global__ void k_index_keys(const float* __restrict__ fv, int F, const float* _
     unsigned t = 0;
     for (unsigned Q = 512; Q > 1; Q >>= 1)
         if (X[2] & Q) t ^= Q - 1;
-    keys[f] = (int)((spread10(X[0] ^ t) << 2) | (spread10(X[1] ^ t) << 1) | spread10(X[2] ^ t));
+    return (int)((spread10(X[0] ^ t) << 2) | (spread10(X[1] ^ t) << 1) | spread10(X[2] ^ t));
+}
+
+__global__ void k_index_keys(const float* __restrict__ fv, int F, const float* __restrict__ hdr, int* __restrict__ keys) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    unsigned X[3];
+    for (int a = 0; a < 3; ++a) {
+        const float c = (fv[9 * (size_t)f + a] + fv[9 * (size_t)f + 3 + a] + fv[9 * (size_t)f + 6 + a]) * (1.f / 3.f);
+        X[a] = curve_cell(c, hdr[a], hdr[4 + a]);
+    }
+    keys[f] = hilbert_key(X);
+}
+
+// the same key for query points (mp_mesh_index_point_keys): points in key order walk the tree alike, so the lanes of a wave
+// finish together.  Points outside the mesh's box fall into its border cells.
+__global__ void k_index_point_keys(const float* __restrict__ pts, int n, const float* __restrict__ hdr, int* __restrict__ keys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    unsigned X[3];
+    for (int a = 0; a < 3; ++a) X[a] = curve_cell(pts[3 * (size_t)i + a], hdr[a], hdr[4 + a]);
+    keys[i] = hilbert_key(X);
 }
 
 // faces into sorted order and the leaf boxes: one thread per leaf (empty leaves included)
@@ -239,6 +259,73 @@ __global__ __launch_bounds__(QB) void k_index_sdist(const float* __restrict__ pt
     if (visits) { visits[2 * (size_t)i] = nodes_tested; visits[2 * (size_t)i + 1] = faces_tested; }
 }
 
+// Closest face: what k_mesh_closest (mesh_closest.hip) returns -- the lexicographic minimum of (d2, original face id) over the
+// faces, d2 and q from tri_closest -- through the walk of k_index_sdist without its crossing column: a node is skipped when
+// box_dist2 > bound and for no other reason.
+// Slack.  tri_closest forms q = a + v ab + w ac and p - q with every product and sum rounded on its own (no fma): at most five
+// roundings per component of q and one of p - q, each at most u M (u = 2^-24, M = the largest |coordinate| involved), so the
+// value falls short of the true squared distance by what < 6 sqrt(3) u M < 11 u M in norm makes; barycentrics that rounding
+// pushes out of [0, 1] move q along the face's plane by the same order.  That is the estimate of k_index_sdist's comment with
+// two more roundings where tri_dist2 may have fused, and delta = 32 u M covers it three times over, so `bound` is formed as
+// there: a face in a box with lb > bound returns d2 > best STRICTLY.  It can neither win nor tie, so the minimum of
+// (d2, id) over the faces that are visited is the minimum over all faces, whatever the visiting order, and the answer has the
+// bits of brute force.  A box at lb == bound is entered.  NaN (a zero-area face) and +inf fail both comparisons below.
+// order: sorted slot -> original face id (the permutation given to mp_mesh_index_build), NULL = report sorted slots.
+__global__ __launch_bounds__(QB) void k_index_closest(const float* __restrict__ pts, int n, const float* __restrict__ index, int F,
+                                                      const long long* __restrict__ order, float* __restrict__ d2_out,
+                                                      int* __restrict__ face_out, float* __restrict__ q_out,
+                                                      int* __restrict__ visits) {
+    const int i = blockIdx.x * QB + threadIdx.x;
+    if (i >= n) return;
+    const int NLp = n_leaves_pow2(F);
+    const float4* nodes = reinterpret_cast<const float4*>(index + HDR_FLOATS);
+    const float* faces = index + HDR_FLOATS + 16 * (size_t)NLp;
+    const float p[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    float best = INFINITY, bq[3] = {NAN, NAN, NAN};
+    int bid = -1, nodes_tested = 0, faces_tested = 0;
+    // a non-finite point has no closest face (fmaxf in box_dist2 would count a NaN axis as distance 0): no walk
+    if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
+        const float4 rlo = nodes[2], rhi = nodes[3];
+        float M = fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]));
+        M = fmaxf(M, fmaxf(fmaxf(fmaxf(fabsf(rlo.x), fabsf(rhi.x)), fmaxf(fabsf(rlo.y), fabsf(rhi.y))), fmaxf(fabsf(rlo.z), fabsf(rhi.z))));
+        const float delta = 16.f * FLT_EPSILON * M;
+        int seed = 1;
+        while (seed < NLp) {
+            const float dl = box_dist2(p, nodes[4 * seed], nodes[4 * seed + 1]), dr = box_dist2(p, nodes[4 * seed + 2], nodes[4 * seed + 3]);
+            seed = dr < dl ? 2 * seed + 1 : 2 * seed;
+            nodes_tested += 2;
+        }
+        float bound = INFINITY;            // nothing is far before the first face; stays +inf while best is (sqrtf(inf) = inf)
+        bool seeding = true;
+        int node = seed;
+        for (int it = 0; it <= 2 * NLp; ++it) {
+            ++nodes_tested;
+            if (!(box_dist2(p, nodes[2 * node], nodes[2 * node + 1]) > bound)) {
+                if (node < NLp) { node = 2 * node; continue; }
+                const int l = node - NLp;
+                for (int k = LEAF * l; k < min(LEAF * (l + 1), F); ++k) {
+                    float a[9], q[3];
+                    for (int e = 0; e < 9; ++e) a[e] = faces[9 * (size_t)k + e];
+                    const float d2 = tri_closest(p, a, a + 3, a + 6, q);
+                    const int id = order ? (int)order[k] : k;
+                    if (d2 < best || (d2 == best && id < bid)) { best = d2; bid = id; bq[0] = q[0]; bq[1] = q[1]; bq[2] = q[2]; }
+                    ++faces_tested;
+                }
+                const float r = sqrtf(best) + delta;
+                bound = r * r * (1.f + 16.f * FLT_EPSILON);
+            }
+            if (seeding) { seeding = false; node = 1; continue; }
+            node += 1;
+            node >>= __ffs(node) - 1;
+            if (node == 1) break;
+        }
+    }
+    d2_out[i] = best;
+    if (face_out) face_out[i] = bid;
+    if (q_out) { q_out[3 * (size_t)i] = bq[0]; q_out[3 * (size_t)i + 1] = bq[1]; q_out[3 * (size_t)i + 2] = bq[2]; }
+    if (visits) { visits[2 * (size_t)i] = nodes_tested; visits[2 * (size_t)i + 1] = faces_tested; }
+}
+
 }  // namespace
 
 extern "C" int mp_mesh_index_bytes(int n_faces) {
@@ -274,5 +361,22 @@ extern "C" int mp_mesh_index_signed_distance(const float* pts, int n, const void
     if (n_faces <= 0) return -1;
     hipLaunchKernelGGL(k_index_sdist, dim3((n + QB - 1) / QB), dim3(QB), 0, (hipStream_t)stream, pts, n, (const float*)index,
                        n_faces, sdist, visits);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_mesh_index_point_keys(const float* pts, int n, const void* index, int* keys, void* stream) {
+    if (n < 0 || !index || (n > 0 && (!pts || !keys))) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_index_point_keys, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pts, n, (const float*)index,
+                       keys);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_mesh_index_closest(const float* pts, int n, const void* index, int n_faces, const long long* order, float* d2,
+                                     int* face, float* q, int* visits, void* stream) {
+    if (n < 0 || n_faces <= 0 || !index || (n > 0 && (!pts || !d2))) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_index_closest, dim3((n + QB - 1) / QB), dim3(QB), 0, (hipStream_t)stream, pts, n, (const float*)index,
+                       n_faces, order, d2, face, q, visits);
     return (int)hipGetLastError();
 }

@@ -54,6 +54,64 @@ __device__ __forceinline__ float tri_dist2(const float* p, const float* a, const
     return dx * dx + dy * dy + dz * dz;
 }
 
+// Closest point q of triangle (a, b, c) to p and the squared distance |p - q|^2: the region classification of tri_dist2 (Ericson,
+// Real-Time Collision Detection 5.1.5), shared by the brute-force and the indexed closest-face kernels (mesh_closest.hip,
+// mesh_index.hip), which must agree bit for bit.  Unlike tri_dist2 the value does not depend on where the function is inlined:
+// contraction is off in every statement (each product and sum is rounded on its own, no fma is formed from them), the divides
+// are correctly rounded, and nothing here is reassociated -- d2 and q are a function of (p, a, b, c) alone.  That is why the
+// dot products are spelled out below instead of calling dot3, whose operations carry the file's default contraction.
+// A face of zero area -- (b - a) x (c - a) == 0 exactly, e.g. a repeated vertex -- has no closest point: q = NaN, d2 = NaN,
+// which no selection takes.  (tri_dist2 answers such a face with NaN or with the distance to a vertex, whichever region p hits.)
+__device__ __forceinline__ float tri_closest(const float* p, const float* a, const float* b, const float* c, float* q) {
+#pragma clang fp contract(off)
+    float ab[3], ac[3], ap[3];
+    for (int i = 0; i < 3; ++i) { ab[i] = b[i] - a[i]; ac[i] = c[i] - a[i]; ap[i] = p[i] - a[i]; }
+    const float nx = ab[1] * ac[2] - ab[2] * ac[1], ny = ab[2] * ac[0] - ab[0] * ac[2], nz = ab[0] * ac[1] - ab[1] * ac[0];
+    if (nx == 0.f && ny == 0.f && nz == 0.f) {
+        q[0] = q[1] = q[2] = __builtin_nanf("");
+        return __builtin_nanf("");
+    }
+    const float d1 = (ab[0] * ap[0] + ab[1] * ap[1]) + ab[2] * ap[2], d2 = (ac[0] * ap[0] + ac[1] * ap[1]) + ac[2] * ap[2];
+    if (d1 <= 0.f && d2 <= 0.f) { for (int i = 0; i < 3; ++i) q[i] = a[i]; }
+    else {
+        float bp[3];
+        for (int i = 0; i < 3; ++i) bp[i] = p[i] - b[i];
+        const float d3 = (ab[0] * bp[0] + ab[1] * bp[1]) + ab[2] * bp[2], d4 = (ac[0] * bp[0] + ac[1] * bp[1]) + ac[2] * bp[2];
+        if (d3 >= 0.f && d4 <= d3) { for (int i = 0; i < 3; ++i) q[i] = b[i]; }
+        else {
+            const float vc = d1 * d4 - d3 * d2;
+            if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
+                const float v = d1 / (d1 - d3);
+                for (int i = 0; i < 3; ++i) q[i] = a[i] + v * ab[i];
+            } else {
+                float cp[3];
+                for (int i = 0; i < 3; ++i) cp[i] = p[i] - c[i];
+                const float d5 = (ab[0] * cp[0] + ab[1] * cp[1]) + ab[2] * cp[2], d6 = (ac[0] * cp[0] + ac[1] * cp[1]) + ac[2] * cp[2];
+                if (d6 >= 0.f && d5 <= d6) { for (int i = 0; i < 3; ++i) q[i] = c[i]; }
+                else {
+                    const float vb = d5 * d2 - d1 * d6;
+                    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
+                        const float w = d2 / (d2 - d6);
+                        for (int i = 0; i < 3; ++i) q[i] = a[i] + w * ac[i];
+                    } else {
+                        const float va = d3 * d6 - d5 * d4;
+                        if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
+                            const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+                            for (int i = 0; i < 3; ++i) q[i] = b[i] + w * (c[i] - b[i]);
+                        } else {
+                            const float den = 1.0f / ((va + vb) + vc);
+                            const float v = vb * den, w = vc * den;
+                            for (int i = 0; i < 3; ++i) q[i] = (a[i] + ab[i] * v) + ac[i] * w;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
 // does the ray p + t (1,0,0), t > 0 cross the triangle?  (y,z) projection, half-open edges: an edge (u,v) counts when
 // exactly one endpoint has y > p.y; the crossing is inside when the edge functions agree in sign.
 __device__ __forceinline__ bool ray_x_crosses(const float* p, const float* a, const float* b, const float* c) {

@@ -849,8 +849,8 @@ class MeshIndex:
         self.buf = torch.empty(int(L.mp_mesh_index_bytes(self.n_faces)), dtype=torch.uint8, device=dev)
         keys = torch.empty(self.n_faces, dtype=torch.int32, device=dev)
         L.mp_mesh_index_keys(fv, self.n_faces, self.buf, keys, stream())
-        order = torch.sort(keys, stable=True).indices
-        L.mp_mesh_index_build(fv, self.n_faces, order, self.buf, stream())
+        self.order = torch.sort(keys, stable=True).indices       # sorted slot -> face: closest() reports faces by it
+        L.mp_mesh_index_build(fv, self.n_faces, self.order, self.buf, stream())
 
     def signed_distance(self, pts, out=None, visits=None):
         """signed distance (n,) of pts (n,3), equal to mesh_signed_distance's; visits: optional (n,2) int32 = boxes tested, faces
@@ -859,6 +859,33 @@ class MeshIndex:
         sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
         lib().mp_mesh_index_signed_distance(pts, n, self.buf, self.n_faces, sd, visits, stream())
         return sd
+
+    def closest(self, pts, want_face=True, want_point=True, visits=None, sort_points=None):
+        """(d2 (n,), face (n,) int32 or None, q (n,3) or None) of pts (n,3): squared distance to the closest face, its id in the
+        mesh the index was built from, and the closest point on it (mp_mesh_index_closest) -- the bits of mesh_closest without an
+        index.  Ties go to the lower face id; a non-finite point gets (+inf, -1, NaN).  visits: optional (n,2) int32 = boxes
+        tested, faces evaluated per point.  sort_points (None = MESH_CLOSEST_SORT_POINTS): query the points in Hilbert-curve order
+        of the mesh's box and put the answers back (two torch sorts' worth of plumbing; the answers do not depend on it)."""
+        L, n, dev = lib(), pts.shape[0], pts.device
+        pts = pts.detach().float().contiguous()
+        sort_points = MESH_CLOSEST_SORT_POINTS if sort_points is None else sort_points
+        perm = None
+        if sort_points and n > 1:
+            keys = torch.empty(n, dtype=torch.int32, device=dev)
+            L.mp_mesh_index_point_keys(pts, n, self.buf, keys, stream())
+            perm = torch.sort(keys).indices
+            pts = pts[perm].contiguous()
+        d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev) if want_face else None
+        q = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_point else None
+        vis = visits if perm is None or visits is None else torch.empty_like(visits)
+        L.mp_mesh_index_closest(pts, n, self.buf, self.n_faces, self.order, d2, face, q, vis, stream())
+        if perm is not None:
+            back = lambda t: None if t is None else torch.empty_like(t).index_copy_(0, perm, t)
+            d2, face, q = back(d2), back(face), back(q)
+            if visits is not None:
+                visits.index_copy_(0, perm, vis)
+        return d2, face, q
 
 
 class MeshIndexCache:
@@ -893,3 +920,40 @@ def mesh_signed_distance(pts, face_verts, out=None, index=None):
     sd = torch.empty(n, dtype=torch.float32, device=pts.device) if out is None else out
     lib().mp_mesh_signed_distance(pts, n, face_verts, face_verts.shape[0], sd, stream())
     return sd
+
+
+# ------------------------------------------------------------------------------------------------ closest face, mesh metrics
+# Query points in Hilbert-curve order by default?  No: measured (profiles/mesh_closest.txt, tools/mesh_index_bench.py --closest)
+# at 100 000 points the ordering cuts the faces a wave evaluates to a third but not the time (2 897 against 2 934 us against 24 660
+# faces, inside the spread; 11 144 against 8 969 us against 394 184): the launch is one round of waves and ends with its slowest one.  DESIGN 6g.
+MESH_CLOSEST_SORT_POINTS = False
+
+
+def mesh_closest(pts, face_verts, index=None, want_face=True, want_point=True):
+    """(d2 (n,), face (n,) int32, q (n,3)) of pts (n,3) against the mesh face_verts (F,3,3), closed or not: squared distance to
+    the closest face, that face (ties: the lower id; -1 for a non-finite point or a mesh of zero-area faces only) and the closest
+    point on it.  mp_mesh_closest, or through a MeshIndex of the same faces (same bits)."""
+    fv = face_verts.detach().reshape(-1, 9).float().contiguous()
+    if index is not None:
+        assert index.n_faces == fv.shape[0], "the index was built from another mesh"
+        return index.closest(pts, want_face, want_point)
+    pts = pts.detach().float().contiguous()
+    n, dev = pts.shape[0], pts.device
+    d2 = torch.empty(n, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev) if want_face else None
+    q = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_point else None
+    lib().mp_mesh_closest(pts, n, fv, fv.shape[0], d2, face, q, stream())
+    return d2, face, q
+
+
+def mesh_metric_reduce(d2, face, normals, face_normals, thresholds=()):
+    """One directed set of metrics (mp_mesh_metric_reduce) from a closest-face query: (7 + T,) float64 on the device = mean
+    distance, mean squared distance, max distance, mean n.n', mean |n.n'|, samples counted, samples left out (face < 0), then
+    per threshold the number of samples nearer than it."""
+    n, dev = d2.shape[0], face_normals.device
+    T = len(thresholds)
+    tau = torch.tensor([float(t) for t in thresholds], dtype=torch.float32, device=dev) if T else None
+    out = torch.empty(7 + T, dtype=torch.float64, device=dev)
+    lib().mp_mesh_metric_reduce(d2 if n else None, face if n else None, normals if n else None, face_normals, n,
+                                face_normals.shape[0], tau, T, out, stream())
+    return out

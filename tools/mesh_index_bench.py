@@ -9,7 +9,11 @@ build is timed as a whole (keys, torch.sort, gather, boxes).  Shapes:
   (c) squashed spheres of 8 * 4^k and 20 * 4^k faces, 8 192 points in their box: where the index starts to win;
   (d) a single query of 5 120 points with the index built for it (interpenetration_loss).
 The last column says what 'auto' picks for the mesh (hip.mesh_index_wanted: closed surface, hip.MESH_INDEX_MIN_FACES faces).
-Also: boxes tested / faces evaluated per point (the kernel's optional counters), and bit-equality of the two results."""
+Also: boxes tested / faces evaluated per point (the kernel's optional counters), and bit-equality of the two results.
+    python tools/mesh_index_bench.py --closest [--big] [--out profiles/mesh_closest.txt]
+measures the closest-face query instead (mp_mesh_closest against mp_mesh_index_closest): 100 000 surface samples of a shifted
+copy of closed_body_mesh against that mesh (--big: also against its res_up=4 extraction), with and without the Hilbert ordering
+of the query points (its two sorts included), and the signed query of the same index on the same points for comparison."""
 import argparse
 import os
 import statistics
@@ -22,6 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("--closest", action="store_true")
+ap.add_argument("--big", action="store_true")
 args = ap.parse_args()
 sys.argv = sys.argv[:1]
 import bench  # noqa: E402
@@ -95,6 +101,87 @@ def compare(tag, pts, fv, faces=True):
     return tb[0], tq[0], tbuild[0]
 
 
+def wave_max(visits, n):
+    pad = (-n) % 64
+    return torch.cat([visits[:, 1].float(), torch.zeros(pad, device="cuda")]).reshape(-1, 64).max(1).values.mean().item()
+
+
+def closest_rows(tag, pts, fv, brute_reps):
+    """brute force / index with and without sorted points / the signed query, for one mesh; median (min .. max) of the launches"""
+    pts, fv = pts.detach().float().contiguous(), fv.detach().reshape(-1, 9).float().contiguous()
+    n, F = pts.shape[0], fv.shape[0]
+
+    def spread(fn, reps):
+        for _ in range(min(5, reps)):
+            fn()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(1e3 * e0.elapsed_time(e1))
+        return statistics.median(ts), min(ts), max(ts)
+    fmt = lambda t: f"{t[0]:10.1f} ({t[1]:10.1f} .. {t[2]:10.1f})"
+    say(f"  {tag}: {n} points x {F} faces")
+    index = hip.MeshIndex(fv)
+    tbuild = spread(lambda: hip.MeshIndex(fv), max(5, args.reps // 3))
+    say(f"    index build                          {fmt(tbuild)}")
+    want = None
+    if brute_reps:
+        tb = spread(lambda: hip.mesh_closest(pts, fv), brute_reps)
+        want = hip.mesh_closest(pts, fv)
+        say(f"    brute force (d2, face, q)            {fmt(tb)}   [{brute_reps} launches]")
+    rows = {}
+    for sort_points in (False, True):
+        t = spread(lambda: index.closest(pts, sort_points=sort_points), args.reps)
+        visits = torch.zeros(n, 2, dtype=torch.int32, device="cuda")
+        got = index.closest(pts, visits=visits, sort_points=sort_points)
+        torch.cuda.synchronize()
+        vm = visits.float().mean(0).tolist()
+        # the per-wave maximum is over the lanes as LAUNCHED: in the sorted order when the points are sorted
+        lanes = visits
+        if sort_points:
+            keys = torch.empty(n, dtype=torch.int32, device="cuda")
+            hip.lib().mp_mesh_index_point_keys(pts, n, index.buf, keys, hip.stream())
+            lanes = visits[torch.sort(keys).indices]
+        eq = "n/a" if want is None else all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(want, got))
+        rows[sort_points] = t[0]
+        say(f"    index, points {'in Hilbert order' if sort_points else 'as given        '}      {fmt(t)}   boxes/pt {vm[0]:6.1f} faces/pt {vm[1]:6.1f} "
+            f"(per wave max {wave_max(lanes, n):6.1f})  bit-equal to brute {eq}" + (f"  x{tb[0] / t[0]:7.1f}" if brute_reps else ""))
+    if brute_reps == 0:                                           # equality on a subset brute force can afford
+        sub = pts[:2048].contiguous()
+        eq = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(hip.mesh_closest(sub, fv), index.closest(sub)))
+        say(f"    (brute force not timed at this size; bit-equal on the first 2 048 points: {eq})")
+    sd = torch.empty(n, device="cuda")
+    ts = spread(lambda: index.signed_distance(pts, out=sd), args.reps)
+    visits = torch.zeros(n, 2, dtype=torch.int32, device="cuda")
+    index.signed_distance(pts, out=sd, visits=visits)
+    torch.cuda.synchronize()
+    vm = visits.float().mean(0).tolist()
+    say(f"    signed query (same index, as given)  {fmt(ts)}   boxes/pt {vm[0]:6.1f} faces/pt {vm[1]:6.1f} (per wave max {wave_max(visits, n):6.1f})")
+    return rows
+
+
+def closest_section(bv, bf, server):
+    from multiply_amd import metrics
+    say(f"Closest face, brute force vs face index.  {torch.cuda.get_device_name(0)}, one device, one session; library {hip.lib_source_sha16()}")
+    say(f"HIP events around single calls, median (min .. max) of {args.reps} after 5 warm-up calls, microseconds.  'Hilbert order' "
+        f"includes the key kernel, torch's sort and the un-permutation.  hip.MESH_CLOSEST_SORT_POINTS = {hip.MESH_CLOSEST_SORT_POINTS}")
+    say()
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    shifted = (bv + torch.tensor([0.01, -0.008, 0.006], device=bv.device), bf)
+    pts = metrics.surface_samples(shifted, 100_000, gen)[0]
+    res = {"body": closest_rows("samples of a shifted copy / closed_body_mesh", pts, bv[bf], brute_reps=max(3, args.reps // 5))}
+    if args.big:
+        say()
+        v4, f4 = closed_body_mesh(server, res_up=4)
+        res["big"] = closest_rows("the same samples / closed_body_mesh at res_up=4", pts, v4[f4], brute_reps=0)
+    say()
+    for k, r in res.items():
+        say(f"{k}: Hilbert-ordered points {'faster' if r[True] < r[False] else 'slower'} than as given: {r[True]:.1f} vs {r[False]:.1f} us")
+
+
 torch.cuda.set_device(0)
 hip.require_device()
 try:
@@ -112,6 +199,13 @@ gin = bench.to_dev(inp)
 server = model.smpl_server_list[0]
 bv, bf = closed_body_mesh(server)
 body = bv[bf].contiguous()
+if args.closest:
+    lines.clear()
+    closest_section(bv, bf, server)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 say("(a) the fit's step (smpl_init default: 8 192 volume points) against closed_body_mesh; recorded before: 12 994 us")
 cfg = smpl_init.FitConfig()
 target = smpl_init.MeshTarget(bv, bf, "cuda", mesh_index_mode="brute")
