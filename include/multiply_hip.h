@@ -733,6 +733,32 @@ int mp_pen_scatter_bwd(const int* const* pen_idx, const int* list, const int* co
                        const float* const* blend_table, const float* const* dxc, int n_person, int n, int n_verts,
                        float* const* dverts, void* stream);
 
+/* ---- image-space metrics (csrc/image_metrics.hip; multiply_amd/image_metrics.py, whose docstring holds the definitions; the
+ * reference has get_psnr, code/lib/utils/rend_util.py:10-18, and otherwise writes PNGs for an outside script to score).
+ * Images a, b [N][H][W][C] fp32, C = 1 or 3, values in [0, data_range]; mask [N][H][W] bytes (non-zero = inside) or NULL = every
+ * pixel.  A VALUE is one channel of one pixel.  Both calls write out [N][5] doubles per frame:
+ *   out[n] = { sum, number counted, sum over the mask, number counted in the mask, number left out }
+ * through per-workgroup partials in `work` (mp_image_work_bytes(N, H, W, C) bytes, 8-byte aligned; -1 for a shape neither call
+ * takes) that a finishing pass adds in a fixed order: no atomics, bit-identical from call to call.
+ *   mp_image_sqerr : sum of (a - b)^2 in double over the values where a and b are both finite; the others are left out.
+ *                    H * W * C < 2^31.
+ *   mp_image_ssim  : SSIM (Wang et al. 2004): 11 x 11 Gaussian window, sigma 1.5 (taps formed in double, normalised to sum 1),
+ *                    K1 = 0.01, K2 = 0.03, population moments, per channel, only where the whole window lies inside the image:
+ *                    the map is [N][H-10][W-10][C].  sum = the sum of the map; a window that holds a non-finite value of a or b
+ *                    is left out (map value NaN); a window belongs to the mask when its CENTRE pixel does.  map: the map itself,
+ *                    rounded once to fp32, or NULL.  Window sums, moments and the SSIM expression are in double, taken about a
+ *                    per-tile pivot so that flat images lose nothing to cancellation; the expression is symmetric in a and b
+ *                    (swapping them returns the same bits).  One workgroup per MP_SSIM_TILE x MP_SSIM_TILE tile of the map.
+ * Status -1 without a launch: N < 0, C not 1 or 3, a NULL a / b / work / out with N > 0, a grid beyond 2^31 - 1 workgroups;
+ * mp_image_ssim also H < 11, W < 11, data_range not a positive finite number; mp_image_sqerr H < 1 or W < 1.  N == 0: returns 0,
+ * nothing is read or written. */
+#define MP_SSIM_TILE 32
+int mp_image_work_bytes(int N, int H, int W, int C);
+int mp_image_ssim(const float* a, const float* b, const unsigned char* mask, int N, int H, int W, int C, float data_range,
+                  void* work, double* out, float* map, void* stream);
+int mp_image_sqerr(const float* a, const float* b, const unsigned char* mask, int N, int H, int W, int C, void* work,
+                   double* out, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

@@ -121,7 +121,7 @@ def header_prototypes(path=HEADER_PATH):
 # Every entry point returns a status (0, or a hipError_t / negative argument-error code: the header's top comment) except these,
 # which return a value
 VALUE_RETURNING = ("mp_device_ok", "mp_sig_bytes_per_point", "mp_obb_hull_device_work_bytes", "mp_warp_bin_work_bytes",
-                   "mp_debug_hull_abandon", "mp_arch", "mp_mesh_index_bytes")
+                   "mp_debug_hull_abandon", "mp_arch", "mp_mesh_index_bytes", "mp_image_work_bytes")
 _DEBUG_SYNC = bool(int(os.environ.get("MP_DEBUG_SYNC", "0")))
 
 
@@ -956,4 +956,56 @@ def mesh_metric_reduce(d2, face, normals, face_normals, thresholds=()):
     out = torch.empty(7 + T, dtype=torch.float64, device=dev)
     lib().mp_mesh_metric_reduce(d2 if n else None, face if n else None, normals if n else None, face_normals, n,
                                 face_normals.shape[0], tau, T, out, stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ image metrics (csrc/image_metrics.hip)
+SSIM_TILE, SSIM_WINDOW = 32, 11      # = include/multiply_hip.h MP_SSIM_TILE; the 11 x 11 window of mp_image_ssim
+
+
+def _image_args(a, b, mask):
+    """shape / dtype rules of the two image entry points: a, b (N,H,W,C) float32, mask (N,H,W) bool or None"""
+    if a.dim() != 4 or a.shape != b.shape or a.shape[3] not in (1, 3):
+        raise ValueError(f"images must be two (N, H, W, C) tensors of one shape with C = 1 or 3, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise TypeError(f"images must be float32, got {a.dtype} and {b.dtype}")
+    if mask is not None:
+        if mask.dtype != torch.bool:
+            raise TypeError(f"the mask must be bool, got {mask.dtype}")
+        if tuple(mask.shape) != tuple(a.shape[:3]):
+            raise ValueError(f"the mask must be (N, H, W) = {tuple(a.shape[:3])}, got {tuple(mask.shape)}")
+        mask = mask.contiguous().view(torch.uint8)
+    return a.detach().contiguous(), b.detach().contiguous(), mask
+
+
+def _image_work(N, H, W, C, dev):
+    nbytes = int(lib().mp_image_work_bytes(N, H, W, C))
+    if nbytes < 0:
+        raise ValueError(f"images of shape {(N, H, W, C)} are beyond what the image kernels take")
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+
+
+def image_ssim(a, b, mask=None, data_range=1.0, want_map=False):
+    """Per-frame SSIM sums of a, b (N,H,W,C) float32 device tensors (mp_image_ssim; definitions: image_metrics.py): (N,5) float64
+    on the device = sum of the SSIM map, windows counted, the same two over the windows whose centre lies in mask (N,H,W; None =
+    everywhere), windows left out for a non-finite value; and the map (N,H-10,W-10,C) float32 (NaN where left out) or None."""
+    a, b, mask = _image_args(a, b, mask)
+    N, H, W, Cn = a.shape
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f"SSIM needs images of at least {SSIM_WINDOW} x {SSIM_WINDOW} pixels, got {H} x {W}")
+    if not (float(data_range) > 0.0 and math.isfinite(float(data_range))):
+        raise ValueError(f"data_range must be a positive finite number, got {data_range}")
+    out = torch.empty(N, 5, dtype=torch.float64, device=a.device)
+    smap = torch.empty(N, H - 10, W - 10, Cn, dtype=torch.float32, device=a.device) if want_map else None
+    lib().mp_image_ssim(a, b, mask, N, H, W, Cn, float(data_range), _image_work(N, H, W, Cn, a.device), out, smap, stream())
+    return out, smap
+
+
+def image_sqerr(a, b, mask=None):
+    """Per-frame squared-error sums of a, b (N,H,W,C) float32 device tensors (mp_image_sqerr): (N,5) float64 on the device = sum of
+    (a - b)^2 over the finite values, their number, the same two inside mask (N,H,W; None = everywhere), values left out."""
+    a, b, mask = _image_args(a, b, mask)
+    N, H, W, Cn = a.shape
+    out = torch.empty(N, 5, dtype=torch.float64, device=a.device)
+    lib().mp_image_sqerr(a, b, mask, N, H, W, Cn, _image_work(N, H, W, Cn, a.device), out, stream())
     return out
