@@ -74,6 +74,18 @@ typedef struct {
     float bias_scale;
 } MpPackLayer;
 int mp_pack_layers(const MpPackLayer* table, int n_layers, int ks_in, void* stream);
+/* Feature fold.  An SDF network ends in a linear layer W8 [1 + n_feat][in8] (row 0 = sdf, rows 1.. = the feature vector,
+ * networks.py:176-181) whose features only feed the first layer Wc [out_c][in_c] of its rendering network, in columns
+ * [feat_col0, feat_col0 + n_feat) (networks.py:277-281, 305-311).  That layer is linear in them, so
+ *   Wc[:, feat] (W8[1:] h + b8[1:]) = (Wc[:, feat] W8[1:]) h + Wc[:, feat] b8[1:]
+ * and the product depends on parameters only.  This writes, in fp32 and with weight norm resolved on both factors (g NULL: none),
+ *   out_w [out_c][in_c] : Wc_eff, with columns feat_col0 + k (k < in8 <= n_feat) replaced by sum_f Wc_eff[r][feat_col0 + f] *
+ *                         W8_eff[1 + f][k] (zeros for in8 <= k < n_feat): a layer that takes the SDF network's last hidden
+ *                         vector where Wc takes the features;
+ *   out_b [out_c]       : bc + Wc_eff[:, feat] b8[1:]
+ * for mp_pack_layer(s) to pack like any other layer (in scaled units: colscale = 1/K on those columns).  n_feat <= 1024. */
+int mp_fold_features(const float* vc, const float* gc, const float* bc, int out_c, int in_c, int feat_col0, int n_feat,
+                     const float* v8, const float* g8, const float* b8, int in8, float* out_w, float* out_b, void* stream);
 
 /* ---- fused MLP evaluation -------------------------------------------------------------------
  * mp_mlp_sdf: ImplicitNet.forward restricted to the sdf column (networks.py:126-181; caller:
@@ -122,9 +134,19 @@ int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float* bias, con
                      const void* w8_slots, const float* xc, const float* jinv, const int* worklist, const int* count,
                      int max_count, float* sdf_out, float* normal_out, void* feat_frag, void* sig, int seg_points,
                      void* stream);
+/* mp_mlp_shade_rev_fold: mp_mlp_shade_rev without the 256 feature rows of the last layer.  net / wpack / bias: the 'sdf' plan
+ * (the network ends in the one-chunk sdf row, as for mp_mlp_sdf; anything else: -1); h7_frag receives, in feat_frag's layout and
+ * size, the last hidden layer's activations in scaled units (x 100 log2 e) as f16 B-fragments.  mp_mlp_color turns them into the
+ * same colours when its first layer is packed from mp_fold_features' output.  sdf_out and normal_out: the bits of
+ * mp_mlp_shade_rev (the same sdf row, K order and accumulator; the reverse sweep does not read the features). */
+int mp_mlp_shade_rev_fold(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet, const void* gpack,
+                          const void* w8_slots, const float* xc, const float* jinv, const int* worklist, const int* count,
+                          int max_count, float* sdf_out, float* normal_out, void* h7_frag, void* sig, int seg_points,
+                          void* stream);
 
 /* mp_mlp_color: RenderingNet.forward mode 'pose_no_view' (networks.py:277-281, 305-311):
- * sigmoid(MLP([x_c, n, lin_pose(pose) (hoisted), feat])) -> rgb_out[id][3]. */
+ * sigmoid(MLP([x_c, n, lin_pose(pose) (hoisted), feat])) -> rgb_out[id][3].  feat_frag: the features as written by mp_mlp_shade /
+ * mp_mlp_shade_rev -- or mp_mlp_shade_rev_fold's h7_frag together with a pack whose first layer is the folded one. */
 int mp_mlp_color(const MpNet* net, const void* wpack, const float* bias, const float* xc, const float* normal,
                  const void* feat_frag, const int* worklist, const int* count, int max_count, float* rgb_out,
                  void* stream);
@@ -136,6 +158,12 @@ int mp_mlp_color(const MpNet* net, const void* wpack, const float* bias, const f
 int mp_background(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren,
                   const void* wpack_ren, const float* bias_ren, const float* dirs, const float* cam, const float* z_bg,
                   int z_per_ray, int n_rays, float radius, float* bg_rgb, void* stream);
+/* mp_background_fold: the same with the feature fold: net_imp is the 'sdf' plan of the background ImplicitNet (it ends in the
+ * one-chunk density row; anything else: -1) and net_ren's first layer is packed from mp_fold_features' output, so that it takes
+ * the density network's last hidden activations from the registers. */
+int mp_background_fold(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren,
+                       const void* wpack_ren, const float* bias_ren, const float* dirs, const float* cam, const float* z_bg,
+                       int z_per_ray, int n_rays, float radius, float* bg_rgb, void* stream);
 
 /* ---- SMPL ------------------------------------------------------------------------------------
  * SMPLServer.forward (lib/model/smpl.py:50-94) -> lbs (lib/smpl/lbs.py:136-229): posed vertices, bone

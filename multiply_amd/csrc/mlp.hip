@@ -390,7 +390,10 @@ struct GradCapture {
 // ---- sweep 1: work indices [offset, offset + seg) of the worklist.  sig block of (tile t, wave w) of the segment:
 //      sig + ((t * 8 + w) * 8 layers) * SIG_LAYER;  inside: [layer][K step = chunk][lane][16 B] as UNORM8 (both column blocks of
 //      a chunk in one 16-byte vector; half-precision build: [layer][K step][block][lane][16 B])
-template <int NB, int WAVES>
+// FOLD (mp_mlp_shade_rev_fold): the network is the 'sdf' pack -- it ends in the one-chunk sdf layer -- and the fragment stream
+// written to feat_frag is the last hidden layer's activations h7' as they stand in the operand registers: the 256 feature rows of
+// the last layer are folded into the colour network's first layer on the host (hip.py FoldedColor), 8 chunks per tile fewer.
+template <int NB, int WAVES, bool FOLD>
 __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, const char* __restrict__ wpack,
                                                             const float* __restrict__ bias, const float* __restrict__ xc,
                                                             const int* __restrict__ worklist,
@@ -426,10 +429,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_fwdsave(const NetDesc net, c
         stream_prologue_wait(rs);
         MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 2);
         const SigIO sio = {sigbuf + ((size_t)t * WAVES + wave) * (size_t)(8 * SIG_LAYER), SIG_LAYER};
-        run_net<NB, false, KS_IN, HID_SOFTPLUS_SAVE, WAVES>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out, wave, lane,
-                                                            sio, NoCapture(), rs, cm, more ? wpack : nullptr, cm);
+        run_net<NB, false, KS_IN, HID_SOFTPLUS_SAVE, WAVES, NoCapture, FOLD>(net, wpack, bias_lds, smem + L::ring, Bcur, stage, out,
+                                                                             wave, lane, sio, NoCapture(), rs, cm,
+                                                                             more ? wpack : nullptr, cm);
         MP_STAMP_AT(HID_SOFTPLUS_SAVE, 120 + MP_TILE_SLOT(t), 3);
-        // features in the colour kernel's layout: tiles of 64 work items (offset is a multiple of 256), 4 blocks of 16 columns
+        // features (FOLD: h7') in the colour kernel's layout: tiles of 64 work items (offset is a multiple of 256), 4 blocks of 16 columns
         const size_t tile = (size_t)(offset / 64) + (size_t)t * 4 + (wave >> 1);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
@@ -639,7 +643,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_mlp_color(const NetDesc net, con
 
 // ------------------------------------------------------------------------------------------------ background
 // A wave owns 16*NB consecutive samples; with NB = 2 and 32 samples per ray that is exactly one ray.
-template <int NB, int WAVES>
+// FOLD (mp_background_fold): the density network is its 'sdf' pack (it ends in the one-chunk density row) and the colour network's
+// first layer takes the density network's last hidden activations from the registers through the folded pack (hip.py FoldedColor).
+template <int NB, int WAVES, bool FOLD>
 __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp, const char* __restrict__ wp_imp,
                                                            const float* __restrict__ bias_imp, const NetDesc net_ren,
                                                            const char* __restrict__ wp_ren,
@@ -703,8 +709,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
         f32x4 out[NB];
         zero_b<NB>(Bcur);
         stream_prologue_wait(rs);
-        run_net<NB, false, KS_IN, HID_SOFTPLUS, WAVES>(net_imp, wp_imp, bias_lds0, smem + L::ring, Bcur, stage, out, wave,
-                                                       lane, SigIO{nullptr, 0}, NoCapture(), rs, cm_imp, wraps ? wp_ren : nullptr, cm_ren);
+        run_net<NB, false, KS_IN, HID_SOFTPLUS, WAVES, NoCapture, FOLD>(net_imp, wp_imp, bias_lds0, smem + L::ring, Bcur, stage, out,
+                                                                        wave, lane, SigIO{nullptr, 0}, NoCapture(), rs, cm_imp,
+                                                                        wraps ? wp_ren : nullptr, cm_ren);
         // the colour net's first chunks came with the tail of the density net's stream; a pack that cannot wrap: behind the last
         // barrier of the network above the ring is free, their latency runs beside the density / view-direction staging below
         stream_prologue_issue<KS_IN, WAVES>(rs, net_ren, wp_ren, smem + L::ring, wave, lane);
@@ -712,7 +719,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_background(const NetDesc net_imp
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) scr[(nb * 16 + lane) * 4 + 3] = fabsf(out[nb][0]);  // AbsDensity (density.py:32-34)
         }
-        // colour net: [PE_4(view dir) (27), frame code (hoisted), features (registers)]
+        // colour net: [PE_4(view dir) (27), frame code (hoisted), features (registers; FOLD: the density net's h7')]
         if (lane < L::PTS) stage_pe<3, 4, KS_IN>(stage + lane * in_stride(KS_IN), d);
         stream_prologue_wait(rs);
         run_net<NB, false, KS_IN, HID_RELU, WAVES>(net_ren, wp_ren, bias_lds1, smem + L::ring, Bcur, stage, out, wave, lane,
@@ -787,6 +794,14 @@ bool net_ok(const MpNet* net) {
     return chunks == net->total_chunks;
 }
 
+// The folded kernels hand on the INPUT of the network's last layer (run_layer_pp KEEP_B): it must be the only linear layer, one
+// chunk, register-fed, returning its chunk 0 -- the 'sdf' plan of multiply_amd/hip.py.
+bool net_ends_in_sdf_row(const MpNet* net) {
+    if (!net_ok(net) || net->n_layers < 2) return false;
+    const auto& L = net->layer[net->n_layers - 1];
+    return L.act == ACT_NONE && net->layer[net->n_layers - 2].act != ACT_NONE && L.n_chunk == 1 && L.out_chunk == 0 && L.use_reg;
+}
+
 constexpr int PNB = 2, PWAVES = 8;   // plain-mode geometry
 
 }  // namespace
@@ -849,13 +864,15 @@ extern "C" int mp_mlp_full(const MpNet* net, const void* wpack, const float* bia
 
 extern "C" int mp_sig_bytes_per_point(void) { return 8 * KS_REG * SIG_CHUNK_BYTES / 32; }
 
-extern "C" int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet, const void* gpack,
-                                const void* w8_slots, const float* xc, const float* jinv, const int* worklist,
-                                const int* count, int max_count, float* sdf_out, float* normal_out, void* feat_frag,
-                                void* sig, int seg_points, void* stream) {
+namespace {
+template <bool FOLD>
+int shade_rev(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet, const void* gpack,
+              const void* w8_slots, const float* xc, const float* jinv, const int* worklist, const int* count, int max_count,
+              float* sdf_out, float* normal_out, void* feat_frag, void* sig, int seg_points, void* stream) {
     if (max_count <= 0) return 0;
     if (seg_points < 256 || seg_points % 256) return -1;
     if (!net_ok(net) || !net_ok(gnet)) return -1;
+    if (FOLD && !net_ends_in_sdf_row(net)) return -1;
     // the reverse sweep fetches its stored sigmoids one chunk ahead into alternating buffers (mlp_core.hpp run_layer_pp):
     // every sigmoid-multiplied layer must be 8 chunks (256 rows) so that the alternation carries across layers
     for (int l = 0; l < gnet->n_layers; ++l)
@@ -864,19 +881,36 @@ extern "C" int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float
     using L = Lds<2, PNB, PWAVES>;
     constexpr int TILE = 16 * PNB * PWAVES;
     constexpr int LDS_G = RING_SLOTS * chunk_bytes(0) + 512 + PWAVES * 2 * 16 * PNB * 48 * 2;
-    MP_LDS_ATTR((k_mlp_fwdsave<PNB, PWAVES>), L::total);
+    MP_LDS_ATTR((k_mlp_fwdsave<PNB, PWAVES, FOLD>), L::total);
     MP_LDS_ATTR((k_mlp_grad<PNB, PWAVES>), LDS_G);
     const NetDesc d = as_desc(net), gd = as_desc(gnet);
     for (int off = 0; off < max_count; off += seg_points) {   // segments past the device-side count return at once
         const int n = max_count - off < seg_points ? max_count - off : seg_points;
         const int grid = grid_for((n + TILE - 1) / TILE, 1);
-        hipLaunchKernelGGL((k_mlp_fwdsave<PNB, PWAVES>), dim3(grid), dim3(PWAVES * 64), L::total, st, d, (const char*)wpack, bias,
+        hipLaunchKernelGGL((k_mlp_fwdsave<PNB, PWAVES, FOLD>), dim3(grid), dim3(PWAVES * 64), L::total, st, d, (const char*)wpack, bias,
                            xc, worklist, count, max_count, off, seg_points, sdf_out, (char*)feat_frag, (char*)sig);
         hipLaunchKernelGGL((k_mlp_grad<PNB, PWAVES>), dim3(grid), dim3(PWAVES * 64), LDS_G, st, gd, (const char*)gpack,
                            (const op_t*)w8_slots, xc, jinv, worklist, count, max_count, off, seg_points, (const char*)sig,
                            sdf_out, normal_out);
     }
     return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int mp_mlp_shade_rev(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet, const void* gpack,
+                                const void* w8_slots, const float* xc, const float* jinv, const int* worklist,
+                                const int* count, int max_count, float* sdf_out, float* normal_out, void* feat_frag,
+                                void* sig, int seg_points, void* stream) {
+    return shade_rev<false>(net, wpack, bias, gnet, gpack, w8_slots, xc, jinv, worklist, count, max_count, sdf_out, normal_out,
+                            feat_frag, sig, seg_points, stream);
+}
+
+extern "C" int mp_mlp_shade_rev_fold(const MpNet* net, const void* wpack, const float* bias, const MpNet* gnet,
+                                     const void* gpack, const void* w8_slots, const float* xc, const float* jinv,
+                                     const int* worklist, const int* count, int max_count, float* sdf_out,
+                                     float* normal_out, void* h7_frag, void* sig, int seg_points, void* stream) {
+    return shade_rev<true>(net, wpack, bias, gnet, gpack, w8_slots, xc, jinv, worklist, count, max_count, sdf_out, normal_out,
+                           h7_frag, sig, seg_points, stream);
 }
 
 extern "C" int mp_mlp_shade(const MpNet* net, const void* wpack, const float* bias, const float* xc,
@@ -909,17 +943,35 @@ extern "C" int mp_mlp_color(const MpNet* net, const void* wpack, const float* bi
     return (int)hipGetLastError();
 }
 
-extern "C" int mp_background(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren,
-                             const void* wpack_ren, const float* bias_ren, const float* dirs, const float* cam,
-                             const float* z_bg, int z_per_ray, int n_rays, float radius, float* bg_rgb, void* stream) {
+namespace {
+template <bool FOLD>
+int background(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren, const void* wpack_ren,
+               const float* bias_ren, const float* dirs, const float* cam, const float* z_bg, int z_per_ray, int n_rays,
+               float radius, float* bg_rgb, void* stream) {
     if (n_rays <= 0) return 0;
     if (!net_ok(net_imp) || !net_ok(net_ren)) return -1;
+    if (FOLD && !net_ends_in_sdf_row(net_imp)) return -1;
     hipStream_t st = (hipStream_t)stream;
     using L = Lds<3, PNB, PWAVES>;
-    MP_LDS_ATTR((k_background<PNB, PWAVES>), L::total);
+    MP_LDS_ATTR((k_background<PNB, PWAVES, FOLD>), L::total);
     const NetDesc d0 = as_desc(net_imp), d1 = as_desc(net_ren);
-    hipLaunchKernelGGL((k_background<PNB, PWAVES>), dim3(grid_for((n_rays * 32 + L::TILE - 1) / L::TILE, 1)),
+    hipLaunchKernelGGL((k_background<PNB, PWAVES, FOLD>), dim3(grid_for((n_rays * 32 + L::TILE - 1) / L::TILE, 1)),
                        dim3(PWAVES * 64), L::total, st, d0, (const char*)wpack_imp, bias_imp, d1, (const char*)wpack_ren,
                        bias_ren, dirs, cam, z_bg, z_per_ray, n_rays, radius, bg_rgb);
     return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int mp_background(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren,
+                             const void* wpack_ren, const float* bias_ren, const float* dirs, const float* cam,
+                             const float* z_bg, int z_per_ray, int n_rays, float radius, float* bg_rgb, void* stream) {
+    return background<false>(net_imp, wpack_imp, bias_imp, net_ren, wpack_ren, bias_ren, dirs, cam, z_bg, z_per_ray, n_rays,
+                             radius, bg_rgb, stream);
+}
+
+extern "C" int mp_background_fold(const MpNet* net_imp, const void* wpack_imp, const float* bias_imp, const MpNet* net_ren,
+                                  const void* wpack_ren, const float* bias_ren, const float* dirs, const float* cam,
+                                  const float* z_bg, int z_per_ray, int n_rays, float radius, float* bg_rgb, void* stream) {
+    return background<true>(net_imp, wpack_imp, bias_imp, net_ren, wpack_ren, bias_ren, dirs, cam, z_bg, z_per_ray, n_rays,
+                            radius, bg_rgb, stream);
 }

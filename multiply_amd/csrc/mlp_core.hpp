@@ -648,7 +648,10 @@ __device__ __forceinline__ bool ring_can_wrap(const NetDesc& net) { return net.t
 // One layer of the phase-separated stream (every layer kind of the plain-mode kernels: softplus with or without the
 // stored sigmoids, ReLU, the reverse sweep's multiplication by the stored sigmoids, and -- HIDDEN = false -- the linear
 // output layers).  `pp_last`: last chunk index of the network.
-template <int KS_IN, int HID, int WAVES, bool HIDDEN, typename Cap, typename NB_T>
+// KEEP_B (linear layers only): the layer is one chunk whose fp32 `out` rows are all it returns (out_chunk = 0): nothing is written
+// to Bn and Bcur is NOT replaced, so that on return it still holds the layer's INPUT -- the last hidden layer's activations,
+// which the caller hands on in place of the features that were this layer's other rows (feature fold, hip.py FoldedColor).
+template <int KS_IN, int HID, int WAVES, bool HIDDEN, bool KEEP_B = false, typename Cap, typename NB_T>
 __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc L, int l, const char* __restrict__ wpack,
                                              const float* bias_lds, char* wring, opx8 (&Bcur)[KS_REG][2], NB_T& Bn,
                                              opx8 (&aq)[AQ_LEN], u32x4 (&sg)[2], const op_t* stage_wave,
@@ -678,7 +681,7 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
     };
 #pragma unroll
     for (int c = 0; c < MAX_CHUNKS; ++c) {
-        if ((HIDDEN ? c < KS_REG : true) && c < L.n_chunk) {
+        if ((HIDDEN ? c < KS_REG : (KEEP_B ? c < 1 : true)) && c < L.n_chunk) {
             MP_STAMP(0);
             // ring_pos: the ring slot of chunk ci, carried along from chunk to chunk and -- on the continuous stream -- from tile to tile
             const int ring_next = ring_pos + 1 == RING_SLOTS ? 0 : ring_pos + 1;
@@ -786,6 +789,8 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
                 ActRegs8 a;
                 if constexpr (HID == HID_SOFTPLUS_X2) {
                     if constexpr (HIDDEN) x2_program(acc, Bn, c);   // the linear output layer: `out` holds the two partial sums
+                } else if constexpr (KEEP_B && !HIDDEN) {
+                    // `out` is all this chunk returns: no operand to build
                 } else {
                     pp_program<HID, HIDDEN, 0>(a, kact, acc, Bn, c, sg);
                 }
@@ -826,10 +831,12 @@ __device__ __forceinline__ void run_layer_pp(const NetDesc& net, const LayerDesc
             ring_pos = ring_next;
         }
     }
+    if constexpr (!(KEEP_B && !HIDDEN)) {
 #pragma unroll
-    for (int k = 0; k < KS_REG; ++k)
+        for (int k = 0; k < KS_REG; ++k)
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) Bcur[k][nb] = Bn.get(k, nb);
+            for (int nb = 0; nb < 2; ++nb) Bcur[k][nb] = Bn.get(k, nb);
+    }
 }
 
 
@@ -956,14 +963,15 @@ __device__ __forceinline__ void run_layer(const NetDesc& net, const LayerDesc L,
 
 // Runs the whole network for this wave's NB column blocks.
 //   Bcur : register K operand of layer 0 (zeros when the network input only enters through the staging tile); on
-//          return it holds the last layer's (half) output blocks (e.g. the 256 features).
+//          return it holds the last layer's (half) output blocks (e.g. the 256 features) -- with KEEP_B (phase-separated
+//          stream; the network ends in ONE linear one-chunk layer with out_chunk = 0) that layer's input instead.
 //   stage_wave : this wave's input staging tile in LDS ([16*NB rows][in_stride] halves, rows = columns): the encoded
 //          network input, read on demand as the K operand of K steps 8.. of every layer with use_in.
 //   out  : fp32 rows 0..15 of the `out_chunk` (must be the last chunk of its layer).
 // The caller must have run prologue() (the pack's first chunks in ring slots 0, 1 (, 2), barrier) -- or, on the phase-separated stream, have
 // been handed the ring by the network that ran before (rs.fed).  rs / cm / next_wpack / next_cm: the continuous weight stream
 // (RingStream); cm = chunk_masks(net), next_cm those of the pack behind next_wpack (nullptr: the ring drains with this network).
-template <int NB, bool FWD, int KS_IN, int HID, int WAVES, typename Cap = NoCapture>
+template <int NB, bool FWD, int KS_IN, int HID, int WAVES, typename Cap = NoCapture, bool KEEP_B = false>
 __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restrict__ wpack, const float* bias_lds,
                                         char* wring, opx8 (&Bcur)[KS_REG][NB], const op_t* stage_wave,
                                         f32x4 (&out)[NB], int wave, int lane, SigIO sig, Cap cap, RingStream& rs,
@@ -979,6 +987,7 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
     int l = 0;
     constexpr bool PP = !FWD && NB == 2;
     static_assert(PP || (FWD && NB == 2 && HID == HID_SOFTPLUS), "the interleaved stream (run_layer) serves the forward-mode kernel only");
+    static_assert(PP || !KEEP_B, "KEEP_B: phase-separated stream only");
     if constexpr (PP) {
         // sigmoid fragment of the chunk under construction (HID_SOFTPLUS_SAVE) / about to be applied (HID_SIGMUL)
         u32x4 sg[2];
@@ -999,7 +1008,7 @@ __device__ __forceinline__ void run_net(const NetDesc& net, const char* __restri
             run_layer_pp<KS_IN, HID, WAVES, true>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sg, stage_wave, out,
                                                   wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
         for (; l < net.n_layers; ++l)
-            run_layer_pp<KS_IN, HID, WAVES, false>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sg, stage_wave, out,
+            run_layer_pp<KS_IN, HID, WAVES, false, KEEP_B>(net, net.layer[l], l, wpack, bias_lds, wring, Bcur, Bn, aq, sg, stage_wave, out,
                                                    wave, lane, sig, cap, ci, ring_pos, cm, dl, pp_last, fed, next_wpack, next_cm);
         // handed on: the next pack's chunks 0 and 1 are in flight; or drained: the next prologue starts at slot 0
         rs.pos = next_wpack != nullptr ? ring_pos : 0;

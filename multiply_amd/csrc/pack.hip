@@ -105,6 +105,50 @@ __global__ __launch_bounds__(64) void k_pack_layers(const MpPackLayer* __restric
     }
 }
 
+// Feature fold (mp_fold_features): block r builds row r of the colour network's first layer with the SDF network's last layer
+// multiplied in.  256 threads; cold path (runs when a parameter of either layer changed).
+constexpr int FOLD_MAX_FEAT = 1024;
+__global__ __launch_bounds__(256) void k_fold_features(const float* __restrict__ vc, const float* __restrict__ gc,
+                                                       const float* __restrict__ bc, int in_c, int feat_col0, int n_feat,
+                                                       const float* __restrict__ v8, const float* __restrict__ g8,
+                                                       const float* __restrict__ b8, int in8, float* __restrict__ out_w,
+                                                       float* __restrict__ out_b) {
+    __shared__ float a[FOLD_MAX_FEAT];   // Wc_eff[r][feat_col0 + f] * (weight-norm factor of row 1 + f of the SDF layer)
+    __shared__ float sh[4];
+    const int r = blockIdx.x, t = threadIdx.x;
+    const float* row = vc + (size_t)r * in_c;
+    float sc = 1.0f;
+    if (gc) {
+        float ss = 0.0f;
+        for (int c = t; c < in_c; c += 256) ss += row[c] * row[c];
+        sc = gc[r] / sqrtf(mp::block_sum256(ss, sh));
+    }
+    float bsum = 0.0f;
+    for (int f = t; f < n_feat; f += 256) {
+        const float w = row[feat_col0 + f] * sc;
+        float s8 = 1.0f;
+        if (g8) {
+            const float* r8 = v8 + (size_t)(1 + f) * in8;
+            float ss = 0.0f;
+            for (int k = 0; k < in8; ++k) ss += r8[k] * r8[k];
+            s8 = g8[1 + f] / sqrtf(ss);
+        }
+        a[f] = w * s8;
+        bsum += w * b8[1 + f];
+    }
+    bsum = mp::block_sum256(bsum, sh);   // (its barriers also publish a[])
+    float* orow = out_w + (size_t)r * in_c;
+    for (int c = t; c < in_c; c += 256)
+        if (c < feat_col0 || c >= feat_col0 + n_feat) orow[c] = row[c] * sc;
+    for (int k = t; k < n_feat; k += 256) {
+        float acc = 0.0f;
+        if (k < in8)
+            for (int f = 0; f < n_feat; ++f) acc = __builtin_fmaf(a[f], v8[(size_t)(1 + f) * in8 + k], acc);
+        orow[feat_col0 + k] = acc;
+    }
+    if (t == 0) out_b[r] = bc[r] + bsum;
+}
+
 __global__ void k_zero_f(float* p, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.0f;
@@ -128,6 +172,17 @@ extern "C" int mp_pack_layer(const float* v, const float* g, const float* b, int
 extern "C" int mp_pack_layers(const MpPackLayer* table, int n_layers, int ks_in, void* stream) {
     if (n_layers <= 0 || n_layers > MP_MAX_LAYERS || (ks_in != 0 && ks_in != 2 && ks_in != 3)) return -1;
     hipLaunchKernelGGL(k_pack_layers, dim3(MP_BIAS_STRIDE, n_layers), dim3(64), 0, (hipStream_t)stream, table, ks_in);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_fold_features(const float* vc, const float* gc, const float* bc, int out_c, int in_c, int feat_col0,
+                                int n_feat, const float* v8, const float* g8, const float* b8, int in8, float* out_w,
+                                float* out_b, void* stream) {
+    if (out_c <= 0 || n_feat <= 0 || n_feat > FOLD_MAX_FEAT || feat_col0 < 0 || feat_col0 + n_feat > in_c || in8 <= 0 ||
+        in8 > n_feat)
+        return -1;
+    hipLaunchKernelGGL(k_fold_features, dim3(out_c), dim3(256), 0, (hipStream_t)stream, vc, gc, bc, in_c, feat_col0, n_feat,
+                       v8, g8, b8, in8, out_w, out_b);
     return (int)hipGetLastError();
 }
 

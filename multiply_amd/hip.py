@@ -398,9 +398,16 @@ def sdf_row_slots(net):
     return w[0][idx].to(torch.float16).contiguous()
 
 
-def rendering_plans(net):
+def feature_col0(net):
+    """first of the 256 feature columns of a RenderingNet's first layer"""
+    return 14 if net.mode == "pose_no_view" else 59
+
+
+def rendering_plans(net, folded=None):
     """LayerPlans of a RenderingNet: 'pose_no_view' = [x_c3, n3 | pose8 hoisted | feat256]; 'nerf_frame_encoding' =
-    [PE4(view) 27 | frame32 hoisted | feat256]."""
+    [PE4(view) 27 | frame32 hoisted | feat256].
+    folded: a FoldedLinear in place of layer 0 (FoldedColor): its feature columns multiply the SDF network's last hidden vector,
+    which arrives in scaled units h' = K h, so the register-fed K slots carry 1/K; everything else as for the layer itself."""
     plans, nl = [], net.num_layers - 1
     for l, lin in enumerate(net.layers()):
         out_dim = (lin.weight_v if hasattr(lin, "weight_v") else lin.weight).shape[0]
@@ -408,12 +415,14 @@ def rendering_plans(net):
         act = ACT_NONE if last else ACT_RELU
         rows = range(out_dim)
         if l == 0:
+            fold = {} if folded is None else dict(scale=1.0 / SOFTPLUS_K, in_scale=1.0)
+            lin = lin if folded is None else folded
             if net.mode == "pose_no_view":
                 plans.append(LayerPlan(lin, rows, reg_cols=14 + np.arange(256), in_cols=np.arange(6), hoist=(6, 8),
-                                       act=act, out_chunk=0 if last else -1))
+                                       act=act, out_chunk=0 if last else -1, **fold))
             else:
                 plans.append(LayerPlan(lin, rows, reg_cols=59 + np.arange(256), in_cols=np.arange(27), hoist=(27, 32),
-                                       act=act, out_chunk=0 if last else -1))
+                                       act=act, out_chunk=0 if last else -1, **fold))
         else:
             plans.append(LayerPlan(lin, rows, reg_cols=np.arange(net.dims[l]), act=act, out_chunk=0 if last else -1))
     return plans
@@ -507,6 +516,72 @@ def packed(module, role, ks_in):
             plans = rendering_plans(module)
         cache[key] = PackedNet(plans, ks_in, dev)
     return cache[key]
+
+
+class FoldedLinear:
+    """what mp_fold_features writes: the first layer of a rendering network as an effective fp32 weight (weight norm resolved)
+    whose feature columns hold Wc[:, feat] . W8[1:], and its bias bc + Wc[:, feat] . b8[1:].  Packed like an nn.Linear."""
+
+    def __init__(self, out_dim, in_dim, device):
+        self.weight = torch.zeros(out_dim, in_dim, dtype=torch.float32, device=device)
+        self.bias = torch.zeros(out_dim, dtype=torch.float32, device=device)
+
+
+def _lin_params(lin):
+    if hasattr(lin, "weight_g"):
+        return lin.weight_v, lin.weight_g, lin.bias
+    return lin.weight, None, lin.bias
+
+
+class FoldedColor:
+    """A rendering network PAIRED WITH its SDF network (eval path): the SDF network's last layer is linear and its 256 feature
+    rows only feed the rendering network's first layer, which is linear in them -- so the product of the two (256 x 256; 128 x
+    256 for the background) replaces both: the SDF side runs its 'sdf' plan (last layer = the sdf row alone), hands on its last
+    hidden vector h7' (scaled units) where it handed on the features, and the colour side's first layer is packed from the
+    product.  The product is formed on the device (mp_fold_features) when a parameter of EITHER of the two layers changed -- the
+    (data_ptr, _version) key of PackedNet.param_version over both, with the cache generation (invalidate_packed) -- and the pack
+    of the whole rendering network follows; per call only the hoisted pose / frame bias is refreshed, as for the plain pack."""
+
+    def __init__(self, ren, imp, ks_in):
+        self.lin_c, self.lin_8 = list(ren.layers())[0], list(imp.layers())[-1]
+        vc, v8 = _lin_params(self.lin_c)[0], _lin_params(self.lin_8)[0]
+        self.col0, self.n_feat = feature_col0(ren), v8.shape[0] - 1
+        assert self.col0 + self.n_feat == vc.shape[1] and self.n_feat == 256 and v8.shape[1] <= 256, \
+            "feature fold: the rendering network's first layer ends in the SDF network's 256 features"
+        self.folded = FoldedLinear(vc.shape[0], vc.shape[1], vc.device)
+        self.pk = PackedNet(rendering_plans(ren, self.folded), ks_in, vc.device)
+        self.version = None
+
+    def param_version(self):
+        vs = [_GENERATION[0]]
+        for lin in (self.lin_c, self.lin_8):
+            vs += [(t.data_ptr(), t._version) for t in _lin_params(lin) if t is not None]
+        return tuple(vs)
+
+    def refresh(self, hoist_vec=None, force=False):
+        """-> the PackedNet of the folded rendering network, current for the parameters of both modules and this call's
+        conditioning"""
+        ver = self.param_version()
+        stale = force or ver != self.version
+        if stale:
+            (vc, gc, bc), (v8, g8, b8) = _lin_params(self.lin_c), _lin_params(self.lin_8)
+            flat = lambda t: None if t is None else t.detach().reshape(-1).contiguous()
+            lib().mp_fold_features(vc.detach().contiguous(), flat(gc), flat(bc), vc.shape[0], vc.shape[1], self.col0, self.n_feat,
+                                   v8.detach().contiguous(), flat(g8), flat(b8), v8.shape[1], self.folded.weight,
+                                   self.folded.bias, stream())
+            self.version = ver
+        self.pk.refresh(hoist_vec, force=stale)
+        return self.pk
+
+
+def folded_color(ren, imp, ks_in):
+    """the FoldedColor of a rendering network and its SDF network (cached on the rendering module, per SDF module)"""
+    cache = ren.__dict__.setdefault("_mp_folded", {})
+    key = (id(imp), ks_in, str(next(ren.parameters()).device))
+    fc = cache.get(key)
+    if fc is None or fc.lin_8 is not list(imp.layers())[-1]:
+        fc = cache[key] = FoldedColor(ren, imp, ks_in)
+    return fc
 
 
 class PoseEmbed:
@@ -632,10 +707,12 @@ def sig_scratch(device, n_points):
 _SCRATCH = {}
 
 
-def shade_rev_launch(pki, gn, x_c, jinv, worklist, count, n, sdf, nrm, feat):
+def shade_rev_launch(pki, gn, x_c, jinv, worklist, count, n, sdf, nrm, feat, fold=False):
+    """fold: pki is the 'sdf' pack and feat receives h7' for a FoldedColor pack (mp_mlp_shade_rev_fold)"""
     buf, seg = sig_scratch(x_c.device, n)
-    lib().mp_mlp_shade_rev(C.byref(pki.net), pki.wpack, pki.bias, C.byref(gn.pk.net), gn.pk.wpack, gn.w8, x_c, jinv, worklist,
-                           count, n, sdf, nrm, feat, buf, seg, stream())
+    fn = lib().mp_mlp_shade_rev_fold if fold else lib().mp_mlp_shade_rev
+    fn(C.byref(pki.net), pki.wpack, pki.bias, C.byref(gn.pk.net), gn.pk.wpack, gn.w8, x_c, jinv, worklist, count, n, sdf, nrm,
+       feat, buf, seg, stream())
 
 
 def feat_frag_bytes(n):
@@ -644,25 +721,31 @@ def feat_frag_bytes(n):
     return (int(n) + 255) // 256 * 4 * 8 * 4 * 1024
 
 
-def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None):
+def shade_points(imp, ren, x_c, jinv, cond_vec, mode=None, fold=False):
     """sdf, normals, rgb at canonical points (ImplicitNet value + input gradient, RenderingNet 'pose_no_view').
-    mode 'reverse': mp_mlp_shade_rev (two sweeps); 'forward': the forward-mode kernel mp_mlp_shade."""
+    mode 'reverse': mp_mlp_shade_rev (two sweeps); 'forward': the forward-mode kernel mp_mlp_shade.
+    fold (reverse mode only): the feature fold the renderer uses (FoldedColor, mp_mlp_shade_rev_fold)."""
     require_device()
     n = x_c.shape[0]
     x_c = x_c.detach().float().contiguous()
     jinv = jinv.detach().float().contiguous()
     cond_vec = cond_vec.detach().float().contiguous()
-    pki = packed(imp, "full", 2)
+    if fold and (mode or SHADE_MODE) != "reverse":
+        raise ValueError("the feature fold exists in reverse-mode shading only: the forward-mode kernel is its unfolded cross-check")
+    pki = packed(imp, "sdf" if fold else "full", 2)
     pki.refresh(cond_vec)
-    pkr = packed(ren, "color", 2)
-    pkr.refresh(pose_embed(ren)(cond_vec))
+    if fold:
+        pkr = folded_color(ren, imp, 2).refresh(pose_embed(ren)(cond_vec))
+    else:
+        pkr = packed(ren, "color", 2)
+        pkr.refresh(pose_embed(ren)(cond_vec))
     dev = x_c.device
     sdf = torch.empty(n, dtype=torch.float32, device=dev)
     nrm = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
     feat = torch.empty(feat_frag_bytes(n), dtype=torch.uint8, device=dev)
     if (mode or SHADE_MODE) == "reverse":
-        shade_rev_launch(pki, grad_net(imp), x_c, jinv, None, None, n, sdf, nrm, feat)
+        shade_rev_launch(pki, grad_net(imp), x_c, jinv, None, None, n, sdf, nrm, feat, fold=fold)
     else:
         lib().mp_mlp_shade(C.byref(pki.net), pki.wpack, pki.bias, x_c, jinv, None, None, n, sdf, nrm, feat, stream())
     lib().mp_mlp_color(C.byref(pkr.net), pkr.wpack, pkr.bias, x_c, nrm, feat, None, None, n, rgb, stream())
@@ -713,24 +796,29 @@ def rendering_forward(net, points, normals, view_dirs, body_pose, feature_vector
     return rgb
 
 
-def background(bg_imp, bg_ren, dirs, cam, z_bg, frame_code, radius=3.0):
-    """bg_rgb (R,3) of the NeRF++ background branch. z_bg: (n_bg,) shared or (R,n_bg) per-ray inverse depths, descending."""
+def background(bg_imp, bg_ren, dirs, cam, z_bg, frame_code, radius=3.0, fold=False):
+    """bg_rgb (R,3) of the NeRF++ background branch. z_bg: (n_bg,) shared or (R,n_bg) per-ray inverse depths, descending.
+    fold: the feature fold the renderer uses (FoldedColor, mp_background_fold)."""
     require_device()
     dirs = dirs.detach().float().contiguous()
     cam = cam.detach().float().contiguous()
     z_bg = z_bg.detach().float().contiguous()
     code = frame_code.detach().float().reshape(-1).contiguous()
-    pki = packed(bg_imp, "full", 3)
+    pki = packed(bg_imp, "sdf" if fold else "full", 3)
     pki.refresh(code)
-    pkr = packed(bg_ren, "color", 3)
-    pkr.refresh(code)
+    if fold:
+        pkr = folded_color(bg_ren, bg_imp, 3).refresh(code)
+    else:
+        pkr = packed(bg_ren, "color", 3)
+        pkr.refresh(code)
     R = dirs.shape[0]
     if z_bg.shape[-1] != 32:
         raise NotImplementedError("the fused background kernel is specialised for the 32 inverse-sphere samples of the shipped "
                                   f"configs (N_samples_inverse_sphere), got {z_bg.shape[-1]}")
     out = torch.empty(R, 3, dtype=torch.float32, device=dirs.device)
-    lib().mp_background(C.byref(pki.net), pki.wpack, pki.bias, C.byref(pkr.net), pkr.wpack, pkr.bias, dirs, cam, z_bg,
-                        int(z_bg.dim() == 2), R, radius, out, stream())
+    fn = lib().mp_background_fold if fold else lib().mp_background
+    fn(C.byref(pki.net), pki.wpack, pki.bias, C.byref(pkr.net), pkr.wpack, pkr.bias, dirs, cam, z_bg, int(z_bg.dim() == 2), R,
+       radius, out, stream())
     return out
 
 

@@ -129,6 +129,9 @@ class Multiply(nn.Module):
         self.sdf_bounding_sphere = 3.0
         self.threshold = 0.05
         self.shade_mode = hip.SHADE_MODE      # 'reverse' | 'forward' (csrc/mlp.hip: k_mlp_shade_rev | k_mlp_shade)
+        # the SDF networks' feature rows folded into the colour networks' first layer (hip.FoldedColor): reverse-mode shading and the
+        # background; False = the unfolded entry points (the cross-check; forward-mode shading is always unfolded)
+        self.feature_fold = True
         # in / off-surface flags (training, epochs < 250): 'auto' | 'index' | 'brute' -- the face index (csrc/mesh_index.hip) or brute
         # force (csrc/mesh.hip), same values; 'auto' = the index for a closed surface of hip.MESH_INDEX_MIN_FACES faces or more, where it
         # was measured to win (hip.mesh_index_wanted); MP_MESH_INDEX=0: brute; fit_smpl_init(model, ...) follows it too
@@ -514,14 +517,18 @@ class Multiply(nn.Module):
         with self._ph("shade_jacobian"):
             L.mp_warp_jacobian(xc, need, pp["count"], Rp, S, 0, dfm.vsorted_c, dfm.cbound_c, pp["btab"], jinv, None, nn_posed,
                                dfm.verts_c_flat, st)
-        pk_full = hip.packed(imp, "full", 2)
+        fold = self.feature_fold and self.shade_mode == "reverse"
+        pk_full = hip.packed(imp, "sdf" if fold else "full", 2)      # fold: the sampler's pack, feat carries h7'
         pk_full.refresh(pp["cond"])
-        pk_col = hip.packed(ren, "color", 2)
-        pk_col.refresh(hip.pose_embed(ren)(pp["cond"]))
+        if fold:
+            pk_col = hip.folded_color(ren, imp, 2).refresh(hip.pose_embed(ren)(pp["cond"]))
+        else:
+            pk_col = hip.packed(ren, "color", 2)
+            pk_col.refresh(hip.pose_embed(ren)(pp["cond"]))
         feat = torch.empty(hip.feat_frag_bytes(npts), dtype=torch.uint8, device=dev)
         with self._ph("mlp_shade"):
             if self.shade_mode == "reverse":     # value sweep (parks the sigmoids) + reverse sweep for the normals
-                hip.shade_rev_launch(pk_full, hip.grad_net(imp), xc, jinv, work2, wc2, npts, sdf, nrm, feat)
+                hip.shade_rev_launch(pk_full, hip.grad_net(imp), xc, jinv, work2, wc2, npts, sdf, nrm, feat, fold=fold)
             else:
                 L.mp_mlp_shade(C.byref(pk_full.net), pk_full.wpack, pk_full.bias, xc, jinv, work2, wc2, npts, sdf, nrm, feat, st)
         with self._ph("mlp_color"):
@@ -543,7 +550,7 @@ class Multiply(nn.Module):
         with self._ph("background"):
             return hip.background(self.bg_implicit_network, self.bg_rendering_network, cx["dirs"],
                                   cx["pose"].reshape(4, 4)[:3, 3].contiguous(), z_bg, code,
-                                  radius=self.sdf_bounding_sphere)
+                                  radius=self.sdf_bounding_sphere, fold=self.feature_fold)
 
     def _composite(self, cx, persons, bg_rgb):
         """Packed multi-person compositing of the per-person sample arrays in cx['per'] for the subset `persons`

@@ -276,7 +276,8 @@ def render_person_sharded(model, input, canonical_pose=False, group=None, exchan
         t = torch.linspace(0.0, 1.0, rs.N_samples_inverse_sphere, device=dev)
         z_bg = torch.flip(t * (1.0 / rs.scene_bounding_sphere), dims=[0]).contiguous()
         bg_rgb = hip.background(model.bg_implicit_network, model.bg_rendering_network, dirs,
-                                pose.reshape(4, 4)[:3, 3].contiguous(), z_bg, code, radius=model.sdf_bounding_sphere)
+                                pose.reshape(4, 4)[:3, 3].contiguous(), z_bg, code, radius=model.sdf_bounding_sphere,
+                                fold=model.feature_fold)
     out = {k: torch.empty(n_my, 3, **f32) for k in ("rgb_values", "fg_rgb_values", "normal_values")}
     acc_map = torch.empty(n_my, **f32); acc_person = torch.empty(n_my, P, **f32); bg_T = torch.empty(n_my, **f32)
     L.mp_composite(n_my, P, NZ, *tabs, beta, bg_rgb, out["rgb_values"], out["fg_rgb_values"], out["normal_values"], acc_map,

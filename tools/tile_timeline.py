@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Ablation tool: shader-clock timeline of the last TWO tiles of workgroup 0 of k_mlp_sdf (library built with -DMP_EXP_STAMP):
 tile-level phases (input staging, prologue, network, output) and the start time of every weight chunk per wave.
-    MP_LIB_PATH=.../libmultiply_hip_stamp.so python tools/tile_timeline.py"""
+    MP_LIB_PATH=.../libmultiply_hip_stamp.so python tools/tile_timeline.py [sdf | fwdsave | grad | color] [--fold]
+--fold: the shading kernels in feature-fold mode (mp_mlp_shade_rev_fold on the 'sdf' pack, hip.FoldedColor)"""
 import ctypes as C, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +16,8 @@ cond = torch.randn(69, device="cuda") * 0.1
 L = hip.lib()
 L.mp_debug_stamps.argtypes = [C.c_void_p]; L.mp_debug_stamps.restype = C.c_int
 buf = np.zeros(8 * 128 * 4, dtype=np.uint64)
+FOLD = "--fold" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--fold"]
 which = sys.argv[1] if len(sys.argv) > 1 else "sdf"       # sdf | fwdsave | grad | color (the last kernel launched is stamped)
 ren = m.foreground_rendering_network_list[0]
 jinv = torch.eye(3, device="cuda").reshape(1, 9).repeat(n, 1).contiguous()
@@ -22,16 +25,16 @@ for _ in range(2):
     if which == "sdf":
         hip.implicit_sdf(imp, x, cond)
     elif which == "color":
-        hip.shade_points(imp, ren, x, jinv, cond)
+        hip.shade_points(imp, ren, x, jinv, cond, fold=FOLD)
     else:
-        pki = hip.packed(imp, "full", 2); pki.refresh(cond)
+        pki = hip.packed(imp, "sdf" if FOLD else "full", 2); pki.refresh(cond)
         sdf = torch.empty(n, device="cuda"); nrm = torch.empty(n, 3, device="cuda")
         feat = torch.empty((n + 255) // 256 * 4 * 8 * 4 * 1024, dtype=torch.uint8, device="cuda")
         if which == "grad":
-            hip.shade_rev_launch(pki, hip.grad_net(imp), x, jinv, None, None, n, sdf, nrm, feat)
+            hip.shade_rev_launch(pki, hip.grad_net(imp), x, jinv, None, None, n, sdf, nrm, feat, fold=FOLD)
         else:   # fwdsave: launch the pair, then the forward sweep alone is not separable -> stamp build marks only fwdsave
             os.environ["MP_TIMELINE_FWD_ONLY"] = "1"
-            hip.shade_rev_launch(pki, hip.grad_net(imp), x, jinv, None, None, n, sdf, nrm, feat)
+            hip.shade_rev_launch(pki, hip.grad_net(imp), x, jinv, None, None, n, sdf, nrm, feat, fold=FOLD)
 torch.cuda.synchronize()
 assert L.mp_debug_stamps(buf.ctypes.data) == 0
 s = buf.reshape(8, 128, 4).astype(np.int64)
