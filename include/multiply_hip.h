@@ -185,6 +185,19 @@ int mp_smpl_pose(const float* v_template, const float* shapedirs, const float* p
 #define MP_SMPL_DLBS (24 * 16 + 207 + 86)
 int mp_smpl_verts_bwd(const float* posedirs, const float* shapedirs, const float* lbs_weights, const float* params,
                       const float* work, const float* dverts, float* scratch, float* dlbs, void* stream);
+/* mp_smpl_pose for N parameter rows params [N][86] against one table set, forward only, in two launches whatever N is (one
+ * when verts is NULL): the chain runs one workgroup per row, and the vertex kernel stages each 207 x 96 tile of posedirs once
+ * per workgroup and sweeps it over all rows, MP_SMPL_BATCH_ROWS at a time -- posedirs is read once per call, not once per row.
+ * Outputs verts [N][V][3], tfs [N][24][16], joints [N][24][3]; each may be NULL to skip it.  tfs_c_inv as in mp_smpl_pose.
+ * work: N * MP_SMPL_BATCH_ROW_WORK floats (per row: rest joints [72] at 0, rest-relative transforms [24][16] at 80, pose
+ * feature [207] at 464).  The arithmetic per row is mp_smpl_pose's, and a row's operations and their order depend neither on N
+ * nor on the row's position: a row has the same bits alone and inside any batch.  No atomics.
+ * Status -1 without a launch: N < 0, a NULL table, NULL params / work with N > 0; N == 0 returns 0. */
+#define MP_SMPL_BATCH_ROWS 16
+#define MP_SMPL_BATCH_ROW_WORK 672
+int mp_smpl_pose_batch(const float* v_template, const float* shapedirs, const float* posedirs, const float* j_regressor,
+                       const float* lbs_weights, const int* parents, const float* params, int N, const float* tfs_c_inv,
+                       float* verts, float* tfs, float* joints, float* work, void* stream);
 
 /* Nearest-neighbour acceleration structure over one vertex set (exact K=1 search, replaces
  * pytorch3d.ops.knn_points, deformer.py:39): vertices gathered in cluster order + bounding spheres.
@@ -786,6 +799,35 @@ int mp_image_ssim(const float* a, const float* b, const unsigned char* mask, int
                   void* work, double* out, float* map, void* stream);
 int mp_image_sqerr(const float* a, const float* b, const unsigned char* mask, int N, int H, int W, int C, void* work,
                    double* out, void* stream);
+
+/* ---- pose metrics (multiply_amd/pose_metrics.py, csrc/pose_metrics.hip): MPJPE / MVE and the contact distance.
+ *   mp_pose_errors      : M items of n points, pred [M][n][3] against gt [M][n][3], optional roots pred_root / gt_root [M][3]
+ *                         (both or neither) -> out [M][4] DOUBLES per item:
+ *                           out[0] mean |p_i - x_i|                                  (plain)
+ *                           out[1] mean |(p_i - pred_root) - (x_i - gt_root)|        (root-aligned; NaN without roots)
+ *                           out[2] mean |s R p_i + t - x_i|, (s, R, t) the least-squares similarity transform with det R = +1
+ *                                  (Umeyama 1991): H = sum (p_i - mean p)(x_i - mean x)^T = U S V^T, D = diag(1, 1, sign det(V U^T)),
+ *                                  R = V D U^T, s = tr(S D) / sum |p_i - mean p|^2, t = mean x - s R mean p; exactly 0 when the
+ *                                  two sets are equal (the identity attains the minimum)
+ *                           out[3] 0, or why the item is left out: 1 = a non-finite coordinate (points or roots): all three
+ *                                  values NaN; 2 = the predicted points all coincide (sum |p_i - mean p|^2 is exactly 0; tested
+ *                                  point against point, a sum about a rounded mean need not be 0): out[2] alone is NaN.
+ *                         One workgroup per item, three passes over its points (means and the first two sums; H about the means;
+ *                         the residual), every sum in double on the fp32 inputs in a fixed order, the 3 x 3 SVD in double by
+ *                         one-sided Jacobi rotations.  Status -1 without a launch: M < 0, n < 1, a NULL pred / gt / out with M > 0,
+ *                         exactly one root; M == 0 returns 0.
+ *   mp_contact_distance : bodies verts [F][P][V][3], faces [n_faces][3], m correspondences SORTED BY FRAME: corr [m][5] = frame,
+ *                         person a, vertex of a, person b, face of b; bary [m][3]; frame_start [F + 1] = the first correspondence of
+ *                         each frame (frame_start[F] = m).  Distance of one: | v[f, a, vertex] - sum_k bary_k v[f, b, faces[face][k]] |
+ *                         in double; an id out of range (or a frame other than the slot's) gives NaN.  out [2 + 2 F] DOUBLES =
+ *                         overall mean (NaN for m = 0), m, then the per-frame means (NaN for a frame without one) and the per-frame
+ *                         counts.  One workgroup per frame writes its sum to work [F] doubles, a finishing pass adds those in
+ *                         frame order: no atomics, bit-identical from call to call.  Status -1 without a launch: F < 1, P < 1,
+ *                         V < 1, n_faces < 1, m < 0, a NULL verts / faces / frame_start / work / out, NULL corr / bary with m > 0. */
+int mp_pose_errors(const float* pred, const float* gt, const float* pred_root, const float* gt_root, int M, int n, double* out,
+                   void* stream);
+int mp_contact_distance(const float* verts, int F, int P, int V, const int* faces, int n_faces, const int* corr, const float* bary,
+                        const int* frame_start, int m, double* work, double* out, void* stream);
 
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);

@@ -1,5 +1,5 @@
-// SMPL body model: shape and pose blend shapes, kinematic chain, linear blend skinning (mp_smpl_pose), the adjoint of the
-// posed vertices (mp_smpl_verts_bwd) and of the chain (mp_smpl_pose_bwd, mp_smpl_pose_bwd_lbs).
+// SMPL body model: shape and pose blend shapes, kinematic chain, linear blend skinning (mp_smpl_pose; N rows in two launches:
+// mp_smpl_pose_batch), the adjoint of the posed vertices (mp_smpl_verts_bwd) and of the chain (mp_smpl_pose_bwd, mp_smpl_pose_bwd_lbs).
 // Entry points and the reference code they replace: include/multiply_hip.h.
 #include <hip/hip_runtime.h>
 #include "../../include/multiply_hip.h"
@@ -169,6 +169,249 @@ extern "C" int mp_smpl_pose(const float* v_template, const float* shapedirs, con
     hipLaunchKernelGGL(k_smpl_joints, dim3(NJ), dim3(256), 0, st, j_regressor, work);
     hipLaunchKernelGGL(k_smpl_chain, dim3(1), dim3(64), 0, st, parents, params, tfs_c_inv, work, tfs, joints);
     hipLaunchKernelGGL(k_smpl_verts, dim3((V + 255) / 256), dim3(256), 0, st, posedirs, lbs_weights, params, work, verts);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// ---- N parameter rows in two launches (mp_smpl_pose_batch), forward only.
+//   k_smpl_batch_chain  one workgroup per row: the rest joints from v_shaped formed on the fly (per thread the vertices t, t + 256,
+//                       ... in order, then block_sum256: k_smpl_shape + k_smpl_joints in one), then smpl_batch_chain_row.  Leaves
+//                       J | A | pose feature in the row's work slice.
+//   k_smpl_batch_verts  one workgroup per BT_V = 32 vertices: the 207 x 96 tile of posedirs is staged in LDS ONCE and swept over
+//                       all rows, BT_ROWS = 16 at a time.  Thread (slot, column) holds its column's v_template and shapedirs in
+//                       registers and runs the 207-term sums of the slot's four rows off one LDS read of the tile per term; the
+//                       blend and the skinning then go one thread per (row, vertex).
+// A row's operations and their order do not depend on N or on where the row stands (rows only share the tile), so a row has the
+// same bits alone and in any batch.  No atomics.
+constexpr int BW_J = 0, BW_A = 80, BW_PF = BW_A + NJ * 16, BW_ROW = MP_SMPL_BATCH_ROW_WORK;
+constexpr int BT_V = 32, BT_COLS = 3 * BT_V, BT_SLOTS = 4, BT_RB = 4, BT_ROWS = BT_SLOTS * BT_RB, BT_THREADS = BT_SLOTS * BT_COLS;
+constexpr int BT_BLOCKS = (V + BT_V - 1) / BT_V, BT_WLD = NJ + 1, BT_PRM = 16;
+static_assert(BW_PF + 207 <= BW_ROW && BT_ROWS == MP_SMPL_BATCH_ROWS && BT_THREADS % 64 == 0 && BT_COLS % 2 == 0 && BT_RB == 4,
+              "layout of mp_smpl_pose_batch");
+
+// Rodrigues, pose feature, kinematic chain and SMPLServer.forward's scaling of ONE row by the first 24 threads of a workgroup of
+// 256 (every thread must call: two barriers).  The statements of k_smpl_chain, written again instead of shared: moving that
+// kernel's body into a function changed how the compiler contracts six of its multiply-adds, and mp_smpl_pose keeps its bits.
+// J: the row's rest joints (LDS); wA / wPF: where its rest-relative transforms [24][16] and pose feature [207] go; tfs / joints:
+// the row's outputs, either may be NULL.
+__device__ __forceinline__ void smpl_batch_chain_row(const int* __restrict__ parents, const float* __restrict__ params,
+                                                     const float* __restrict__ tfs_c_inv, const float* J, float* __restrict__ wA,
+                                                     float* __restrict__ wPF, float* __restrict__ tfs, float* __restrict__ joints,
+                                                     float (*R)[9], float (*G)[16]) {
+    const int t = threadIdx.x;
+    const float scale = params[0];
+    const float* transl = params + 1;
+    const float* thetas = params + 4;
+    if (t < NJ) {  // batch_rodrigues, lbs.py:276-307
+        const float rx0 = thetas[3 * t], ry0 = thetas[3 * t + 1], rz0 = thetas[3 * t + 2];
+        const float ax = rx0 + 1e-8f, ay = ry0 + 1e-8f, az = rz0 + 1e-8f;
+        const float angle = sqrtf(ax * ax + ay * ay + az * az);
+        const float rx = rx0 / angle, ry = ry0 / angle, rz = rz0 / angle;
+        float s, c;
+        sincosf(angle, &s, &c);
+        const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+        float KK[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                float a = 0.f;
+                for (int k = 0; k < 3; ++k) a += K[3 * i + k] * K[3 * k + j];
+                KK[3 * i + j] = a;
+            }
+        for (int i = 0; i < 9; ++i) R[t][i] = ((i % 4 == 0) ? 1.0f : 0.0f) + s * K[i] + (1.0f - c) * KK[i];
+    }
+    __syncthreads();
+    for (int i = t; i < 207; i += 256) {  // pose_feature = (R[1:] - I).flatten (lbs.py:199)
+        const int j = i / 9 + 1, e = i % 9;
+        wPF[i] = R[j][e] - ((e % 4 == 0) ? 1.0f : 0.0f);
+    }
+    if (t == 0) {  // batch_rigid_transform, lbs.py:323-377 (24 tiny sequential 4x4 products)
+        for (int j = 0; j < NJ; ++j) {
+            const int p = parents[j];
+            float rel[3];
+            for (int a = 0; a < 3; ++a) rel[a] = J[3 * j + a] - (j > 0 ? J[3 * p + a] : 0.0f);
+            float tm[16];
+            for (int a = 0; a < 3; ++a) {
+                for (int b = 0; b < 3; ++b) tm[4 * a + b] = R[j][3 * a + b];
+                tm[4 * a + 3] = rel[a];
+            }
+            tm[12] = tm[13] = tm[14] = 0.f;
+            tm[15] = 1.f;
+            if (j == 0) for (int i = 0; i < 16; ++i) G[0][i] = tm[i];
+            else mat4_mul(G[p], tm, G[j]);
+        }
+    }
+    __syncthreads();
+    if (t < NJ) {
+        float A[16];
+        for (int i = 0; i < 16; ++i) A[i] = G[t][i];
+        for (int a = 0; a < 4; ++a) {  // rel_transforms = G - pad(G @ [J;0])  (lbs.py:372-375)
+            float s = 0.f;
+            for (int k = 0; k < 3; ++k) s += G[t][4 * a + k] * J[3 * t + k];
+            A[4 * a + 3] -= s;
+        }
+        for (int i = 0; i < 16; ++i) wA[16 * t + i] = A[i];
+        float tf[16];  // SMPLServer.forward scaling (smpl.py:80-91)
+        for (int i = 0; i < 16; ++i) tf[i] = A[i];
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 4; ++b) tf[4 * a + b] *= scale;
+            tf[4 * a + 3] += transl[a] * scale;
+        }
+        if (tfs && tfs_c_inv) {
+            float o[16];
+            mat4_mul(tf, tfs_c_inv + 16 * t, o);
+            for (int i = 0; i < 16; ++i) tfs[16 * t + i] = o[i];
+        } else if (tfs) {
+            for (int i = 0; i < 16; ++i) tfs[16 * t + i] = tf[i];
+        }
+        if (joints)
+            for (int a = 0; a < 3; ++a) joints[3 * t + a] = G[t][4 * a + 3] * scale + transl[a] * scale;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_smpl_batch_chain(const float* __restrict__ v_template,
+                                                          const float* __restrict__ shapedirs,
+                                                          const float* __restrict__ j_regressor,
+                                                          const int* __restrict__ parents, const float* __restrict__ params,
+                                                          const float* __restrict__ tfs_c_inv, float* __restrict__ work,
+                                                          float* __restrict__ tfs, float* __restrict__ joints) {
+    __shared__ float R[NJ][9];
+    __shared__ float G[NJ][16];
+    __shared__ float Js[3 * NJ], sh[4];
+    const int t = threadIdx.x;
+    const size_t n = blockIdx.x;
+    const float* prm = params + n * 86;
+    float* w = work + n * BW_ROW;
+    float betas[10], acc[3 * NJ];
+#pragma unroll
+    for (int l = 0; l < 10; ++l) betas[l] = prm[76 + l];
+#pragma unroll
+    for (int e = 0; e < 3 * NJ; ++e) acc[e] = 0.f;
+    for (int i = t; i < V; i += 256) {
+        float vs[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float a = 0.0f;
+#pragma unroll
+            for (int l = 0; l < 10; ++l) a += betas[l] * shapedirs[(size_t)(3 * i + k) * 10 + l];  // blend_shapes, lbs.py:252-273
+            vs[k] = v_template[3 * i + k] + a;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {                              // vertices2joints, lbs.py:232-249
+            const float wj = j_regressor[(size_t)j * V + i];
+            acc[3 * j] += wj * vs[0];
+            acc[3 * j + 1] += wj * vs[1];
+            acc[3 * j + 2] += wj * vs[2];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 3 * NJ; ++e) {
+        const float s = mp::block_sum256(acc[e], sh);
+        if (t == 0) { Js[e] = s; w[BW_J + e] = s; }
+    }
+    __syncthreads();
+    smpl_batch_chain_row(parents, prm, tfs_c_inv, Js, w + BW_A, w + BW_PF, tfs ? tfs + n * NJ * 16 : nullptr,
+                         joints ? joints + n * NJ * 3 : nullptr, R, G);
+}
+
+__global__ __launch_bounds__(BT_THREADS) void k_smpl_batch_verts(const float* __restrict__ posedirs,
+                                                                 const float* __restrict__ shapedirs,
+                                                                 const float* __restrict__ v_template,
+                                                                 const float* __restrict__ lbs_weights,
+                                                                 const float* __restrict__ params,
+                                                                 const float* __restrict__ work, int N,
+                                                                 float* __restrict__ verts) {
+    __shared__ float P[207 * BT_COLS];
+    __shared__ __attribute__((aligned(16))) float pfs[BT_SLOTS * 207 * BT_RB];   // [slot][term][row of the slot]
+    __shared__ float As[BT_ROWS * NJ * 12], W[BT_V * BT_WLD], pv[BT_ROWS * BT_COLS], prm[BT_ROWS * BT_PRM];
+    const int t = threadIdx.x, v0 = blockIdx.x * BT_V, nv = min(BT_V, V - v0);
+    const int slot = t / BT_COLS, c = t % BT_COLS, gc = 3 * v0 + c;
+    for (int e = t; e < 207 * (BT_COLS / 2); e += BT_THREADS) {   // the tile, 8-byte loads (3V and the tile's first column are even)
+        const int r = e / (BT_COLS / 2), cc = 2 * (e % (BT_COLS / 2)), g = 3 * v0 + cc;
+        float2 x = make_float2(0.f, 0.f);
+        if (g < 3 * V) x = *reinterpret_cast<const float2*>(posedirs + (size_t)r * (3 * V) + g);
+        P[r * BT_COLS + cc] = x.x;
+        P[r * BT_COLS + cc + 1] = x.y;
+    }
+    for (int i = t; i < BT_V * NJ; i += BT_THREADS)
+        W[(i / NJ) * BT_WLD + i % NJ] = i < nv * NJ ? lbs_weights[(size_t)v0 * NJ + i] : 0.f;
+    float sd[10], vt = 0.f;
+#pragma unroll
+    for (int l = 0; l < 10; ++l) sd[l] = gc < 3 * V ? shapedirs[(size_t)gc * 10 + l] : 0.f;
+    if (gc < 3 * V) vt = v_template[gc];
+    for (int n0 = 0; n0 < N; n0 += BT_ROWS) {
+        __syncthreads();                                          // the pass before has read its rows
+        for (int e = t; e < BT_ROWS * 207; e += BT_THREADS) {
+            const int row = e / 207, r = e % 207;
+            pfs[((row / BT_RB) * 207 + r) * BT_RB + row % BT_RB] =
+                n0 + row < N ? work[(size_t)(n0 + row) * BW_ROW + BW_PF + r] : 0.f;
+        }
+        for (int e = t; e < BT_ROWS * NJ * 12; e += BT_THREADS) {
+            const int row = e / (NJ * 12), i = e % (NJ * 12);
+            As[e] = n0 + row < N ? work[(size_t)(n0 + row) * BW_ROW + BW_A + 16 * (i / 12) + i % 12] : 0.f;
+        }
+        for (int e = t; e < BT_ROWS * BT_PRM; e += BT_THREADS) {  // per row: betas [10], scale, transl [3]
+            const int row = e / BT_PRM, q = e % BT_PRM;
+            float x = 0.f;
+            if (n0 + row < N && q < 14) x = params[(size_t)(n0 + row) * 86 + (q < 10 ? 76 + q : q - 10)];
+            prm[e] = x;
+        }
+        __syncthreads();
+        float acc[BT_RB] = {0.f, 0.f, 0.f, 0.f};
+        const float4* pf4 = reinterpret_cast<const float4*>(pfs) + slot * 207;
+        for (int q = 0; q < 207; ++q) {                           // lbs.py:201-202, the order of k_smpl_verts
+            const float p = P[q * BT_COLS + c];
+            const float4 f = pf4[q];
+            acc[0] += f.x * p;
+            acc[1] += f.y * p;
+            acc[2] += f.z * p;
+            acc[3] += f.w * p;
+        }
+#pragma unroll
+        for (int k = 0; k < BT_RB; ++k) {
+            const int row = slot * BT_RB + k;
+            float a = 0.0f;
+#pragma unroll
+            for (int l = 0; l < 10; ++l) a += prm[row * BT_PRM + l] * sd[l];
+            pv[row * BT_COLS + c] = acc[k] + (vt + a);
+        }
+        __syncthreads();
+        for (int it = t; it < BT_ROWS * BT_V; it += BT_THREADS) {
+            const int row = it / BT_V, vl = it % BT_V;
+            if (n0 + row >= N || vl >= nv) continue;
+            float T[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) T[i] = 0.f;
+            for (int j = 0; j < NJ; ++j) {                        // lbs.py:217-221
+                const float w = W[vl * BT_WLD + j];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) T[i] += w * As[(row * NJ + j) * 12 + i];
+            }
+            const float* p = pv + row * BT_COLS + 3 * vl;
+            const float scale = prm[row * BT_PRM + 10];
+            float* out = verts + ((size_t)(n0 + row) * V + v0 + vl) * 3;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float x = T[4 * a] * p[0] + T[4 * a + 1] * p[1] + T[4 * a + 2] * p[2] + T[4 * a + 3];
+                out[a] = x * scale + prm[row * BT_PRM + 11 + a] * scale;  // smpl.py:77-78
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int mp_smpl_pose_batch(const float* v_template, const float* shapedirs, const float* posedirs,
+                                  const float* j_regressor, const float* lbs_weights, const int* parents, const float* params,
+                                  int N, const float* tfs_c_inv, float* verts, float* tfs, float* joints, float* work,
+                                  void* stream) {
+    if (N < 0 || !v_template || !shapedirs || !posedirs || !j_regressor || !lbs_weights || !parents) return -1;
+    if (N == 0) return 0;
+    if (!params || !work) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_smpl_batch_chain, dim3(N), dim3(256), 0, st, v_template, shapedirs, j_regressor, parents, params,
+                       tfs_c_inv, work, tfs, joints);
+    if (verts)
+        hipLaunchKernelGGL(k_smpl_batch_verts, dim3(BT_BLOCKS), dim3(BT_THREADS), 0, st, posedirs, shapedirs, v_template,
+                           lbs_weights, params, work, N, verts);
     return (int)hipGetLastError();
 }
 

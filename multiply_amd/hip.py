@@ -19,6 +19,7 @@ MAX_LAYERS, MAX_CHUNKS, BIAS_STRIDE = 10, 9, 288
 ACT_NONE, ACT_SOFTPLUS, ACT_RELU, ACT_SIGMUL = 0, 1, 2, 3
 KNN_CLUSTER, KNN_NC = int(os.environ.get("MP_KNN_CLUSTER", 32)), int(os.environ.get("MP_KNN_NC", 216))   # = include/multiply_hip.h
 SMPL_VBWD_SCRATCH, SMPL_DLBS = 216 * 512, 24 * 16 + 207 + 86     # = include/multiply_hip.h (mp_smpl_verts_bwd)
+SMPL_BATCH_ROWS, SMPL_BATCH_ROW_WORK = 16, 672                   # = include/multiply_hip.h (mp_smpl_pose_batch)
 KNN_CB_ROWS = KNN_NC + KNN_NC // 2      # mp_knn_build's sphere table: the clusters, then the pairs of clusters the training searches use
 
 
@@ -1096,4 +1097,53 @@ def image_sqerr(a, b, mask=None):
     N, H, W, Cn = a.shape
     out = torch.empty(N, 5, dtype=torch.float64, device=a.device)
     lib().mp_image_sqerr(a, b, mask, N, H, W, Cn, _image_work(N, H, W, Cn, a.device), out, stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ pose metrics (csrc/pose_metrics.hip)
+def pose_errors(pred, gt, pred_root=None, gt_root=None):
+    """Per item the three mean distances of pred against gt, both (M, n, 3) float32 device tensors, with optional roots (M, 3)
+    (mp_pose_errors): (M, 4) float64 on the device = plain, root-aligned (NaN without roots), Procrustes-aligned, and 0 or why the
+    item is left out (1: a non-finite coordinate, all three NaN; 2: the predicted points coincide, the Procrustes value NaN)."""
+    if pred.dim() != 3 or pred.shape[2] != 3 or pred.shape != gt.shape or pred.shape[1] < 1:
+        raise ValueError(f"points must be two (M, n, 3) tensors of one shape with n >= 1, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise TypeError(f"points must be float32, got {pred.dtype} and {gt.dtype}")
+    M, n = pred.shape[0], pred.shape[1]
+    if (pred_root is None) != (gt_root is None):
+        raise ValueError("roots: give both or neither")
+    if pred_root is not None:
+        for r in (pred_root, gt_root):
+            if tuple(r.shape) != (M, 3) or r.dtype != torch.float32:
+                raise ValueError(f"roots must be (M, 3) = {(M, 3)} float32, got {tuple(r.shape)} {r.dtype}")
+        pred_root, gt_root = pred_root.detach().contiguous(), gt_root.detach().contiguous()
+    out = torch.empty(M, 4, dtype=torch.float64, device=pred.device)
+    lib().mp_pose_errors(pred.detach().contiguous(), gt.detach().contiguous(), pred_root, gt_root, M, n, out, stream())
+    return out
+
+
+def contact_distance(verts, faces, corr, bary, frame_start):
+    """Contact distances on the bodies verts (F, P, V, 3) float32 (mp_contact_distance): faces (Nf, 3) int32; corr (m, 5) int32 =
+    frame, person a, vertex, person b, face of b, sorted by frame; bary (m, 3) float32; frame_start (F + 1,) int32.  Returns
+    (2 + 2 F,) float64 on the device = overall mean, m, the per-frame means (NaN for a frame without one), the per-frame counts."""
+    if verts.dim() != 4 or verts.shape[3] != 3 or min(verts.shape[:3]) < 1:
+        raise ValueError(f"verts must be (F, P, V, 3) with F, P, V >= 1, got {tuple(verts.shape)}")
+    F, P, V = verts.shape[0], verts.shape[1], verts.shape[2]
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces must be (Nf, 3) with Nf >= 1, got {tuple(faces.shape)}")
+    if corr.dim() != 2 or corr.shape[1] != 5:
+        raise ValueError(f"corr must be (m, 5), got {tuple(corr.shape)}")
+    m = corr.shape[0]
+    if tuple(bary.shape) != (m, 3):
+        raise ValueError(f"bary must be (m, 3) = {(m, 3)}, got {tuple(bary.shape)}")
+    if tuple(frame_start.shape) != (F + 1,):
+        raise ValueError(f"frame_start must be (F + 1,) = {(F + 1,)}, got {tuple(frame_start.shape)}")
+    if verts.dtype != torch.float32 or bary.dtype != torch.float32:
+        raise TypeError(f"verts and bary must be float32, got {verts.dtype} and {bary.dtype}")
+    if faces.dtype != torch.int32 or corr.dtype != torch.int32 or frame_start.dtype != torch.int32:
+        raise TypeError(f"faces, corr and frame_start must be int32, got {faces.dtype}, {corr.dtype} and {frame_start.dtype}")
+    out = torch.empty(2 + 2 * F, dtype=torch.float64, device=verts.device)
+    work = torch.empty(F, dtype=torch.float64, device=verts.device)
+    lib().mp_contact_distance(verts.detach().contiguous(), F, P, V, faces.contiguous(), faces.shape[0], corr.contiguous() if m else None,
+                              bary.contiguous() if m else None, frame_start.contiguous(), m, work, out, stream())
     return out

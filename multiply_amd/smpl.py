@@ -6,7 +6,8 @@ of the SMPL class it wraps (code/lib/smpl/body_models.py:60-365) for what the ho
 forward(scale, transl, thetas, betas, absolute=False) -> {'smpl_verts','smpl_tfs','smpl_jnts','smpl_all_jnts',
 'smpl_weights'}; the SMPL sub-module's parameters / buffers keep the reference's state-dict names.
 The arithmetic (blend shapes, Rodrigues, kinematic chain, LBS) and its adjoint (mp_smpl_pose, mp_smpl_verts_bwd,
-mp_smpl_pose_bwd_lbs) run in csrc/smpl.hip.
+mp_smpl_pose_bwd_lbs) run in csrc/smpl.hip.  Beyond the reference: pose_batch(params (N, 86)) poses N rows in two launches
+(mp_smpl_pose_batch, forward only) for callers that need many bodies at once (pose_metrics.pose_sequence).
 """
 import os
 import pickle
@@ -212,6 +213,45 @@ class SMPLServer(nn.Module):
         hip.lib().mp_smpl_pose(t.v_template, t.shapedirs, t.posedirs, t.j_regressor, t.lbs_weights, t.parents, params86,
                                None if absolute else self.tfs_c_inv, verts, tfs, joints, self._work if work is None else work,
                                hip.stream())
+
+    POSE_BATCH_OUTPUTS = ("verts", "joints", "tfs")
+
+    def pose_batch(self, params, absolute=False, want=POSE_BATCH_OUTPUTS, rows_per_call=None):
+        """N parameter rows at once (mp_smpl_pose_batch: two launches whatever N is, posedirs read once per call instead of once
+        per row).  params (N, 86) = [scale, transl 3, thetas 72, betas 10] per row -> a dict with the entries named in `want`:
+        verts (N, V, 3), joints (N, 24, 3), tfs (N, 24, 4, 4); the values per row are forward()'s (absolute as there), and a row
+        has the same bits alone and inside any batch.  rows_per_call bounds the rows of one kernel call (its work buffer is
+        hip.SMPL_BATCH_ROW_WORK floats per row; the outputs are allocated whole).  FORWARD ONLY: it runs under no_grad on
+        detached inputs and nothing it returns carries a gradient -- optimise poses through forward()."""
+        want = tuple(want)
+        bad = [w for w in want if w not in self.POSE_BATCH_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want: a non-empty subset of {self.POSE_BATCH_OUTPUTS}, got {want}")
+        if not torch.is_tensor(params) or params.dim() != 2 or params.shape[1] != 86:
+            raise ValueError(f"params: expected a (N, 86) tensor, got {tuple(params.shape) if torch.is_tensor(params) else type(params)}")
+        if rows_per_call is not None and int(rows_per_call) < 1:
+            raise ValueError(f"rows_per_call must be at least 1, got {rows_per_call}")
+        with torch.no_grad():
+            t, dev = self.tables, self.param_canonical.device
+            prm = params.detach().to(device=dev, dtype=torch.float32).contiguous()
+            N = prm.shape[0]
+            f32 = dict(dtype=torch.float32, device=dev)
+            out = {}
+            if "verts" in want:
+                out["verts"] = torch.empty(N, NUM_VERTS, 3, **f32)
+            if "joints" in want:
+                out["joints"] = torch.empty(N, NUM_JOINTS, 3, **f32)
+            if "tfs" in want:
+                out["tfs"] = torch.empty(N, NUM_JOINTS, 4, 4, **f32)
+            step = N if rows_per_call is None else int(rows_per_call)
+            work = torch.empty(max(min(step, N), 1) * hip.SMPL_BATCH_ROW_WORK, **f32)
+            for s in range(0, N, max(step, 1)):
+                e = min(N, s + step)
+                part = lambda k: out[k][s:e] if k in out else None
+                hip.lib().mp_smpl_pose_batch(t.v_template, t.shapedirs, t.posedirs, t.j_regressor, t.lbs_weights, t.parents,
+                                             prm[s:e], e - s, None if absolute else self.tfs_c_inv, part("verts"), part("tfs"),
+                                             part("joints"), work, hip.stream())
+        return out
 
     def pose_backward(self, params86, work=None, dverts=None, djoints=None, dall_joints=None, dtfs=None):
         """Adjoint of forward(absolute=False) -> d params (86,) = [scale, transl 3, thetas 72, betas 10].  Upstreams (any may
