@@ -395,7 +395,15 @@ int mp_gemm_tn_bf16x3(const float* A, int lda, const float* B, int ldb, float* C
                int colsum_rows, void* stream);
 /* Up to MP_TN_MAX_GROUPS such contractions in ONE launch (the weight gradients of all layers of a network): groups is a HOST
  * array; every group needs 16-byte aligned A, B, lda / ldb multiples of 4 and M, N multiples of 128.  Far fewer row slices per
- * output than one launch per contraction needs to fill the chip, hence far fewer fp32 atomics. */
+ * output than one launch per contraction needs to fill the chip, hence far fewer fp32 atomics.
+ * Status (the arguments are checked before anything is launched, so a non-zero argument status means NO group was computed):
+ *    0  launched (or n_groups <= 0: nothing to do);  > 0: the launch's hipError_t
+ *   -1  n_groups > MP_TN_MAX_GROUPS (the caller cuts its list: train.gemm_tn_grouped)
+ *   -2  a group the kernels do not take: M or N no positive multiple of 128, lda or ldb no multiple of 4, A or B not 16-byte
+ *       aligned, or an EMPTY contraction, K <= 0.  Unlike mp_gemm_tn[_bf16x3], which return 0 without a launch for K <= 0, an
+ *       empty group is refused and not skipped: every caller contracts over a person's sample rows plus its eikonal points or
+ *       over all background samples, never zero rows, so an empty record is a caller's bug and not a case to pass over.
+ * C, colsum and ldc carry no alignment requirement; two groups of one call may add into the same C. */
 #define MP_TN_MAX_GROUPS 24
 typedef struct {
     const float* A;
