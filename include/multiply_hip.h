@@ -377,7 +377,11 @@ int mp_composite_geometry(int n_rays, int n_person, int n_z, const int* const* i
  * the same computation as explicit forward / adjoint kernels; multiply_amd/train.py chains them inside one
  * torch.autograd.Function so that the reference's Loss and optimisers work unchanged.
  * Forward-mode row convention: a tensor of a network evaluated for P points with spatial tangents has 4P rows:
- * [0,P) values, [P,2P) d/dx, [2P,3P) d/dy, [3P,4P) d/dz.  "ld*" are row strides in floats. */
+ * [0,P) values, [P,2P) d/dx, [2P,3P) d/dy, [3P,4P) d/dz.  "ld*" are row strides in floats.
+ * Empty problems: every mp_tr_* entry point returns 0 and launches NOTHING (no pointer is read, all may be NULL) when its
+ * problem has no elements -- rows, n, P, E, n_pts, R, n_verts, out_dim or C <= 0, whichever it takes (for a product such as
+ * rows x C: either factor).  Three entry points still have an output with one factor empty and write it: mp_tr_colsum with
+ * rows <= 0 and mp_tr_bg_comp_fwd with NBG <= 0 store zeros, mp_tr_hoist_fwd with n <= 0 copies b. */
 /* C[M,N] (+)= A[M,K] . B[N,K]^T (+ bias[N] on rows < bias_rows) (optional ReLU); exact-fp32 MFMA */
 int mp_gemm_nt(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
                const float* bias, int bias_rows, int accumulate, int relu, void* stream);

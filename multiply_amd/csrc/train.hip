@@ -690,6 +690,7 @@ int mp_tr_pe(const float* x, int d_in, int P, int L, int fwd, float scale, float
 }
 int mp_tr_softplus_fwd(const float* Z, int ldz, int rows, int C, int P, float scale, float* H, int ldh, int col0,
                        void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     if (P <= 0 && mul4(C) && mul4(ldz) && mul4(ldh) && mul4(col0) && al16(Z) && al16(H) && fits32(rows, C))
         hipLaunchKernelGGL(k_softplus_fwd4, grid4(rows, C), dim3(TB), 0, ST, Z, ldz, (unsigned)rows, (unsigned)(C / 4), scale, H, ldh, col0);
     else
@@ -698,12 +699,14 @@ int mp_tr_softplus_fwd(const float* Z, int ldz, int rows, int C, int P, float sc
 }
 int mp_tr_softplus_bwd(const float* Z, int ldz, int rows, int C, int P, float scale, const float* dH, int ldh, int col0,
                        float* dZ, int lddz, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     const int vrows = P > 0 ? P : rows;
     hipLaunchKernelGGL(k_softplus_bwd, grid1((long long)vrows * C), dim3(TB), 0, ST, Z, ldz, rows, C, P, scale, dH, ldh, col0,
                        dZ, lddz);
     return (int)hipGetLastError();
 }
 int mp_tr_relu_bwd(const float* H, int ldh, int rows, int C, const float* dH, int lddh, float* dZ, int lddz, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     if (mul4(C) && mul4(ldh) && mul4(lddh) && mul4(lddz) && al16(H) && al16(dH) && al16(dZ) && fits32(rows, C))
         hipLaunchKernelGGL(k_relu_bwd4, grid4(rows, C), dim3(TB), 0, ST, H, ldh, (unsigned)rows, (unsigned)(C / 4), dH, lddh, dZ, lddz);
     else
@@ -735,19 +738,23 @@ int mp_tr_eik_bwd(int P, int e0, int E, const float* dgrad_theta, float* dZ8, fl
     return (int)hipGetLastError();
 }
 int mp_tr_sigmoid_fwd(const float* Z, long long n, float* Y, void* stream) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_sigmoid_fwd, grid1(n), dim3(TB), 0, ST, Z, n, Y);
     return (int)hipGetLastError();
 }
 int mp_tr_sigmoid_bwd(const float* Y, const float* dY, long long n, float* dZ, void* stream) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_sigmoid_bwd, grid1(n), dim3(TB), 0, ST, Y, dY, n, dZ);
     return (int)hipGetLastError();
 }
 int mp_tr_wn_fwd(const float* v, const float* g, int out_dim, int in_dim, float* W, float* WT, void* stream) {
+    if (out_dim <= 0) return 0;
     hipLaunchKernelGGL(k_wn_fwd, dim3(out_dim), dim3(64), 0, ST, v, g, out_dim, in_dim, W, WT);
     return (int)hipGetLastError();
 }
 int mp_tr_wn_bwd(const float* v, const float* g, int out_dim, int in_dim, const float* dW, float* dv, float* dg,
                  void* stream) {
+    if (out_dim <= 0) return 0;
     hipLaunchKernelGGL(k_wn_bwd, dim3(out_dim), dim3(64), 0, ST, v, g, out_dim, in_dim, dW, dv, dg);
     return (int)hipGetLastError();
 }
@@ -763,28 +770,34 @@ int mp_tr_wn_bwd_multi(const MpWnDesc* descs, int n_desc, int total_rows, const 
 }
 int mp_tr_hoist_fwd(const float* W, int out_dim, int in_dim, const float* b, int c0, int n, const float* vec, float* b2,
                     void* stream) {
+    if (out_dim <= 0) return 0;
     hipLaunchKernelGGL(k_hoist_fwd, dim3(out_dim), dim3(64), 0, ST, W, in_dim, b, c0, n, vec, b2);
     return (int)hipGetLastError();
 }
 int mp_tr_hoist_bwd(const float* db2, int out_dim, int in_dim, int c0, int n, const float* vec, float* dW, void* stream) {
+    if (out_dim <= 0 || n <= 0) return 0;
     hipLaunchKernelGGL(k_hoist_bwd, grid1((long long)out_dim * n), dim3(TB), 0, ST, db2, out_dim, in_dim, c0, n, vec, dW);
     return (int)hipGetLastError();
 }
 int mp_tr_colsum(const float* dZ, int ld, int rows, int C, float* db, void* stream) {
+    if (C <= 0) return 0;
     hipLaunchKernelGGL(k_colsum, dim3(C), dim3(256), 0, ST, dZ, ld, rows, C, db);
     return (int)hipGetLastError();
 }
 int mp_tr_bg_points(const float* dirs, const float* cam, const float* zbg, int R, int NBG, float radius, float* pts,
                     void* stream) {
+    if (R <= 0 || NBG <= 0) return 0;
     hipLaunchKernelGGL(k_bg_points, grid1((long long)R * NBG), dim3(TB), 0, ST, dirs, cam, zbg, R, NBG, radius, pts);
     return (int)hipGetLastError();
 }
 int mp_tr_bg_comp_fwd(const float* sdf, const float* rgb, const float* zbg, int R, int NBG, float* out, void* stream) {
+    if (R <= 0) return 0;
     hipLaunchKernelGGL(k_bg_comp_fwd, grid1(R), dim3(TB), 0, ST, sdf, rgb, zbg, R, NBG, out);
     return (int)hipGetLastError();
 }
 int mp_tr_bg_comp_bwd(const float* sdf, const float* rgb, const float* zbg, int R, int NBG, const float* dout, float* dsdf,
                       float* drgb, void* stream) {
+    if (R <= 0 || NBG <= 0) return 0;
     hipLaunchKernelGGL(k_bg_comp_bwd, grid1(R), dim3(TB), 0, ST, sdf, rgb, zbg, R, NBG, dout, dsdf, drgb);
     return (int)hipGetLastError();
 }
@@ -802,12 +815,13 @@ int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const f
     return (int)hipGetLastError();
 }
 int mp_tr_gather_bwd(const int* idx, int n, const float* jinv, const float* dxc, int n_verts, float* dverts, void* stream) {
-    if (n_verts <= 0) return 0;
+    if (n_verts <= 0 || n <= 0) return 0;   // no samples: dverts += 0
     hipLaunchKernelGGL(k_gather_bwd, grid1(n_verts), dim3(TB), 0, ST, idx, n, jinv, dxc, n_verts, dverts);
     return (int)hipGetLastError();
 }
 int mp_tr_sigmul(const float* Z, int ldz, long long rows, int C, const float* U, int ldu, const float* wrow, float scale,
                  float* V, int ldv, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     if (mul4(C) && mul4(ldz) && mul4(ldv) && (U ? mul4(ldu) && al16(U) : al16(wrow)) && al16(Z) && al16(V) && fits32(rows, C))
         hipLaunchKernelGGL(k_sigmul4, grid4(rows, C), dim3(TB), 0, ST, Z, ldz, (unsigned)rows, (unsigned)(C / 4), U, ldu, wrow, scale, V, ldv);
     else
@@ -816,6 +830,7 @@ int mp_tr_sigmul(const float* Z, int ldz, long long rows, int C, const float* U,
 }
 int mp_tr_rev_adj(const float* Z, int ldz, long long rows, int C, const float* U, int ldu, const float* wrow, float uscale,
                   const float* dV, int lddv, float* dU, int lddu, float* dS, int ldds, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     if (mul4(C) && mul4(ldz) && mul4(lddv) && mul4(lddu) && mul4(ldds) && (U ? mul4(ldu) && al16(U) : al16(wrow)) && al16(Z) &&
         al16(dV) && al16(dU) && al16(dS) && fits32(rows, C))
         hipLaunchKernelGGL(k_rev_adj4, grid4(rows, C), dim3(TB), 0, ST, Z, ldz, (unsigned)rows, (unsigned)(C / 4), U, ldu, wrow, uscale, dV,
@@ -827,6 +842,7 @@ int mp_tr_rev_adj(const float* Z, int ldz, long long rows, int C, const float* U
 }
 int mp_tr_dz(const float* Z, int ldz, long long rows, int C, const float* dX, int lddx, float scale, const float* dS, int ldds,
              float* dZ, int lddz, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     if (mul4(C) && mul4(ldz) && mul4(lddx) && mul4(ldds) && mul4(lddz) && al16(Z) && al16(dX) && al16(dS) && al16(dZ) && fits32(rows, C))
         hipLaunchKernelGGL(k_dz4, grid4(rows, C), dim3(TB), 0, ST, Z, ldz, (unsigned)rows, (unsigned)(C / 4), dX, lddx, scale, dS, ldds, dZ,
                            lddz);
@@ -847,6 +863,7 @@ int mp_tr_pe_grad_bwd(const float* x, int P, int L, const float* dgrad, const fl
 }
 int mp_tr_copy_cols(const float* src, int lds, int c0s, float* dst, int ldd, int c0d, long long rows, int C, float scale,
                     int accumulate, void* stream) {
+    if (rows <= 0 || C <= 0) return 0;
     hipLaunchKernelGGL(k_copy_cols, grid1(rows * C), dim3(TB), 0, ST, src, lds, c0s, dst, ldd, c0d, rows, C, scale, accumulate);
     return (int)hipGetLastError();
 }
