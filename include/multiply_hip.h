@@ -841,6 +841,48 @@ int mp_pose_errors(const float* pred, const float* gt, const float* pred_root, c
 int mp_contact_distance(const float* verts, int F, int P, int V, const int* faces, int n_faces, const int* corr, const float* bary,
                         const int* frame_start, int m, double* work, double* out, void* stream);
 
+/* ---- refining SMPL fits to 2D keypoints (multiply_amd/keypoint_fit.py, csrc/keypoint_fit.hip; the reference's `refine` mode,
+ * preprocessing/preprocessing_multiple_trace.py:360-527 with preprocessing/loss.py).  One row = one person in one frame; its free
+ * parameters are params [MP_KP_PARAMS] = transl 3, thetas 72, betas 10 (scale 1, absolute transforms).  One workgroup per row.
+ *   body      SMPL forward as in csrc/smpl.hip (Rodrigues with angle = |theta + 1e-8|, rest joints J = j_template + j_shapedirs betas,
+ *             the chain), and ONLY for the S support vertices v_posed = sv_template + s_shapedirs betas + s_posedirs^T pf, skinned
+ *             with s_weights, plus transl.  The "support pack" of table set t: j_template [24][3], j_shapedirs [24][3][10],
+ *             sv_template [S][3], s_shapedirs [S][3][10], s_posedirs [207][3S], s_weights [S][24]; n_tables sets lie one after the
+ *             other in each array and row_table [N] (NULL: all 0) names a row's set.  parents [24] is shared.
+ *   map       keypoint k = sum_m map_w[m] src[map_idx[m]], m in [map_ptr[k], map_ptr[k+1]), src = [24 posed joints ; S support
+ *             vertices]; tmap_* is the same matrix by source (tmap_ptr [24 + S + 1], tmap_k / tmap_w [nnz]): the adjoint gathers,
+ *             no atomics.  Caps: K <= MP_KP_MAX_K, S <= MP_KP_MAX_S (the row's state lives in 38 KB of LDS), 1 <= K, 0 <= S.
+ *   camera    [N][16] = fx, fy, cx, cy, E [3][4]:  x_c = E [x; 1], u = fx x_c / z_c + cx, v = fy y_c / z_c + cy.
+ *   loss      terms [3] = { L2d = sum_k c_k sum_{u,v} rho^2 r^2 / (r^2 + rho^2), r = target - projected;
+ *                           Lt  = w_p mean_{24x6}((rot6D - rot6D(prev thetas))^2) + mean_3((transl - prev transl)^2);
+ *                           w_2d L2d + w_t Lt }
+ *             targets [N][K][2], c [N][K] (the host folds confidence, joint weight and 1 / (2 K_set) into c), prev [N][75] = transl,
+ *             thetas of the temporal target, held constant (NULL: Lt = 0).  rot6D = the first two columns of a joint's rotation.
+ *             A keypoint with z_c <= 0 (or not a number) contributes nothing, its projection is written as 0, and flags [n] = 1.
+ *   mp_kp_objective : terms [N][3], grad [N][MP_KP_PARAMS] (of the weighted total), proj [N][K][2], flags [N] ints; terms, grad and
+ *                     proj may be NULL.
+ *   mp_kp_fit       : iters steps of torch.optim.Adam (bias correction, eps added to the denominator, lr_t / lr_p / lr_b for
+ *                     transl / thetas / betas) in ONE launch; parameters, moments and the chain never leave the chip.  out
+ *                     [N][MP_KP_PARAMS]; history [N][iters][3] (may be NULL) = the terms evaluated before each step; flags [N] = 1
+ *                     if any step met z_c <= 0.  iters = 0 copies params.
+ * fp32, fixed-order reductions: the same inputs give the same bits, and a row has the same bits alone and inside any batch.
+ * Status -1 without a launch: a NULL required pointer, N < 0, iters < 0, n_tables < 1; -2: K or S outside the caps.  N == 0: 0. */
+#define MP_KP_PARAMS 85
+#define MP_KP_MAX_K 64
+#define MP_KP_MAX_S 256
+int mp_kp_objective(const int* parents, const float* j_template, const float* j_shapedirs, const float* sv_template,
+                    const float* s_shapedirs, const float* s_posedirs, const float* s_weights, int n_tables, const int* row_table,
+                    const int* map_ptr, const int* map_idx, const float* map_w, const int* tmap_ptr, const int* tmap_k,
+                    const float* tmap_w, int S, int K, const float* params, const float* prev, const float* targets,
+                    const float* c, const float* camera, int N, float rho, float w_2d, float w_t, float w_p, float* terms,
+                    float* grad, float* proj, int* flags, void* stream);
+int mp_kp_fit(const int* parents, const float* j_template, const float* j_shapedirs, const float* sv_template,
+              const float* s_shapedirs, const float* s_posedirs, const float* s_weights, int n_tables, const int* row_table,
+              const int* map_ptr, const int* map_idx, const float* map_w, const int* tmap_ptr, const int* tmap_k,
+              const float* tmap_w, int S, int K, const float* params, const float* prev, const float* targets, const float* c,
+              const float* camera, int N, float rho, float w_2d, float w_t, float w_p, int iters, float lr_t, float lr_p,
+              float lr_b, float beta1, float beta2, float eps, float* out, float* history, int* flags, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/multiply_hip.h"
 #include "common.hpp"
+#include "smpl_chain.hpp"
 
 namespace {
 constexpr int V = MP_SMPL_V, NJ = MP_SMPL_J;
@@ -624,33 +625,13 @@ __global__ void k_smpl_pose_bwd(const int* __restrict__ parents, const float* __
                 dG[j][4 * a + 3] += scale * dj;
             }
     }
-    for (int j = NJ - 1; j >= 1; --j) {   // G_j = G_p [R_j | rel_j]
-        const int p = parents[j];
-        float rel[3];
-        for (int a = 0; a < 3; ++a) rel[a] = J[3 * j + a] - J[3 * p + a];
-        float drel[3] = {0.f, 0.f, 0.f};
-        for (int b = 0; b < 3; ++b)
-            for (int c2 = 0; c2 < 3; ++c2) {
-                float v = 0.f;
-                for (int a = 0; a < 3; ++a) v += G[p][4 * a + b] * dG[j][4 * a + c2];
-                dR[j][3 * b + c2] = v;
-            }
-        for (int b = 0; b < 3; ++b)
-            for (int a = 0; a < 3; ++a) drel[b] += G[p][4 * a + b] * dG[j][4 * a + 3];
-        for (int a = 0; a < 3; ++a) {
-            for (int b = 0; b < 3; ++b) {
-                float v = dG[j][4 * a + 3] * rel[b];
-                for (int c2 = 0; c2 < 3; ++c2) v += dG[j][4 * a + c2] * R[j][3 * b + c2];
-                dG[p][4 * a + b] += v;
-            }
-            dG[p][4 * a + 3] += dG[j][4 * a + 3];
-        }
-        for (int a = 0; a < 3; ++a) { dJ[j][a] += drel[a]; dJ[p][a] -= drel[a]; }
-    }
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 3; ++b) dR[0][3 * a + b] = dG[0][4 * a + b];
-        dJ[0][a] += dG[0][4 * a + 3];
-    }
+    // The recursion is smpl_chain.hpp's, shared with the keypoint fit (keypoint_fit.hip).  Rodrigues, the forward chain, the seed
+    // above and Rodrigues' adjoint below stay written out here although the header has them too: routed through the header's
+    // functions the compiler contracted their multiply-adds differently (other fma / mul / add counts in the kernel), and
+    // mp_smpl_pose_bwd* keeps its bits.
+    for (int j = NJ - 1; j >= 1; --j)     // G_j = G_p [R_j | rel_j]
+        mp::smpl_chain_joint_adjoint(j, parents[j], J, R, G, dG, dJ, dR);
+    mp::smpl_chain_root_adjoint(dG, dJ, dR);
     if (dpf)              // pose_feature = (R_j - I).flatten, j >= 1 (lbs.py:199)
         for (int j = 1; j < NJ; ++j)
             for (int e = 0; e < 9; ++e) dR[j][e] += dpf[9 * (j - 1) + e];
