@@ -883,6 +883,35 @@ int mp_kp_fit(const int* parents, const float* j_template, const float* j_shaped
               const float* camera, int N, float rho, float w_2d, float w_t, float w_p, int iters, float lr_t, float lr_p,
               float lr_b, float beta1, float beta2, float eps, float* out, float* history, int* flags, void* stream);
 
+/* ---- building a scene folder from refined fits (multiply_amd/scene_build.py, csrc/raster.hip + csrc/scene.hip; the reference's
+ * `final` mode, preprocessing/preprocessing_multiple_trace.py:529-599, which rasterises with pytorch3d and dilates with cv2 on the
+ * host, one body at a time).  Masks are [N][H][W] bytes.
+ *   mp_raster_mask_batch : coverage of N meshes verts [N][n_verts][3] that share faces [n_faces][3] and ONE camera (cam_host,
+ *                          z_clip, the pixel convention: mp_raster_zbuf's): mask[n][r][c] = 255 where mp_raster_zbuf of mesh n
+ *                          alone gives zbuf >= 0 (the same projection, box and coverage arithmetic), 0 elsewhere.  big
+ *                          [1 + N n_faces] ints is scratch.  Two launches whatever N is; a mesh's mask has the same bytes alone
+ *                          and at any position of any batch.  Status -1 without a launch: N, n_verts or n_faces < 0, H or W < 1,
+ *                          a NULL cam_host, with N > 0 a NULL mask / big (verts / faces with n_faces > 0), N n_faces >= 2^31 - 1;
+ *                          N == 0 returns 0 and touches nothing.
+ *   mp_mask_dilate       : out[n][r][c] = 255 if in[n][r + dr][c + dc] != 0 for some dr in [-ay, kh - 1 - ay], dc in [-ax, kw - 1 -
+ *                          ax] inside the image, else 0 (cv2.dilate with a kh x kw box of ones and anchor (ax, ay); its default
+ *                          anchor is (kw / 2, kh / 2)).  in and out must not overlap.  Status -2 without a launch: kh or kw outside
+ *                          1 .. MP_DILATE_MAX_K, ay outside [0, kh), ax outside [0, kw); -1: N < 0, H or W < 1, with N > 0 a NULL
+ *                          or aliased pointer, N > 65535; N == 0 returns 0.
+ *   mp_mask_stats        : stats [N][7] 64-bit integers of the nonzero pixels = { count, min row, max row, min col, max col,
+ *                          sum of rows, sum of cols }; an empty mask gives { 0, H, -1, W, -1, 0, 0 }.  Integer arithmetic: exact
+ *                          whatever the order.  Status -1 without a launch: N < 0, H or W < 1, with N > 0 a NULL pointer, N > 65535.
+ *   mp_verts_bounds      : verts [F][n][3].  shift == NULL: out [F][6] = min x, y, z, max x, y, z of frame f (the values of
+ *                          torch.amin / amax);  shift [F][3]: out [F] = max_i |v_i + shift_f| in fp32.  One workgroup per frame,
+ *                          no atomics.  Finite inputs.  Status -1 without a launch: F < 0, n < 1, with F > 0 a NULL verts / out;
+ *                          F == 0 returns 0. */
+#define MP_DILATE_MAX_K 64
+int mp_raster_mask_batch(const float* verts, int N, int n_verts, const int* faces, int n_faces, const float* cam_host, float z_clip,
+                         int H, int W, int* big, unsigned char* mask, void* stream);
+int mp_mask_dilate(const unsigned char* in, int N, int H, int W, int kh, int kw, int ay, int ax, unsigned char* out, void* stream);
+int mp_mask_stats(const unsigned char* mask, int N, int H, int W, long long* stats, void* stream);
+int mp_verts_bounds(const float* verts, int F, int n, const float* shift, float* out, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

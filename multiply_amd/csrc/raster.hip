@@ -352,6 +352,62 @@ __global__ __launch_bounds__(64) void k_soft_blend(const float* __restrict__ ver
     o[3] = (float)(1.0 - alpha);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Coverage only, for N meshes that share one face table and one camera (mp_raster_mask_batch; multiply_amd/scene_build.py):
+// mask[n][r][c] = 255 where mp_raster_zbuf of mesh n would leave zbuf >= 0 -- a pixel is covered there as soon as ONE face
+// passes load_tri, pixel_box and cover, so the same three functions decide here, and nothing else is kept: no depth, no
+// keys, no resolve.  All writers of a pixel store the same byte, so plain stores need no ordering.  One thread per (mesh,
+// face); a face whose box holds more than SMALL_BOX pixel centres goes to a queue of (mesh, face) items that a second
+// launch sweeps with one WAVE per item (lanes over the box's pixels): two launches whatever N is.
+__device__ __forceinline__ void mark(const Tri& t, int r, int c, int W, unsigned char* __restrict__ m) {
+    float b0, b1, b2, pz;
+    if (cover(t, c + 0.5f, r + 0.5f, b0, b1, b2, pz)) m[(size_t)r * W + c] = 255;
+}
+
+__global__ __launch_bounds__(256) void k_mask_faces(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces,
+                                                    int F, long long total, Cam cam, int H, int W,
+                                                    unsigned char* __restrict__ mask, int* __restrict__ big) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int n = (int)(i / F), f = (int)(i % F);
+    Tri t;
+    int c0, c1, r0, r1;
+    if (!load_tri(cam, verts + (size_t)n * n_verts * 3, faces, f, t) || !pixel_box(t, H, W, c0, c1, r0, r1)) return;
+    if ((c1 - c0 + 1) * (long long)(r1 - r0 + 1) > SMALL_BOX) {
+        big[1 + atomicAdd(big, 1)] = (int)i;
+        return;
+    }
+    unsigned char* m = mask + (size_t)n * H * W;
+    for (int r = r0; r <= r1; ++r)
+        for (int c = c0; c <= c1; ++c) mark(t, r, c, W, m);
+}
+
+__global__ __launch_bounds__(256) void k_mask_big(const float* __restrict__ verts, int n_verts, const int* __restrict__ faces, int F,
+                                                  Cam cam, int H, int W, unsigned char* __restrict__ mask,
+                                                  const int* __restrict__ big) {
+    const int count = big[0], lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), waves = gridDim.x * (blockDim.x >> 6);
+    for (int q = wave; q < count; q += waves) {
+        const int i = big[1 + q], n = i / F, f = i % F;
+        Tri t;
+        int c0, c1, r0, r1;
+        if (!load_tri(cam, verts + (size_t)n * n_verts * 3, faces, f, t) || !pixel_box(t, H, W, c0, c1, r0, r1)) continue;
+        unsigned char* m = mask + (size_t)n * H * W;
+        // lane l takes the box's pixels l, l + 64, ... in row-major order.  (row, column) are stepped, not divided out of the
+        // index: two integer divisions per ITEM instead of two 64-bit ones per pixel.  Both stay loop-carried -- with a row
+        // loop around a column loop the compiler hoists the row's products out of cover()'s edge functions and contracts the
+        // rest into other multiply-adds than mp_raster_zbuf's kernels, and pixels on an outline flip
+        const int bw = c1 - c0 + 1, dr = 64 / bw, dc = 64 % bw;
+        int r = r0 + lane / bw, c = c0 + lane % bw;
+        while (r <= r1) {
+            mark(t, r, c, W, m);
+            r += dr;
+            c += dc;
+            if (c > c1) { c -= bw; ++r; }
+        }
+    }
+}
+
 __host__ Cam cam_from_host(const float* cam_host, float z_clip) {
     Cam cam;
     for (int i = 0; i < 9; ++i) cam.R[i] = cam_host[i];
@@ -429,5 +485,27 @@ extern "C" int mp_raster_soft(const float* verts, int n_verts, const int* faces,
     // call's -- a first call with K = 10 (11 KB) would otherwise leave a later K = 100 call (80 KB) above the 64 KB default
     MP_LDS_ATTR(k_soft_blend, SOFT_MAX_K * 64 * 12 + 64 * (int)(sizeof(SoftTri) + sizeof(int)));
     hipLaunchKernelGGL(k_soft_blend, dim3(T), dim3(64), lds, st, verts, faces, colors, cam, H, W, sp, tx, offsets, list, image, sel);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_raster_mask_batch(const float* verts, int N, int n_verts, const int* faces, int n_faces, const float* cam_host,
+                                    float z_clip, int H, int W, int* big, unsigned char* mask, void* stream) {
+    if (N < 0 || H <= 0 || W <= 0 || n_verts < 0 || n_faces < 0 || !cam_host) return -1;
+    if (N == 0) return 0;
+    if (!mask || !big || (n_faces > 0 && (!verts || !faces))) return -1;
+    const long long total = (long long)N * n_faces;
+    if (total > 0x7fffffffLL - 1) return -1;            // a queue item is one int: call with fewer rows
+    hipStream_t st = (hipStream_t)stream;
+    const Cam cam = cam_from_host(cam_host, z_clip);
+    hipError_t e = hipMemsetAsync(mask, 0, (size_t)N * H * W, st);
+    if (e != hipSuccess) return (int)e;
+    if (total == 0) return 0;
+    e = hipMemsetAsync(big, 0, sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_mask_faces, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, verts, n_verts, faces, n_faces, total,
+                       cam, H, W, mask, big);
+    const long long items = (total + 3) / 4;             // four waves per workgroup
+    hipLaunchKernelGGL(k_mask_big, dim3((unsigned)(items < 4096 ? items : 4096)), dim3(256), 0, st, verts, n_verts, faces, n_faces,
+                       cam, H, W, mask, big);
     return (int)hipGetLastError();
 }
