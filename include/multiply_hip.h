@@ -912,6 +912,38 @@ int mp_mask_dilate(const unsigned char* in, int N, int H, int W, int kh, int kw,
 int mp_mask_stats(const unsigned char* mask, int N, int H, int W, long long* stats, void* stream);
 int mp_verts_bounds(const float* verts, int F, int n, const float* shift, float* out, void* stream);
 
+/* ---- the optimiser of the training loop (multiply_amd/trainer.py DeviceAdam, csrc/optim.hip; the reference steps two
+ * torch.optim.Adam objects from Lightning's loop, multiply_model.py:62-78, 212-225).
+ * mp_adam_multi: torch.optim.Adam's single-tensor step (no weight decay, no amsgrad) for every tensor of an optimiser in ONE
+ * launch.  descs = DEVICE array of n_desc records; the blocks (256 threads) of all tensors are concatenated in one grid: block0 =
+ * first block of a tensor (ascending from 0), n_block >= 1 its number of blocks, total_blocks = their sum; a tensor with more
+ * elements than its blocks cover in one pass is strided over.
+ *   p, m (exp_avg), v (exp_avg_sq) [n] are updated in place from g [n]:  m = fma(g - m, 1 - beta1, m);  v = fma(v, beta2,
+ *   ((1 - beta2) g) g);  p = fma(-lr[group] / (1 - beta1^t), m / (sqrt(v) / sqrt(1 - beta2^t) + eps), p)  with t = *step + 1 and
+ *   the two bias corrections computed in double, as torch's python scalars are.
+ *   step  : the tensor's own count, ONE device float (torch's state['step']).  The update kernel only reads the counts; a
+ *           trailing n_desc-thread launch on the same stream adds 1 to the count of every active tensor, so no block ever sees
+ *           t + 1 for t.  (No ping-pong buffers: the counts stay where the state dict has them.)
+ *   g == NULL : the record is inactive -- nothing of it is read or written and its count does not advance (torch: p.grad is None).
+ *   mode  : MP_ADAM_SCALAR = 4-byte accesses; MP_ADAM_VEC = 16-byte accesses between a scalar head and tail, valid when p, g, m, v
+ *           share their address modulo 16; MP_ADAM_VEC_G4 = the same with g read by dwords, valid when p, m, v share it (gradients
+ *           are views of a flat buffer at arbitrary float offsets).  The caller sets the mode from the addresses.
+ *   lr    : DEVICE floats, one per group;  skip : DEVICE byte or NULL: when *skip != 0 the launch changes nothing, no count advances.
+ * No allocation, no synchronisation.  Status -1 without a launch: n_desc or total_blocks < 0, with n_desc > 0 a NULL descs / lr;
+ * -2: beta1 / beta2 outside [0, 1) or eps < 0; n_desc == 0 or total_blocks == 0 returns 0 and touches nothing. */
+enum { MP_ADAM_SCALAR = 0, MP_ADAM_VEC = 1, MP_ADAM_VEC_G4 = 2 };
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* step;
+    long long n;
+    int group, block0, n_block, mode;
+} MpAdamDesc;
+int mp_adam_multi(const MpAdamDesc* descs, int n_desc, int total_blocks, const float* lr, const unsigned char* skip, double beta1,
+                  double beta2, double eps, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

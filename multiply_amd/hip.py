@@ -103,7 +103,7 @@ def header_prototypes(path=HEADER_PATH):
     with open(path) as f:
         txt = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
     txt = re.sub(r"//[^\n]*", " ", txt)
-    scal = {"int": C.c_int, "float": C.c_float, "long long": C.c_longlong, "unsigned": C.c_uint, "void": None}
+    scal = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "long long": C.c_longlong, "unsigned": C.c_uint, "void": None}
     protos = {}
     for ret, name, args in re.findall(r"\b(int|void|const char\s*\*)\s+(mp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", txt):
         at = []
