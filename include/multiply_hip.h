@@ -417,6 +417,22 @@ typedef struct {
     int lda, ldb, ldc, M, N, K, colsum_rows, pad_;
 } MpTnGroup;
 int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, void* stream);
+/* DETERMINISTIC forms of the three contractions (the training path's opt-in deterministic mode): the same kernels, but every row
+ * slice STORES its partial tile into a caller-provided workspace ws [slice][Mp][Np] (Mp, Np = M, N rounded up to 128; a grouped
+ * call: group after group) and its column sums into [slice][Mp] behind it; a finishing kernel then adds the slices of every element
+ * in ascending slice order and does one C += sum (colsum likewise).  No atomic anywhere: the result is a function of the operands
+ * and the shape alone.  The slice plan is the atomic forms' (shape and compile-time constants only).  Groups of one call that add
+ * into the same C (same pointer; M, N, ldc must then agree) or the same colsum are added in the order of the groups; C matrices that
+ * overlap in any other way are not supported.  The library allocates nothing: *bytes of the size queries (host pointers; bf16x3 != 0:
+ * the split-bf16 entry point's plan) is what ws must hold, 16-byte aligned; ws may be reused by the next call on the same stream.
+ * Status as above, and -3: ws is NULL, misaligned or smaller than the query's answer (nothing launched). */
+int mp_gemm_tn_ws_bytes(int M, int N, int K, int bf16x3, long long* bytes);
+int mp_gemm_tn_grouped_ws_bytes(const MpTnGroup* groups, int n_groups, long long* bytes);
+int mp_gemm_tn_det(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* colsum,
+               int colsum_rows, float* ws, long long ws_bytes, void* stream);
+int mp_gemm_tn_bf16x3_det(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* colsum,
+               int colsum_rows, float* ws, long long ws_bytes, void* stream);
+int mp_gemm_tn_bf16x3_grouped_det(const MpTnGroup* groups, int n_groups, float* ws, long long ws_bytes, void* stream);
 /* Fourier features (embedders.py) of x [P][d_in] (d_in 3|4, L octaves) times `scale` into out[.][ld] at col0; fwd != 0 also
  * writes the three (d_in = 3) tangent row blocks */
 int mp_tr_pe(const float* x, int d_in, int P, int L, int fwd, float scale, float* out, int ld, int col0, void* stream);
@@ -484,6 +500,18 @@ int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, const int* c
                                  const float* d_acc_solo /*[R][P]*/, const float* d_depth_solo /*[R][P]*/,
                                  const float* d_depth_solo_level /*[R][P]*/,
                                  float* const* d_sdf, float* d_beta, void* stream);
+/* DETERMINISTIC forms of the two adjoints: every ray's wave STORES its own d beta sum into d_beta_part [n_rays] (the caller's
+ * scratch) and a finishing kernel adds them in a fixed order (thread t of 256: rays t, t + 256, .. ascending; then the 256 sums
+ * ascending) into d_beta (+=).  Everything else as above (d sdf / d rgb never went through atomics).  -3: d_beta_part is NULL. */
+int mp_tr_composite_bwd_det(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                            const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
+                            const float* d_rgb_values, const float* d_acc, const float* d_acc_person, float* const* d_sdf,
+                            float* const* d_rgb, float* d_bg_rgb, float* d_beta, float* d_beta_part, void* stream);
+int mp_tr_composite_geometry_bwd_det(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                                     const float* const* sdf, const float* beta, float level, const float* d_depth,
+                                     const float* d_depth_person, const float* d_acc_solo, const float* d_depth_solo,
+                                     const float* d_depth_solo_level, float* const* d_sdf, float* d_beta, float* d_beta_part,
+                                     void* stream);
 /* background branch pieces (multiply.py:682-726) with per-ray depths zbg [R][NBG] */
 int mp_tr_bg_points(const float* dirs, const float* cam, const float* zbg, int R, int NBG, float radius, float* pts,
                     void* stream);
@@ -500,6 +528,12 @@ int mp_tr_bg_comp_bwd(const float* sdf, const float* rgb, const float* zbg, int 
 int mp_tr_pe_bwd(const float* x, int d_in, int P, int L, int fwd, const float* dIN, int ld, float* dx, void* stream);
 int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const float* djinv, const int* nn_posed,
                    const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, void* stream);
+/* DETERMINISTIC form: the points in fixed runs (a function of n), each entry of the 24 x 12 table accumulated by one thread over
+ * its run's points in ascending order, one partial table per run into part (floats: the size query's answer, a host pointer),
+ * then the tables added in ascending order into dtfs (+=).  -3: part is NULL. */
+int mp_tr_warp_bwd_part_floats(int n, long long* floats);
+int mp_tr_warp_bwd_det(const float* xc, const float* dxc, const float* jinv, const float* djinv, const int* nn_posed,
+                       const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, float* part, void* stream);
 int mp_smpl_pose_bwd(const int* parents, const float* params, const float* tfs_c_inv, const float* rest_joints,
                      const float* j_shapedirs, const float* dtfs, float* dparams, void* stream);
 /*   mp_smpl_pose_bwd_lbs: the same chain adjoint with every upstream of SMPLServer.forward: dtfs [24][16] (smpl_tfs),
@@ -594,6 +628,15 @@ int mp_tf_bg_pack(const float* const* W, const float* const* B, void* wpack, flo
 int mp_tf_bg_fwd(const void* wpack, const float* bias_all, float* arena, int P, float* feat, float* sdf, void* stream);
 int mp_tf_bg_bwd(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf, float* dw8,
                  float* db8, void* stream);
+/* DETERMINISTIC forms of the two backward launches (same stashes, same arithmetic): the last layer's 256 + 1 sums go through one
+ * LDS block per wave, added in wave order; every workgroup (= tile of 128 points) STORES its row of part, and finishing launches
+ * add the rows in ascending order (beyond 64 tiles: runs of 64 rows first, then the runs) into dw8 / db8 (+=).  part: the size
+ * query's floats (a host pointer) for the call's P.  -3: part is NULL. */
+int mp_tf_bwd_part_floats(int P, long long* floats);
+int mp_tf_sdf_bwd_det(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf, float* dw8,
+                      float* db8, float* part, void* stream);
+int mp_tf_bg_bwd_det(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf, float* dw8,
+                     float* db8, float* part, void* stream);
 
 /* The foreground RenderingNet ('pose_no_view', networks.py:263-312: 270 -> 4 x 256 ReLU -> 3, sigmoid) on the same skeleton:
  *   mp_tf_col_pack : W[5] (effective weights, layer 0 = [256][270]: columns 0..5 x_c / normal, 6..13 pose embedding, 14.. features),

@@ -195,6 +195,8 @@ __global__ __launch_bounds__(64 * WPB) void k_composite_geometry(int n_rays, int
 //     dw_j T_j exp(-fe_j)  -  sum_{i behind j} dw_i w_i  -  [j is not the very last sample] dT_bg T_bg
 // E and the sum behind are per-person prefix sums looked up at the ranks.  (The first version walked the merged list with one
 // THREAD per ray: 512 threads on the whole device, ~1 ms.)
+// DET (the deterministic form): d_beta is a buffer [n_rays] that receives every ray's own sum; k_beta_finish adds them in order.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_composite_bwd(
     int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
     const float* const* __restrict__ sdf, const float* const* __restrict__ rgb, const float* __restrict__ beta_p,
@@ -281,6 +283,10 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
         }
     }
     dbeta_local = mp::wsum(dbeta_local);
+    if constexpr (DET) {
+        if (lane == 0 && live) d_beta[r] = dbeta_local;
+        return;
+    }
     if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
 }
 
@@ -291,6 +297,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(
 //     dfe_j = dw_j e^-E e^-fe - sum_{behind j, merged} dw w  +  dws_j e^-Es e^-fe - sum_{i>j, own} dws w0  -  c [j < j*]  -  c f [j == j*]
 // (c = d level (te-ts)/fe of sample j*, f = (L-Es)/fe there; nothing where the forward clamps or finds no crossing) into d sdf and
 // d beta.  It ACCUMULATES (d_sdf +=: each element belongs to one lane), after k_composite_bwd's `=` on the same stream.
+template <bool DET = false>       // DET: as k_composite_bwd
 __global__ __launch_bounds__(256) void k_composite_geometry_bwd(
     int n_rays, int P, int n_z, const int* const* __restrict__ inv_index, const float* const* __restrict__ z,
     const float* const* __restrict__ sdf, const float* __restrict__ beta_p, float L, const float* __restrict__ d_depth,
@@ -398,7 +405,25 @@ __global__ __launch_bounds__(256) void k_composite_geometry_bwd(
         }
     }
     dbeta_local = mp::wsum(dbeta_local);
+    if constexpr (DET) {
+        if (lane == 0 && live) d_beta[r] = dbeta_local;
+        return;
+    }
     if (lane == 0 && dbeta_local != 0.0f) atomicAdd(d_beta, dbeta_local);
+}
+
+// *out += part[0] + part[1] + .. in a fixed order: thread t adds part[t], part[t + 256], .. ascending, thread 0 the 256 sums ascending
+__global__ __launch_bounds__(256) void k_beta_finish(const float* __restrict__ part, int n, float* __restrict__ out) {
+    __shared__ float red[256];
+    float v = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) v += part[i];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int i = 0; i < 256; ++i) t += red[i];
+        *out += t;
+    }
 }
 
 // Launch shape of the family for `per_person` floats of LDS per person and wave.  rc -1: n_person outside [0, MAX_P]; rc -2: the
@@ -455,8 +480,8 @@ extern "C" int mp_tr_composite_bwd(int n_rays, int n_person, int n_z, const int*
     if (sh.rc == -1) return -1;
     if (n_rays <= 0) return 0;
     if (sh.rc) return sh.rc;
-    MP_LDS_ATTR((k_composite_bwd), LDS_MAX);
-    hipLaunchKernelGGL(k_composite_bwd, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream, n_rays,
+    MP_LDS_ATTR((k_composite_bwd<>), LDS_MAX);
+    hipLaunchKernelGGL(k_composite_bwd<>, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream, n_rays,
                        n_person, n_z, inv_index, z, sdf, rgb, beta, bg_rgb, d_rgb_values, d_acc, d_acc_person, d_sdf, d_rgb,
                        d_bg_rgb, d_beta);
     return (int)hipGetLastError();
@@ -473,10 +498,50 @@ extern "C" int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, c
     if (n_rays <= 0) return 0;
     if (!d_depth && !d_depth_person && !d_acc_solo && !d_depth_solo && !d_depth_solo_level) return 0;
     if (sh.rc) return sh.rc;
-    MP_LDS_ATTR((k_composite_geometry_bwd), LDS_MAX);
+    MP_LDS_ATTR((k_composite_geometry_bwd<>), LDS_MAX);
     const float L = (float)-log1p(-(double)level);
-    hipLaunchKernelGGL(k_composite_geometry_bwd, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_composite_geometry_bwd<>, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream,
                        n_rays, n_person, n_z, inv_index, z, sdf, beta, L, d_depth, d_depth_person, d_acc_solo, d_depth_solo,
                        d_depth_solo_level, d_sdf, d_beta);
+    return (int)hipGetLastError();
+}
+
+// Deterministic forms: d_beta_part [n_rays] is the caller's scratch for the rays' own sums (written, never read back by the caller)
+extern "C" int mp_tr_composite_bwd_det(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
+                                       const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
+                                       const float* d_rgb_values, const float* d_acc, const float* d_acc_person,
+                                       float* const* d_sdf, float* const* d_rgb, float* d_bg_rgb, float* d_beta,
+                                       float* d_beta_part, void* stream) {
+    const LaunchShape sh = launch_shape(n_person, bwd_stride(n_z - 1), true);
+    if (sh.rc == -1) return -1;
+    if (n_rays <= 0) return 0;
+    if (sh.rc) return sh.rc;
+    if (d_beta_part == nullptr) return -3;
+    MP_LDS_ATTR((k_composite_bwd<true>), LDS_MAX);
+    hipLaunchKernelGGL(k_composite_bwd<true>, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds, (hipStream_t)stream,
+                       n_rays, n_person, n_z, inv_index, z, sdf, rgb, beta, bg_rgb, d_rgb_values, d_acc, d_acc_person, d_sdf, d_rgb,
+                       d_bg_rgb, d_beta_part);
+    hipLaunchKernelGGL(k_beta_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, d_beta_part, n_rays, d_beta);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mp_tr_composite_geometry_bwd_det(int n_rays, int n_person, int n_z, const int* const* inv_index,
+                                                const float* const* z, const float* const* sdf, const float* beta, float level,
+                                                const float* d_depth, const float* d_depth_person, const float* d_acc_solo,
+                                                const float* d_depth_solo, const float* d_depth_solo_level, float* const* d_sdf,
+                                                float* d_beta, float* d_beta_part, void* stream) {
+    const LaunchShape sh = launch_shape(n_person, geometry_bwd_stride(n_z - 1), true);
+    if (sh.rc == -1) return -1;
+    if (!(level > 0.f && level < 1.f)) return -3;
+    if (n_rays <= 0) return 0;
+    if (!d_depth && !d_depth_person && !d_acc_solo && !d_depth_solo && !d_depth_solo_level) return 0;
+    if (sh.rc) return sh.rc;
+    if (d_beta_part == nullptr) return -3;
+    MP_LDS_ATTR((k_composite_geometry_bwd<true>), LDS_MAX);
+    const float L = (float)-log1p(-(double)level);
+    hipLaunchKernelGGL(k_composite_geometry_bwd<true>, dim3((n_rays + sh.wpb - 1) / sh.wpb), dim3(64 * sh.wpb), sh.lds,
+                       (hipStream_t)stream, n_rays, n_person, n_z, inv_index, z, sdf, beta, L, d_depth, d_depth_person, d_acc_solo,
+                       d_depth_solo, d_depth_solo_level, d_sdf, d_beta_part);
+    hipLaunchKernelGGL(k_beta_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, d_beta_part, n_rays, d_beta);
     return (int)hipGetLastError();
 }

@@ -293,7 +293,9 @@ __global__ __launch_bounds__(NT_THREADS, 2) void k_gemm_nt_b3(const float* __res
 
 // C[M,N] += sum_r A[r,m] B[r,n]; block = 128x128 tile of C x one slice of the rows
 // FAST: aligned operands, M and N multiples of the tile: only the row-slice bound remains in the loop
-template <bool FAST>
+// DET (the deterministic form, mp_gemm_tn_det): C is the WORKSPACE [slice][Mp][Np] (Mp, Np = M, N rounded up to the tile) and
+// colsum its column-sum part [slice][Mp]: every slice STORES its whole partial tile, k_tn_finish adds the slices in order.
+template <bool FAST, bool DET = false>
 __global__ __launch_bounds__(NT_THREADS) void k_gemm_tn(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                  float* __restrict__ C, int ldc, int M, int N, int K, int rows_per_block,
                                                  float* __restrict__ colsum, int colsum_rows) {
@@ -371,9 +373,31 @@ __global__ __launch_bounds__(NT_THREADS) void k_gemm_tn(const float* __restrict_
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm + 4 * (dr + r) + i;
+                if constexpr (DET) continue;
                 if (m < M) atomicAdd(C + (size_t)m * ldc + n, acc[i][j][r]);
             }
         }
+    if constexpr (DET) {
+        const int Mp = gridDim.x * BM, Np = gridDim.y * BN;
+        float* W = C + (size_t)blockIdx.z * Mp * Np;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)          // columns 2 dc, 2 dc + 1 of one row: one 8-byte store
+                *(f32x2*)(W + (size_t)(m0 + wm + 4 * (dr + r) + i) * Np + n0 + wn + 2 * dc) = (f32x2){acc[i][0][r], acc[i][1][r]};
+        if (do_sum) {   // the 16 staging threads of a column group: one LDS slot each, added in the order of sr
+            __syncthreads();
+            float* red = smem;
+            *(f32x4*)&red[sr * BM + sc] = csum;
+            __syncthreads();
+            if (t < BM) {
+                float v = 0.f;
+                for (int q = 0; q < 16; ++q) v += red[q * BM + t];
+                colsum[(size_t)blockIdx.z * Mp + m0 + t] = v;
+            }
+        }
+        return;
+    }
     if (do_sum) {   // threads with the same sc hold partial sums of the same 4 columns: fold them through LDS
         __syncthreads();
         float* red = smem;
@@ -394,7 +418,9 @@ __global__ __launch_bounds__(NT_THREADS) void k_gemm_tn(const float* __restrict_
 // contiguous bytes (two b128 writes, conflict-free across the wave), and a lane's operand for a 32-row stage is the two row
 // blocks (2 kg, 2 kg + 1) of its column: two b64 reads, consecutive lanes on consecutive 8-byte slots (conflict-free).
 // (operand rows fetched PT = 2 stages ahead through a register ring, k loop unrolled by 2 -- what fits under 128 VGPRs; see k_gemm_nt_b3)
-template <bool FAST>
+// DET: C / ldc / colsum are this SLICE's part of the workspace (tile-padded, so stored without bounds): plain stores of the whole
+// tile, the column sums through one LDS slot per staging thread, added in the order of rb.
+template <bool FAST, bool DET = false>
 __device__ __forceinline__ void tn_b3_tile(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                            float* __restrict__ C, int ldc, int M, int N, int m0, int n0, int r_begin, int r_end,
                                            float* __restrict__ colsum, int colsum_rows, bool sum_tile) {
@@ -490,6 +516,27 @@ __device__ __forceinline__ void tn_b3_tile(const float* __restrict__ A, int lda,
     }
     // D: col = lane&15 (n), row = 4*(lane>>4)+reg (m)
     const int cn = lane & 15, cr = (lane >> 4) * 4;
+    if constexpr (DET) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    C[(size_t)(m0 + wm + 16 * i + cr + r) * ldc + n0 + wn + 16 * j + cn] = acc[i][j][r];
+        if (colsum != nullptr && sum_tile) {
+            __syncthreads();
+            float* red = smem;
+            if (!is_b) *(f32x4*)&red[rb * BM + 4 * mg] = csum;
+            __syncthreads();
+            if (t < BM) {
+                float v = 0.f;
+                for (int q = 0; q < BK / 4; ++q) v += red[q * BM + t];
+                colsum[m0 + t] = v;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -515,11 +562,18 @@ __device__ __forceinline__ void tn_b3_tile(const float* __restrict__ A, int lda,
     }
 }
 
-template <bool FAST>
+template <bool FAST, bool DET = false>
 __global__ __launch_bounds__(NT_THREADS, 2) void k_gemm_tn_b3(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                     float* __restrict__ C, int ldc, int M, int N, int K, int rows_per_block,
                                                     float* __restrict__ colsum, int colsum_rows) {
     const int r_begin = blockIdx.z * rows_per_block;
+    if constexpr (DET) {   // C = the workspace [slice][Mp][Np], colsum = its [slice][Mp] part (see k_gemm_tn)
+        const int Mp = gridDim.x * BM, Np = gridDim.y * BN;
+        tn_b3_tile<FAST, true>(A, lda, B, ldb, C + (size_t)blockIdx.z * Mp * Np, Np, M, N, blockIdx.x * BM, blockIdx.y * BN, r_begin,
+                               min(K, r_begin + rows_per_block), colsum ? colsum + (size_t)blockIdx.z * Mp : nullptr, colsum_rows,
+                               blockIdx.y == 0);
+        return;
+    }
     tn_b3_tile<FAST>(A, lda, B, ldb, C, ldc, M, N, blockIdx.x * BM, blockIdx.y * BN, r_begin, min(K, r_begin + rows_per_block), colsum,
                      colsum_rows, blockIdx.y == 0);
 }
@@ -539,6 +593,8 @@ struct TnGroups {
 // hence tile = (L / 8) % tiles, slice = L % 8 + 8 (L / (8 tiles)) -- and the second reader finds the rows in that XCD's L2.
 // With the (tile fastest, slice slowest) order of a plain 3-D grid the four tiles of a slice sit on four different XCDs and every
 // operand byte crosses the fabric twice: the kernel then runs at the memory system's rate on 2x its algorithmic bytes.
+// DET: every group's C / colsum are its part of the workspace, [slice of the group][M][N] and [slice of the group][M]
+template <bool DET = false>
 __global__ __launch_bounds__(NT_THREADS, 2) void k_gemm_tn_b3g(TnGroups T, int mt, int nt, int n_slice) {
     const int tiles = mt * nt, L = blockIdx.x;
     const int tile = (L >> 3) % tiles, slice = (L & 7) + 8 * (L / (8 * tiles));
@@ -552,6 +608,12 @@ __global__ __launch_bounds__(NT_THREADS, 2) void k_gemm_tn_b3g(TnGroups T, int m
     const int m0 = bx * BM, n0 = by * BN;
     if (m0 >= G.M || n0 >= G.N) return;
     const int r_begin = (slice - T.slice0[gi]) * T.rows_per_block;
+    if constexpr (DET) {
+        const size_t ls = slice - T.slice0[gi];
+        tn_b3_tile<true, true>(G.A, G.lda, G.B, G.ldb, G.C + ls * G.M * G.N, G.N, G.M, G.N, m0, n0, r_begin,
+                               min(G.K, r_begin + T.rows_per_block), G.colsum ? G.colsum + ls * G.M : nullptr, G.colsum_rows, by == 0);
+        return;
+    }
     tn_b3_tile<true>(G.A, G.lda, G.B, G.ldb, G.C, G.ldc, G.M, G.N, m0, n0, r_begin, min(G.K, r_begin + T.rows_per_block), G.colsum,
                      G.colsum_rows, by == 0);
 }
@@ -570,6 +632,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void k_gemm_tn_b3g(TnGroups T, int m
 constexpr int WT_ = 256;                                  // output tile (both ways)
 constexpr int WT_RB = WT_;                                // 8-byte slots between row blocks (padding them apart by 8 changed nothing)
 constexpr int LDS_B3W = 2 * 2 * 2 * (BK / 4) * WT_RB * 4 * 2;    // [stage][A | B][hi | lo][row block][column][4] bf16 = 128 KB
+template <bool DET = false>       // DET: as k_gemm_tn_b3g
 __global__ __launch_bounds__(NT_THREADS, 1) void k_gemm_tn_b3w(TnGroups T, int n_slice) {
     const int slice = blockIdx.x;
     if (slice >= n_slice) return;
@@ -690,6 +753,24 @@ __global__ __launch_bounds__(NT_THREADS, 1) void k_gemm_tn_b3w(TnGroups T, int n
         }
     }
     const int cn = lane & 15, cr = (lane >> 4) * 4;
+    if constexpr (DET) {
+        const size_t ls = slice - T.slice0[gi];
+        float* W = G.C + ls * WT_ * WT_;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) W[(size_t)(wm + 16 * i + cr + r) * WT_ + wn + 16 * j + cn] = acc[i][j][r];
+        if (colsum != nullptr) {   // one LDS slot per A-staging thread, added in the order of rb
+            __syncthreads();
+            float* red = smem;
+            if (!is_b) *(f32x4*)&red[rb * WT_ + 4 * mg] = csum;
+            __syncthreads();
+            if (t < WT_) colsum[ls * WT_ + t] = ((red[t] + red[WT_ + t]) + red[2 * WT_ + t]) + red[3 * WT_ + t];
+        }
+        return;
+    }
     float* Cm = G.C;
     const int ldc = G.ldc;
 #pragma unroll
@@ -712,6 +793,114 @@ __global__ __launch_bounds__(NT_THREADS, 1) void k_gemm_tn_b3w(TnGroups T, int n
         for (int i = t; i < WT_; i += NT_THREADS)
             if (red[i] != 0.f) atomicAdd(colsum + i, red[i]);
     }
+}
+
+// ---- the deterministic forms' finishing pass ------------------------------------------------------------------------------------
+// C[m][n] += sum over the row slices s = 0, 1, .. of W[s][m][n], one thread per 4 consecutive n of a row (16-byte reads, coalesced
+// along n; the slices of an element are added in ascending order into a register that starts at 0, then ONE C += sum), and the
+// same for colsum over [s][m].  Records whose C (colsum) is the same matrix -- the value sweep's and the gradient sweep's
+// contraction of one layer -- are CHAINED: the first record's threads add the later records' slices behind their own, in the
+// order of the records, so that no two threads ever touch one element.
+struct TnFinish {
+    struct Rec {
+        const float* ws;      // [S][Mp][Np]
+        const float* wsum;    // [S][Mp] (null: no colsum)
+        float* C;
+        float* colsum;
+        int M, N, ldc, Mp, Np, S, head_c, head_s;     // head_*: first record with the same C / colsum (own index: a head)
+    } g[MP_TN_MAX_GROUPS];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void k_tn_finish(TnFinish F) {
+    const int gi = blockIdx.y;
+    const TnFinish::Rec& G = F.g[gi];
+    const int q = blockIdx.x * 256 + threadIdx.x, npq = G.Np >> 2, nq = G.M * npq;
+    if (q < nq) {
+        if (G.head_c != gi) return;
+        const int m = q / npq, n4 = 4 * (q - m * npq);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        for (int j = gi; j < F.n; ++j) {
+            const TnFinish::Rec& H = F.g[j];
+            if (H.head_c != gi) continue;
+            const float* w = H.ws + (size_t)m * H.Np + n4;
+            const size_t st = (size_t)H.Mp * H.Np;
+            for (int s = 0; s < H.S; ++s) v += *(const f32x4*)(w + s * st);
+        }
+        float* c = G.C + (size_t)m * G.ldc + n4;
+        if (n4 + 3 < G.N && (G.ldc & 3) == 0 && ((size_t)G.C & 15) == 0) {
+            *(f32x4*)c = *(const f32x4*)c + v;
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (n4 + e < G.N) c[e] += v[e];
+        }
+        return;
+    }
+    const int m4 = 4 * (q - nq);
+    if (m4 >= G.M || G.colsum == nullptr || G.head_s != gi) return;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int j = gi; j < F.n; ++j) {
+        const TnFinish::Rec& H = F.g[j];
+        if (H.head_s != gi || H.wsum == nullptr) continue;
+        for (int s = 0; s < H.S; ++s) v += *(const f32x4*)(H.wsum + (size_t)s * H.Mp + m4);
+    }
+    for (int e = 0; e < 4; ++e)
+        if (m4 + e < G.M) G.colsum[m4 + e] += v[e];
+}
+
+// heads of the chains; -2: two records share C (colsum) with different shapes
+int tn_finish_chain(TnFinish& F) {
+    for (int i = 0; i < F.n; ++i) {
+        F.g[i].head_c = F.g[i].head_s = i;
+        for (int j = 0; j < i; ++j) {
+            if (F.g[j].C == F.g[i].C && F.g[i].head_c == i) {
+                if (F.g[j].M != F.g[i].M || F.g[j].N != F.g[i].N || F.g[j].ldc != F.g[i].ldc) return -2;
+                F.g[i].head_c = F.g[j].head_c;
+            }
+            if (F.g[i].colsum && F.g[j].colsum == F.g[i].colsum && F.g[i].head_s == i) {
+                if (F.g[j].M != F.g[i].M) return -2;
+                F.g[i].head_s = F.g[j].head_s;
+            }
+        }
+    }
+    return 0;
+}
+
+int tn_finish_launch(const TnFinish& F, hipStream_t stream) {
+    int most = 0;
+    for (int i = 0; i < F.n; ++i) {
+        const int q = F.g[i].M * (F.g[i].Np / 4) + F.g[i].Mp / 4;
+        most = q > most ? q : most;
+    }
+    hipLaunchKernelGGL(k_tn_finish, dim3((most + 255) / 256, F.n), dim3(256), 0, stream, F);
+    return (int)hipGetLastError();
+}
+
+#ifndef MP_TN_WGS       // workgroups the contraction is split into (tiles x row slices): every slice adds its 128 x 128 partial to C with
+#define MP_TN_WGS 512   // fp32 atomics, so fewer slices = fewer atomics but less of the chip busy
+#endif
+#ifndef MP_TNW_WGS
+#define MP_TNW_WGS 256    // workgroups of a wide launch: one per CU
+#endif
+#ifndef MP_TNG_WGS
+#define MP_TNG_WGS 1024   // workgroups of a grouped launch: 2 resident per CU, two rounds
+#endif
+
+// Slice plan of a single contraction: enough workgroups to fill 256 CUs twice, at least 4 stages (128 rows) each.  A function of the
+// shape and of compile-time constants only.
+int tn_single_plan(int M, int N, int K, int wgs, int* rows_out) {
+    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    int slices = (wgs + tiles - 1) / tiles;
+    int rows = (K + slices - 1) / slices;
+    rows = (rows + BK - 1) / BK * BK;
+    if (rows < 4 * BK) rows = 4 * BK;
+    *rows_out = rows;
+    return (K + rows - 1) / rows;
+}
+
+long long tn_single_ws_floats(int M, int N, int slices) {
+    const long long Mp = (M + BM - 1) / BM * BM, Np = (N + BN - 1) / BN * BN;
+    return (long long)slices * (Mp * Np + Mp);
 }
 
 }  // namespace
@@ -750,13 +939,8 @@ extern "C" int mp_gemm_nt_bf16x3(const float* A, int lda, const float* B, int ld
 extern "C" int mp_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
                           float* colsum, int colsum_rows, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    // slices of the contraction: enough workgroups to fill 256 CUs twice, at least 4 stages (128 rows) each
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    int slices = (512 + tiles - 1) / tiles;
-    int rows = (K + slices - 1) / slices;
-    rows = (rows + BK - 1) / BK * BK;
-    if (rows < 4 * BK) rows = 4 * BK;
-    slices = (K + rows - 1) / rows;
+    int rows;
+    const int slices = tn_single_plan(M, N, K, 512, &rows);
     constexpr int LDS_TN = 4 * BK * LDM * (int)sizeof(float);
     MP_LDS_ATTR((k_gemm_tn<true>), LDS_TN);
     MP_LDS_ATTR((k_gemm_tn<false>), LDS_TN);
@@ -774,15 +958,8 @@ extern "C" int mp_gemm_tn(const float* A, int lda, const float* B, int ldb, floa
 extern "C" int mp_gemm_tn_bf16x3(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
                                  float* colsum, int colsum_rows, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-#ifndef MP_TN_WGS       // workgroups the contraction is split into (tiles x row slices): every slice adds its 128 x 128 partial to C with
-#define MP_TN_WGS 512   // fp32 atomics, so fewer slices = fewer atomics but less of the chip busy
-#endif
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    int slices = (MP_TN_WGS + tiles - 1) / tiles;
-    int rows = (K + slices - 1) / slices;
-    rows = (rows + BK - 1) / BK * BK;
-    if (rows < 4 * BK) rows = 4 * BK;
-    slices = (K + rows - 1) / rows;
+    int rows;
+    const int slices = tn_single_plan(M, N, K, MP_TN_WGS, &rows);
     constexpr int LDS_B3 = 2 * 2 * 2 * (BK / 4) * BM * 4 * 2;   // 2 stages x (A, B) x (hi, lo) x [BK/4][128][4] bf16
     MP_LDS_ATTR((k_gemm_tn_b3<true>), LDS_B3);
     MP_LDS_ATTR((k_gemm_tn_b3<false>), LDS_B3);
@@ -797,7 +974,32 @@ extern "C" int mp_gemm_tn_bf16x3(const float* A, int lda, const float* B, int ld
     return (int)hipGetLastError();
 }
 
-extern "C" int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, void* stream) {
+namespace {
+enum { TN_ATOMIC = 0, TN_DET = 1, TN_QUERY = 2 };
+
+// TN_DET / TN_QUERY: group i's part of the workspace is [its slices][M][N] followed (with a colsum) by [its slices][M], the groups
+// one after another; TN_DET points T's C / colsum there, launches the <true> kernel and then the finishing pass on the real ones
+int tn_grouped_ws(const MpTnGroup* groups, TnGroups& T, int mode, float* ws, long long ws_bytes, long long* need, TnFinish& F) {
+    long long off = 0;
+    F.n = T.n;
+    for (int i = 0; i < T.n; ++i) {
+        const MpTnGroup& g = groups[i];
+        const long long S = T.slice0[i + 1] - T.slice0[i], c = S * g.M * g.N, s = g.colsum ? S * g.M : 0;
+        if (mode == TN_DET && 4 * (off + c + s) <= ws_bytes) {
+            T.g[i].C = ws + off;
+            T.g[i].colsum = g.colsum ? ws + off + c : nullptr;
+            F.g[i] = {ws + off, g.colsum ? ws + off + c : nullptr, g.C, g.colsum, g.M, g.N, g.ldc, g.M, g.N, (int)S, i, i};
+        }
+        off += c + s;
+    }
+    if (need) *need = 4 * off;
+    if (mode == TN_QUERY) return 0;
+    if (ws == nullptr || ((size_t)ws & 15) || 4 * off > ws_bytes) return -3;
+    return tn_finish_chain(F);
+}
+
+int tn_grouped(const MpTnGroup* groups, int n_groups, int mode, float* ws, long long ws_bytes, long long* need, void* stream) {
+    if (need) *need = 0;
     if (n_groups <= 0) return 0;
     if (n_groups > MP_TN_MAX_GROUPS) return -1;
     TnGroups T;
@@ -814,9 +1016,7 @@ extern "C" int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, 
         mt = g.M / BM > mt ? g.M / BM : mt;
         nt = g.N / BN > nt ? g.N / BN : nt;
     }
-#ifndef MP_TNW_WGS
-#define MP_TNW_WGS 256    // workgroups of a wide launch: one per CU
-#endif
+    TnFinish F;
     bool wide = true;
     for (int i = 0; i < n_groups; ++i) wide = wide && groups[i].M == WT_ && groups[i].N == WT_;
     if (wide) {
@@ -836,13 +1036,18 @@ extern "C" int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, 
             z += (int)((groups[i].K + rows - 1) / rows);
         }
         T.slice0[n_groups] = z;
-        MP_LDS_ATTR(k_gemm_tn_b3w, LDS_B3W);
-        hipLaunchKernelGGL(k_gemm_tn_b3w, dim3(z), dim3(NT_THREADS), LDS_B3W, (hipStream_t)stream, T, z);
+        if (mode != TN_ATOMIC) {
+            const int rc = tn_grouped_ws(groups, T, mode, ws, ws_bytes, need, F);
+            if (rc || mode == TN_QUERY) return rc;
+            MP_LDS_ATTR(k_gemm_tn_b3w<true>, LDS_B3W);
+            hipLaunchKernelGGL(k_gemm_tn_b3w<true>, dim3(z), dim3(NT_THREADS), LDS_B3W, (hipStream_t)stream, T, z);
+            const int e = (int)hipGetLastError();
+            return e ? e : tn_finish_launch(F, (hipStream_t)stream);
+        }
+        MP_LDS_ATTR(k_gemm_tn_b3w<>, LDS_B3W);
+        hipLaunchKernelGGL(k_gemm_tn_b3w<>, dim3(z), dim3(NT_THREADS), LDS_B3W, (hipStream_t)stream, T, z);
         return (int)hipGetLastError();
     }
-#ifndef MP_TNG_WGS
-#define MP_TNG_WGS 1024   // workgroups of a grouped launch: 2 resident per CU, two rounds
-#endif
     long long rows = (work + MP_TNG_WGS - 1) / MP_TNG_WGS;
     rows = (rows + BK - 1) / BK * BK;
     if (rows < 8 * BK) rows = 8 * BK;
@@ -860,8 +1065,76 @@ extern "C" int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, 
     }
     T.slice0[n_groups] = z;
     constexpr int LDS_B3 = 2 * 2 * 2 * (BK / 4) * BM * 4 * 2;
-    MP_LDS_ATTR(k_gemm_tn_b3g, LDS_B3);
     const int zpad = (z + 7) / 8 * 8;
-    hipLaunchKernelGGL(k_gemm_tn_b3g, dim3(mt * nt * zpad), dim3(NT_THREADS), LDS_B3, (hipStream_t)stream, T, mt, nt, z);
+    if (mode != TN_ATOMIC) {
+        const int rc = tn_grouped_ws(groups, T, mode, ws, ws_bytes, need, F);
+        if (rc || mode == TN_QUERY) return rc;
+        MP_LDS_ATTR(k_gemm_tn_b3g<true>, LDS_B3);
+        hipLaunchKernelGGL(k_gemm_tn_b3g<true>, dim3(mt * nt * zpad), dim3(NT_THREADS), LDS_B3, (hipStream_t)stream, T, mt, nt, z);
+        const int e = (int)hipGetLastError();
+        return e ? e : tn_finish_launch(F, (hipStream_t)stream);
+    }
+    MP_LDS_ATTR(k_gemm_tn_b3g<>, LDS_B3);
+    hipLaunchKernelGGL(k_gemm_tn_b3g<>, dim3(mt * nt * zpad), dim3(NT_THREADS), LDS_B3, (hipStream_t)stream, T, mt, nt, z);
     return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int mp_gemm_tn_bf16x3_grouped(const MpTnGroup* groups, int n_groups, void* stream) {
+    return tn_grouped(groups, n_groups, TN_ATOMIC, nullptr, 0, nullptr, stream);
+}
+
+// ---- deterministic forms: the same kernels' <DET> instantiations into a caller-provided workspace, then k_tn_finish ------------
+extern "C" int mp_gemm_tn_ws_bytes(int M, int N, int K, int bf16x3, long long* bytes) {
+    *bytes = 0;
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    int rows;
+    *bytes = 4 * tn_single_ws_floats(M, N, tn_single_plan(M, N, K, bf16x3 ? MP_TN_WGS : 512, &rows));
+    return 0;
+}
+
+extern "C" int mp_gemm_tn_grouped_ws_bytes(const MpTnGroup* groups, int n_groups, long long* bytes) {
+    return tn_grouped(groups, n_groups, TN_QUERY, nullptr, 0, bytes, nullptr);
+}
+
+namespace {
+int tn_single_det(bool b3, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* colsum,
+                  int colsum_rows, float* ws, long long ws_bytes, void* stream) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    int rows;
+    const int slices = tn_single_plan(M, N, K, b3 ? MP_TN_WGS : 512, &rows);
+    const int mt = (M + BM - 1) / BM, nt = (N + BN - 1) / BN;
+    if (ws == nullptr || ((size_t)ws & 15) || 4 * tn_single_ws_floats(M, N, slices) > ws_bytes) return -3;
+    float* wsum = ws + (size_t)slices * mt * BM * nt * BN;
+    const bool fast = (lda & 3) == 0 && (ldb & 3) == 0 && ((size_t)A & 15) == 0 && ((size_t)B & 15) == 0 && M % BM == 0 &&
+                      N % BN == 0;
+    const dim3 grid(mt, nt, slices);
+    constexpr int LDS_TN = 4 * BK * LDM * (int)sizeof(float);
+    constexpr int LDS_B3 = 2 * 2 * 2 * (BK / 4) * BM * 4 * 2;
+#define MP_TN_DET(KERNEL, LDS) do { MP_LDS_ATTR((KERNEL), LDS); hipLaunchKernelGGL((KERNEL), grid, dim3(NT_THREADS), LDS, \
+    (hipStream_t)stream, A, lda, B, ldb, ws, 0, M, N, K, rows, colsum ? wsum : nullptr, colsum_rows); } while (0)
+    if (b3) { if (fast) MP_TN_DET((k_gemm_tn_b3<true, true>), LDS_B3); else MP_TN_DET((k_gemm_tn_b3<false, true>), LDS_B3); }
+    else { if (fast) MP_TN_DET((k_gemm_tn<true, true>), LDS_TN); else MP_TN_DET((k_gemm_tn<false, true>), LDS_TN); }
+#undef MP_TN_DET
+    const int e = (int)hipGetLastError();
+    if (e) return e;
+    TnFinish F;
+    F.n = 1;
+    F.g[0] = {ws, colsum ? wsum : nullptr, C, colsum, M, N, ldc, mt * BM, nt * BN, slices, 0, 0};
+    return tn_finish_launch(F, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int mp_gemm_tn_det(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* colsum,
+                              int colsum_rows, float* ws, long long ws_bytes, void* stream) {
+    return tn_single_det(false, A, lda, B, ldb, C, ldc, M, N, K, colsum, colsum_rows, ws, ws_bytes, stream);
+}
+
+extern "C" int mp_gemm_tn_bf16x3_det(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
+                                     float* colsum, int colsum_rows, float* ws, long long ws_bytes, void* stream) {
+    return tn_single_det(true, A, lda, B, ldb, C, ldc, M, N, K, colsum, colsum_rows, ws, ws_bytes, stream);
+}
+
+extern "C" int mp_gemm_tn_bf16x3_grouped_det(const MpTnGroup* groups, int n_groups, float* ws, long long ws_bytes, void* stream) {
+    return tn_grouped(groups, n_groups, TN_DET, ws, ws_bytes, nullptr, stream);
 }

@@ -674,6 +674,8 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_val(TfValArgs a) {
 
 // ================================================================================================================ backward
 // sum over the 16 points of a wave (lanes j = 0..15 of each group g) of 8 per-lane values -> LDS column sums
+// DET: cx.redf is THIS WAVE's own [256] block and the slot is this lane's alone: a plain add, in program order
+template <bool DET = false>
 __device__ __forceinline__ void col_reduce(const Ctx& cx, int c, float (&r)[8]) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -685,12 +687,19 @@ __device__ __forceinline__ void col_reduce(const Ctx& cx, int c, float (&r)[8]) 
         r[e] = v;
     }
     if (cx.j == 0) {
+        if constexpr (DET) {
+            float* p = cx.redf + 32 * c + 4 * cx.g;
+            *(f32x4*)p = *(const f32x4*)p + (f32x4){r[0], r[1], r[2], r[3]};
+            *(f32x4*)(p + 16) = *(const f32x4*)(p + 16) + (f32x4){r[4], r[5], r[6], r[7]};
+            return;
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) atomicAdd(cx.redf + 32 * c + (e < 4 ? 4 * cx.g + e : 16 + 4 * cx.g + e - 4), r[e]);
     }
 }
 
 // ascending sweep: dV_l arrives in the accumulators;  dU = s (.) dV,  dS = s'' (.) U (.) dV,  dT_{l+1} = scale * dU
+template <bool DET = false>
 struct EpiC {
     // The next layer's operand (dT_{l+1}) is NOT kept in registers while this layer runs: it is re-read from the rows this wave
     // has just stored for the weight-gradient contraction (its own stores: in order, L2-resident).  This sweep prefetches four
@@ -753,7 +762,7 @@ struct EpiC {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) du[e] = 0.0f;
             }
-            col_reduce(cx, c, du);
+            col_reduce<DET>(cx, c, du);
             return;
         }
         {
@@ -765,6 +774,7 @@ struct EpiC {
 };
 
 // descending sweep: dX_l arrives in the accumulators;  dZ_{l-1} = s_{l-1} (.) dX_l + dS_{l-1}
+template <bool DET = false>
 struct EpiD {
     static constexpr bool NEXT_FROM_MEM = true;      // see EpiC: the next operand dZ_{l-1} is re-read from the rows just stored
     __device__ __forceinline__ void load_next(const Ctx& cx, BReg& B) {
@@ -819,25 +829,79 @@ struct EpiD {
             float r[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) r[e] = cx.valid ? dsdf * px[e >> 2][e & 3] : 0.0f;
-            col_reduce(cx, c, r);
+            col_reduce<DET>(cx, c, r);
         }
     }
 };
 
+// DETERMINISTIC form of the two backward kernels' last-layer sums (k_tf_sdf_bwd<true>, k_tf_bg_bwd<true>): no atomics.
+// Where the slots come from: the kernels' LDS is ring 3 x 40 KiB + input blocks 8 x 4 KiB = 152 KiB, and the [257] sums take
+// 1088 bytes behind them; the CU has 160 KiB, of which ONE workgroup is resident either way (8 waves = 2 per SIMD, as the
+// default instantiation: the occupancy is set by the LDS, and 160 KiB <= 160 KiB still fits one workgroup).  The remaining 8 KiB are
+// exactly one [256] block per wave (LDS_BYTES_DET = 160 KiB): a wave's column sums go to ITS block with plain adds (a slot
+// belongs to one lane: the gradient sweep's add at layer 7, then the value sweep's at layer 8, in program order).  The wave's d sdf
+// sum (the 257th value) stays in a register.  After the tile's last barrier thread c adds the eight blocks of column c in wave
+// order, the eight d sdf sums go through the (then free) first block, and the workgroup STORES its row [260] of `part` (a.dw8; a
+// workgroup runs exactly one tile: the grid is the number of tiles).  k_tf_rows_sum adds the rows in ascending order.
+constexpr int LDS_BYTES_DET = RING * CH_BYTES + TF_WAVES * BIN_BYTES + TF_WAVES * 256 * 4;
+constexpr int TF_PART_LD = 260;
+static_assert(LDS_BYTES_DET <= 160 * 1024, "the per-wave blocks must fit the CU's LDS");
+
+__device__ __forceinline__ void det_begin(Ctx& cx) {
+    float* base = cx.redf;
+    for (int i = threadIdx.x; i < TF_WAVES * 256; i += TF_THREADS) base[i] = 0.0f;
+    cx.redf = base + 256 * cx.wave;
+}
+// after the tile's last barrier: the workgroup's row of the partial sums
+__device__ __forceinline__ void det_end(const Ctx& cx, float db_wave, float* __restrict__ part) {
+    float* base = cx.redf - 256 * cx.wave;
+    float* row = part + (size_t)blockIdx.x * TF_PART_LD;
+    float v = 0.0f;
+    if (threadIdx.x < 256) {
+#pragma unroll
+        for (int w = 0; w < TF_WAVES; ++w) v += base[256 * w + threadIdx.x];
+        row[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if (cx.lane == 0) base[cx.wave] = db_wave;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < TF_WAVES; ++w) t += base[w];
+        row[256] = t;
+    }
+}
+
+// dst (+)= the sum of rows [b run, min(n_rows, (b + 1) run)) of src [n_rows][260], ascending, for block b: dst_w [.][ld] takes the
+// 256 column sums, dst_b [.][ld] the 257th
+__global__ __launch_bounds__(320) void k_tf_rows_sum(const float* __restrict__ src, int n_rows, int run, float* __restrict__ dst_w,
+                                                     float* __restrict__ dst_b, int ld, int accumulate) {
+    const int c = threadIdx.x;
+    if (c > 256) return;
+    const int r0 = blockIdx.x * run, r1 = min(n_rows, r0 + run);
+    float v = 0.0f;
+    for (int r = r0; r < r1; ++r) v += src[(size_t)r * TF_PART_LD + c];
+    float* d = c < 256 ? dst_w + (size_t)blockIdx.x * ld + c : dst_b + (size_t)blockIdx.x * ld;
+    *d = accumulate ? *d + v : v;
+}
+
+template <bool DET = false>
 __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_bwd(TfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx cx;
     ctx_setup(cx, smem, a.wpack, a.P, BWD_CHUNKS, 64, BWD_SHIFT, a.arena + 46 * (size_t)(a.P + 1) * HID + 117 * (size_t)a.P);
     const size_t R1 = (size_t)(a.P + 1) * HID;
     build_bin(cx, a.arena + off_dG(R1, a.P));
-    if (threadIdx.x < 257) cx.redf[threadIdx.x] = 0.0f;
+    if constexpr (DET) det_begin(cx);
+    else if (threadIdx.x < 257) cx.redf[threadIdx.x] = 0.0f;
     tf_prologue(cx);
     BReg Bcur, Bnext;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { Bcur.h[k] = Bcur.l[k] = Bnext.h[k] = Bnext.l[k] = zero_frag(); }
     // ---- ascending: the adjoint of the gradient sweep
     for (int l = 0; l <= 7; ++l) {
-        EpiC ep;
+        EpiC<DET> ep;
         ep.xin = a.arena + off_X(R1, l + 1);
         ep.kx = l == 3 ? K2 / R2 : K2;
         ep.top = l == 7;
@@ -845,7 +909,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_bwd(TfArgs a) {
         ep.dtout = a.arena + off_dT(R1, l < 7 ? l + 1 : 7);
         ep.dsout = a.arena + off_dS(R1, l);
         ep.osc = l == 3 ? R2 : 1.0f;
-        tf_layer<EpiC, 8, true>(cx, ep, 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
+        tf_layer<EpiC<DET>, 8, true>(cx, ep, 8, l > 0, l == 0 || l == 4, Bcur, Bnext);
     }
     // ---- descending: the adjoint of the value sweep, from dZ_8 [P][257] = (d sdf | d features)
     const float dsdf = a.dsdf[cx.prow];
@@ -855,16 +919,18 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_bwd(TfArgs a) {
         const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
         split8(v, Bcur.h[ks], Bcur.l[ks]);
     }
+    float db_wave = 0.0f;
     {   // the last layer's sdf bias gradient: sum over the workgroup's points of d sdf
         float t = (cx.valid && cx.g == 0) ? dsdf : 0.0f;
         t += __shfl_xor(t, 1);
         t += __shfl_xor(t, 2);
         t += __shfl_xor(t, 4);
         t += __shfl_xor(t, 8);
-        if (cx.lane == 0) atomicAdd(cx.redf + 256, t);
+        if constexpr (DET) db_wave = t;
+        else if (cx.lane == 0) atomicAdd(cx.redf + 256, t);
     }
     for (int l = 8; l >= 1; --l) {
-        EpiD ep;
+        EpiD<DET> ep;
         ep.xin = a.arena + off_X(R1, l);
         ep.kx = l == 4 ? K2 / R2 : K2;
         ep.dsin = a.arena + off_dS(R1, l - 1);
@@ -872,9 +938,13 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_sdf_bwd(TfArgs a) {
         ep.first = l == 8;
         ep.w8 = a.w8;
         ep.dsdf = dsdf;
-        tf_layer<EpiD, 8, false>(cx, ep, 8, true, false, Bcur, Bnext);
+        tf_layer<EpiD<DET>, 8, false>(cx, ep, 8, true, false, Bcur, Bnext);
     }
     __syncthreads();
+    if constexpr (DET) {
+        det_end(cx, db_wave, a.dw8);
+        return;
+    }
     if (threadIdx.x < 256) atomicAdd(a.dw8 + threadIdx.x, cx.redf[threadIdx.x]);
     if (threadIdx.x == 256) atomicAdd(a.db8, cx.redf[256]);
 }
@@ -1058,13 +1128,15 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_bg_fwd(TfArgs a) {
     }
 }
 
+template <bool DET = false>       // DET: see k_tf_sdf_bwd
 __global__ __launch_bounds__(TF_THREADS) void k_tf_bg_bwd(TfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Ctx cx;
     const size_t R1 = (size_t)(a.P + 1) * HID;
     ctx_setup(cx, smem, a.wpack, a.P, 64, 0, BG_FWD, nullptr);       // stream position k = chunk 73 + k
     bg_ctx(cx);
-    if (threadIdx.x < 257) cx.redf[threadIdx.x] = 0.0f;
+    if constexpr (DET) det_begin(cx);
+    else if (threadIdx.x < 257) cx.redf[threadIdx.x] = 0.0f;
     tf_prologue(cx);
     BReg Bcur, Bnext;
 #pragma unroll
@@ -1076,16 +1148,18 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_bg_bwd(TfArgs a) {
         const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
         split8(v, Bcur.h[ks], Bcur.l[ks]);
     }
+    float db_wave = 0.0f;
     {   // the last layer's sdf bias gradient: sum over the workgroup's points of d sdf
         float t = (cx.valid && cx.g == 0) ? dsdf : 0.0f;
         t += __shfl_xor(t, 1);
         t += __shfl_xor(t, 2);
         t += __shfl_xor(t, 4);
         t += __shfl_xor(t, 8);
-        if (cx.lane == 0) atomicAdd(cx.redf + 256, t);
+        if constexpr (DET) db_wave = t;
+        else if (cx.lane == 0) atomicAdd(cx.redf + 256, t);
     }
     for (int l = 8; l >= 1; --l) {
-        EpiD ep;
+        EpiD<DET> ep;
         ep.xin = a.arena + bgoff_X(R1, l);
         ep.kx = l == 4 ? K2 / R2 : K2;
         ep.dsin = nullptr;
@@ -1093,9 +1167,13 @@ __global__ __launch_bounds__(TF_THREADS) void k_tf_bg_bwd(TfArgs a) {
         ep.first = l == 8;
         ep.w8 = a.w8;
         ep.dsdf = dsdf;
-        tf_layer<EpiD, 8, false>(cx, ep, 8, true, false, Bcur, Bnext);
+        tf_layer<EpiD<DET>, 8, false>(cx, ep, 8, true, false, Bcur, Bnext);
     }
     __syncthreads();
+    if constexpr (DET) {
+        det_end(cx, db_wave, a.dw8);
+        return;
+    }
     if (threadIdx.x < 256) atomicAdd(a.dw8 + threadIdx.x, cx.redf[threadIdx.x]);
     if (threadIdx.x == 256) atomicAdd(a.db8, cx.redf[256]);
 }
@@ -1344,9 +1422,9 @@ extern "C" int mp_tf_sdf_val(const void* wpack, const float* bias_all, const flo
 extern "C" int mp_tf_sdf_bwd(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf,
                              float* dw8, float* db8, void* stream) {
     if (P <= 0) return 0;
-    MP_LDS_ATTR(k_tf_sdf_bwd, LDS_BYTES);
+    MP_LDS_ATTR(k_tf_sdf_bwd<>, LDS_BYTES);
     TfArgs a{(const char*)wpack, nullptr, w8, arena, nullptr, nullptr, dfeat, dsdf, dw8, db8, P};
-    hipLaunchKernelGGL(k_tf_sdf_bwd, dim3((P + TF_PTS - 1) / TF_PTS), dim3(TF_THREADS), LDS_BYTES, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_tf_sdf_bwd<>, dim3((P + TF_PTS - 1) / TF_PTS), dim3(TF_THREADS), LDS_BYTES, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -1383,10 +1461,56 @@ extern "C" int mp_tf_bg_fwd(const void* wpack, const float* bias_all, float* are
 extern "C" int mp_tf_bg_bwd(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf,
                             float* dw8, float* db8, void* stream) {
     if (P <= 0) return 0;
-    MP_LDS_ATTR(k_tf_bg_bwd, LDS_BYTES);
+    MP_LDS_ATTR(k_tf_bg_bwd<>, LDS_BYTES);
     TfArgs a{(const char*)wpack, nullptr, w8, arena, nullptr, nullptr, dfeat, dsdf, dw8, db8, P};
-    hipLaunchKernelGGL(k_tf_bg_bwd, dim3((P + TF_PTS - 1) / TF_PTS), dim3(TF_THREADS), LDS_BYTES, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_tf_bg_bwd<>, dim3((P + TF_PTS - 1) / TF_PTS), dim3(TF_THREADS), LDS_BYTES, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+// ---- deterministic forms of the two backward launches: the workgroups' rows into `part`, then the rows added in ascending order
+// (more than TF_FIN_RUN rows: in runs of TF_FIN_RUN first, into the rows behind them, then the runs' sums)
+namespace {
+constexpr int TF_FIN_RUN = 64;
+template <typename K>
+int tf_bwd_det(K kernel, const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf, float* dw8,
+               float* db8, float* part, hipStream_t stream) {
+    const int tiles = (P + TF_PTS - 1) / TF_PTS;
+    TfArgs a{(const char*)wpack, nullptr, w8, arena, nullptr, nullptr, dfeat, dsdf, part, nullptr, P};
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(TF_THREADS), LDS_BYTES_DET, stream, a);
+    const float* src = part;
+    int rows = tiles;
+    if (rows > TF_FIN_RUN) {
+        float* runs = part + (size_t)tiles * TF_PART_LD;
+        const int n_runs = (rows + TF_FIN_RUN - 1) / TF_FIN_RUN;
+        hipLaunchKernelGGL(k_tf_rows_sum, dim3(n_runs), dim3(320), 0, stream, src, rows, TF_FIN_RUN, runs, runs + 256, TF_PART_LD, 0);
+        src = runs;
+        rows = n_runs;
+    }
+    hipLaunchKernelGGL(k_tf_rows_sum, dim3(1), dim3(320), 0, stream, src, rows, rows, dw8, db8, 0, 1);
+    return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int mp_tf_bwd_part_floats(int P, long long* floats) {
+    const long long tiles = P <= 0 ? 0 : (P + TF_PTS - 1) / TF_PTS;
+    *floats = (tiles + (tiles + TF_FIN_RUN - 1) / TF_FIN_RUN) * TF_PART_LD;
+    return 0;
+}
+
+extern "C" int mp_tf_sdf_bwd_det(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf,
+                                 float* dw8, float* db8, float* part, void* stream) {
+    if (P <= 0) return 0;
+    if (part == nullptr) return -3;
+    MP_LDS_ATTR(k_tf_sdf_bwd<true>, LDS_BYTES_DET);
+    return tf_bwd_det(k_tf_sdf_bwd<true>, wpack, w8, arena, P, dfeat, dsdf, dw8, db8, part, (hipStream_t)stream);
+}
+
+extern "C" int mp_tf_bg_bwd_det(const void* wpack, const float* w8, float* arena, int P, const float* dfeat, const float* dsdf,
+                                float* dw8, float* db8, float* part, void* stream) {
+    if (P <= 0) return 0;
+    if (part == nullptr) return -3;
+    MP_LDS_ATTR(k_tf_bg_bwd<true>, LDS_BYTES_DET);
+    return tf_bwd_det(k_tf_bg_bwd<true>, wpack, w8, arena, P, dfeat, dsdf, dw8, db8, part, (hipStream_t)stream);
 }
 
 extern "C" int mp_tf_col_sizes(int n, long long* stash_floats, long long* pack_bytes) {

@@ -499,6 +499,119 @@ __global__ __launch_bounds__(256) void k_warp_bwd(const float* __restrict__ xc, 
         if (acc[e] != 0.f) atomicAdd(&dtfs[16 * (e / 12) + (e % 12)], acc[e]);
 }
 
+// DETERMINISTIC form of k_warp_bwd (mp_tr_warp_bwd_det): no atomics.  The points are cut into fixed runs of `per_wg` (a multiple
+// of 256; a function of n alone), one workgroup per run.  A workgroup walks its run 256 points at a time: every thread derives
+// its point's dT (12) and dRc (9), then the four waves take turns to stage theirs and the two weight rows (24 + 24) in LDS,
+// 64 points at a time, and thread e (and e + 256 for e < 32) adds w_j dT_k + wc_j dRc_k of the 64 staged points to ITS entry
+// (j, k) = (e / 12, e % 12) of the 24 x 12 table, points ascending.  One partial table per workgroup, k_warp_bwd_finish adds
+// them in ascending order.  LDS: 64 x 69 + 384 floats = 19 KiB.
+constexpr int WB_SUB = 64, WB_MAX_WGS = 512;
+__global__ __launch_bounds__(256) void k_warp_bwd_det(const float* __restrict__ xc, const float* __restrict__ dxc,
+                                                      const float* __restrict__ jinv, const float* __restrict__ djinv,
+                                                      const int* __restrict__ nn_posed, const int* __restrict__ nn_cano, int n,
+                                                      int per_wg, const float* __restrict__ skin_w, const float* __restrict__ tfs,
+                                                      float* __restrict__ part) {
+    constexpr int NJ = 24;
+    __shared__ float tl[NJ * 16];
+    __shared__ float sw[WB_SUB][NJ], swc[WB_SUB][NJ], sdT[WB_SUB][12], sdR[WB_SUB][9];
+    const int t = threadIdx.x;
+    for (int i = t; i < NJ * 16; i += 256) tl[i] = tfs[i];
+    __syncthreads();
+    const bool second = t < NJ * 12 - 256;
+    const int j0 = t / 12, k0 = t % 12, j1 = (t + 256) / 12, k1 = (t + 256) % 12;
+    const int r0 = (k0 & 3) < 3 ? 3 * (k0 >> 2) + (k0 & 3) : -1, r1 = (k1 & 3) < 3 ? 3 * (k1 >> 2) + (k1 & 3) : -1;
+    float a0 = 0.f, a1 = 0.f;
+    const int begin = blockIdx.x * per_wg, end = min(n, begin + per_wg);
+    for (int base = begin; base < end; base += 256) {
+        const int i = base + t;
+        const bool have = i < end;
+        float dT[12], dRc[9];
+        for (int e = 0; e < 12; ++e) dT[e] = 0.f;
+        for (int e = 0; e < 9; ++e) dRc[e] = 0.f;
+        const float* w = skin_w;
+        const float* wc = skin_w;
+        if (have) {
+            w = skin_w + (size_t)nn_posed[i] * NJ;
+            float R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int j = 0; j < NJ; ++j) {
+                const float wj = w[j];
+                if (wj != 0.f)
+                    for (int a = 0; a < 3; ++a)
+                        for (int b = 0; b < 3; ++b) R[3 * a + b] += wj * tl[16 * j + 4 * a + b];
+            }
+            const float c0 = R[4] * R[8] - R[5] * R[7], c1 = R[5] * R[6] - R[3] * R[8], c2 = R[3] * R[7] - R[4] * R[6];
+            const float r = 1.0f / (R[0] * c0 + R[1] * c1 + R[2] * c2);
+            const float I[9] = {c0 * r, (R[2] * R[7] - R[1] * R[8]) * r, (R[1] * R[5] - R[2] * R[4]) * r,
+                                c1 * r, (R[0] * R[8] - R[2] * R[6]) * r, (R[2] * R[3] - R[0] * R[5]) * r,
+                                c2 * r, (R[1] * R[6] - R[0] * R[7]) * r, (R[0] * R[4] - R[1] * R[3]) * r};
+            const float d[3] = {dxc[3 * (size_t)i], dxc[3 * (size_t)i + 1], dxc[3 * (size_t)i + 2]};
+            const float q[3] = {xc[3 * (size_t)i], xc[3 * (size_t)i + 1], xc[3 * (size_t)i + 2]};
+            float u[3];   // u = R^-T dx_c
+            for (int a = 0; a < 3; ++a) u[a] = I[a] * d[0] + I[3 + a] * d[1] + I[6 + a] * d[2];
+            for (int a = 0; a < 3; ++a) {
+                for (int b = 0; b < 3; ++b) dT[4 * a + b] = -u[a] * q[b];
+                dT[4 * a + 3] = -u[a];
+            }
+            if (djinv) {
+                const float* M = jinv + 9 * (size_t)i;
+                const float* dM = djinv + 9 * (size_t)i;
+                float t1[9];   // dRc = -M^T dM M^T
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) {
+                        float sacc = 0.f;
+                        for (int k = 0; k < 3; ++k) sacc += M[3 * k + a] * dM[3 * k + b];
+                        t1[3 * a + b] = sacc;
+                    }
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) {
+                        float sacc = 0.f;
+                        for (int k = 0; k < 3; ++k) sacc += t1[3 * a + k] * M[3 * b + k];
+                        dRc[3 * a + b] = -sacc;
+                    }
+                wc = skin_w + (size_t)nn_cano[i] * NJ;
+            }
+        }
+        for (int round = 0; round < 4; ++round) {
+            if ((t >> 6) == round) {
+                const int l = t & 63;
+                for (int j = 0; j < NJ; ++j) {
+                    sw[l][j] = have ? w[j] : 0.f;
+                    swc[l][j] = (have && djinv) ? wc[j] : 0.f;
+                }
+                for (int e = 0; e < 12; ++e) sdT[l][e] = dT[e];
+                for (int e = 0; e < 9; ++e) sdR[l][e] = dRc[e];
+            }
+            __syncthreads();
+            for (int l = 0; l < WB_SUB; ++l) {
+                a0 += sw[l][j0] * sdT[l][k0];
+                if (r0 >= 0) a0 += swc[l][j0] * sdR[l][r0];
+                if (second) {
+                    a1 += sw[l][j1] * sdT[l][k1];
+                    if (r1 >= 0) a1 += swc[l][j1] * sdR[l][r1];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    part[(size_t)blockIdx.x * (NJ * 12) + t] = a0;
+    if (second) part[(size_t)blockIdx.x * (NJ * 12) + 256 + t] = a1;
+}
+
+// dtfs [24][16] += the workgroups' partial tables [n_part][288], ascending
+__global__ __launch_bounds__(320) void k_warp_bwd_finish(const float* __restrict__ part, int n_part, float* __restrict__ dtfs) {
+    const int e = threadIdx.x;
+    if (e >= 24 * 12) return;
+    float v = 0.f;
+    for (int c = 0; c < n_part; ++c) v += part[(size_t)c * (24 * 12) + e];
+    dtfs[16 * (e / 12) + (e % 12)] += v;
+}
+
+// run length of k_warp_bwd_det: the multiple of 256 points that cuts n points into at most WB_MAX_WGS runs
+int warp_det_run(int n) {
+    const int chunks = (n + 255) / 256;
+    return 256 * ((chunks + WB_MAX_WGS - 1) / WB_MAX_WGS);
+}
+
 // ---- adjoint of x_c = I_nn (x - c_nn) w.r.t. explicit points x = verts[idx[s]] (the smpl_surface regulariser under pose
 // optimisation): dverts[v] += sum_{s : idx[s] == v} I_s^T dxc_s, samples in ascending order (idx is drawn with replacement)
 __global__ void k_gather_bwd(const int* __restrict__ idx, int n, const float* __restrict__ jinv, const float* __restrict__ dxc,
@@ -812,6 +925,19 @@ int mp_tr_warp_bwd(const float* xc, const float* dxc, const float* jinv, const f
                    const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, void* stream) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_warp_bwd, grid1(n), dim3(TB), 0, ST, xc, dxc, jinv, djinv, nn_posed, nn_cano, n, skin_w, tfs, dtfs);
+    return (int)hipGetLastError();
+}
+int mp_tr_warp_bwd_part_floats(int n, long long* floats) {
+    *floats = n <= 0 ? 0 : (long long)((n + warp_det_run(n) - 1) / warp_det_run(n)) * 288;
+    return 0;
+}
+int mp_tr_warp_bwd_det(const float* xc, const float* dxc, const float* jinv, const float* djinv, const int* nn_posed,
+                       const int* nn_cano, int n, const float* skin_w, const float* tfs, float* dtfs, float* part, void* stream) {
+    if (n <= 0) return 0;
+    if (part == nullptr) return -3;
+    const int run = warp_det_run(n), wgs = (n + run - 1) / run;
+    hipLaunchKernelGGL(k_warp_bwd_det, dim3(wgs), dim3(256), 0, ST, xc, dxc, jinv, djinv, nn_posed, nn_cano, n, run, skin_w, tfs, part);
+    hipLaunchKernelGGL(k_warp_bwd_finish, dim3(1), dim3(320), 0, ST, part, wgs, dtfs);
     return (int)hipGetLastError();
 }
 int mp_tr_gather_bwd(const int* idx, int n, const float* jinv, const float* dxc, int n_verts, float* dverts, void* stream) {

@@ -45,10 +45,112 @@ def gemm_nt(A, lda, B, ldb, Cm, ldc, M, N, K, bias=None, bias_rows=0, accumulate
     fn(A, lda, B, ldb, Cm, ldc, M, N, K, bias, bias_rows, int(accumulate), int(relu), hip.stream())
 
 
+# Deterministic training mode (opt-in): every gradient of a step is a function of its inputs alone.  The four places
+# where the default step adds fp32 values with atomics -- the split weight-gradient contractions (csrc/gemm.hip), the last
+# layer's sums of the fused SDF / background backward (csrc/tfuse.hip), d beta of the compositing adjoints (csrc/composite.hip)
+# and the canonical warp's d tfs (csrc/train.hip) -- go through the `_det` entry points instead: partial results by plain
+# stores, added by a finishing kernel in a fixed order.  Switches: MP_TRAIN_DETERMINISTIC=1 (this module's default),
+# model.train_deterministic = True / False (overrides it for that model's training steps), the Trainer's config key
+# `deterministic`.  Off by default: with it off nothing changes.
+def _env_flag(value):
+    return str(value).strip().lower() not in ("", "0", "false", "no", "off")
+
+
+DETERMINISTIC = _env_flag(os.environ.get("MP_TRAIN_DETERMINISTIC", "0"))
+_DET = [None]            # the mode of the TrainGraph whose forward / adjoint sweep is running; None outside one: the module default
+DET_WS_BYTES = 68 << 20  # the contractions' workspace: one round of the wide form is at most 256 slices x 256 KiB (+ column sums)
+_DET_WS = {}             # (device, stream) -> workspace; allocated once, grown only if a larger contraction ever arrives
+
+
+def deterministic(model=None):
+    """is the deterministic training mode on (for `model`'s steps: model.train_deterministic, when set, wins over the default)?"""
+    v = getattr(model, "train_deterministic", None) if model is not None else None
+    return DETERMINISTIC if v is None else bool(v)
+
+
+def _det():
+    return DETERMINISTIC if _DET[0] is None else _DET[0]
+
+
+def det_workspace(n_bytes):
+    """the deterministic contractions' workspace on the current device and stream (calls on one stream run in order, so they share it)"""
+    key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
+    ws = _DET_WS.get(key)
+    if ws is None or 4 * ws.numel() < n_bytes:
+        ws = _DET_WS[key] = torch.empty(max(int(n_bytes), DET_WS_BYTES) // 4 + 4, dtype=F32, device="cuda")
+    return ws
+
+
+def det_workspace_bytes():
+    """bytes the deterministic mode holds in workspaces (all devices and streams)"""
+    return sum(4 * ws.numel() for ws in _DET_WS.values())
+
+
+def release_det_workspace():
+    _DET_WS.clear()
+
+
+def _in_graph_mode(fn):
+    """TrainGraph method decorator: the graph's own mode holds while its forward / adjoint sweep runs"""
+    def wrapped(self, *a, **k):
+        prev, _DET[0] = _DET[0], self.det
+        try:
+            return fn(self, *a, **k)
+        finally:
+            _DET[0] = prev
+    wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
+    return wrapped
+
+
+def _part(query, n):
+    """scratch for the partial sums of a deterministic launch: `query(n, &floats)` floats"""
+    need = C.c_longlong()
+    query(n, C.byref(need))
+    return torch.empty(max(int(need.value), 4), dtype=F32, device="cuda")
+
+
+def tf_bwd(kind, wpack, w8, arena, P, dfeat, dsdf, dw8, db8):
+    """mp_tf_sdf_bwd / mp_tf_bg_bwd (kind 'sdf' | 'bg'), or their deterministic forms"""
+    L, st = hip.lib(), hip.stream()
+    assert kind in ("sdf", "bg")
+    if _det():
+        part = _part(L.mp_tf_bwd_part_floats, P)
+        if kind == "sdf":
+            L.mp_tf_sdf_bwd_det(wpack, w8, arena, P, dfeat, dsdf, dw8, db8, part, st)
+        else:
+            L.mp_tf_bg_bwd_det(wpack, w8, arena, P, dfeat, dsdf, dw8, db8, part, st)
+    elif kind == "sdf":
+        L.mp_tf_sdf_bwd(wpack, w8, arena, P, dfeat, dsdf, dw8, db8, st)
+    else:
+        L.mp_tf_bg_bwd(wpack, w8, arena, P, dfeat, dsdf, dw8, db8, st)
+
+
+def warp_bwd(xc, dxc, jinv, djinv, nn_posed, nn_cano, n, skin_w, tfs, dtfs):
+    """mp_tr_warp_bwd, or its deterministic form"""
+    L, st = hip.lib(), hip.stream()
+    if _det():
+        L.mp_tr_warp_bwd_det(xc, dxc, jinv, djinv, nn_posed, nn_cano, n, skin_w, tfs, dtfs, _part(L.mp_tr_warp_bwd_part_floats, n), st)
+    else:
+        L.mp_tr_warp_bwd(xc, dxc, jinv, djinv, nn_posed, nn_cano, n, skin_w, tfs, dtfs, st)
+
+
 def gemm_tn(A, lda, B, ldb, Cm, ldc, M, N, K, colsum=None, colsum_rows=0):
     """Cm[M,N] += A[K,M]^T B[K,N];  colsum[M] += column sums of A's first colsum_rows rows (the bias gradient)"""
+    if _det():
+        return _gemm_tn_det(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows)
     fn = hip.lib().mp_gemm_tn if TRAIN_PRECISION == "f32" else hip.lib().mp_gemm_tn_bf16x3
     fn(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows, hip.stream())
+
+
+def _gemm_tn_det(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows):
+    """gemm_tn in the deterministic mode: the workspace the size query asks for, then the `_det` entry point"""
+    need = C.c_longlong()
+    hip.lib().mp_gemm_tn_ws_bytes(M, N, K, int(TRAIN_PRECISION != "f32"), C.byref(need))
+    ws = det_workspace(need.value)
+    if TRAIN_PRECISION == "f32":
+        hip.lib().mp_gemm_tn_det(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows, ws, 4 * ws.numel(), hip.stream())
+    else:
+        hip.lib().mp_gemm_tn_bf16x3_det(A, lda, B, ldb, Cm, ldc, M, N, K, colsum, colsum_rows, ws, 4 * ws.numel(), hip.stream())
 
 
 class MpTnGroup(C.Structure):
@@ -68,6 +170,12 @@ def gemm_tn_grouped(groups):
     for i in range(0, len(groups), 24):
         chunk = groups[i:i + 24]
         arr = (MpTnGroup * len(chunk))(*chunk)
+        if _det():
+            need = C.c_longlong()
+            hip.lib().mp_gemm_tn_grouped_ws_bytes(arr, len(chunk), C.byref(need))
+            ws = det_workspace(need.value)
+            hip.lib().mp_gemm_tn_bf16x3_grouped_det(arr, len(chunk), ws, 4 * ws.numel(), hip.stream())
+            continue
         hip.lib().mp_gemm_tn_bf16x3_grouped(arr, len(chunk), hip.stream())
 
 
@@ -766,7 +874,7 @@ class ImplicitTrainFused(_FusedImplicit):
         self.dx = torch.zeros(P, 3, dtype=F32, device=self.x.device) if want_dx else None
         L.mp_tr_pe_grad_bwd(self.x, P, net.multires, dgrad, off(A, self.o_G), E, dG, E, self.dx, st)
         lw8 = self.lins[8]                              # the sdf row's gradient goes straight into row 0 of dW_8 / db_8
-        L.mp_tf_sdf_bwd(fs.wpack, self.w8, A, P, dfeat, dsdf, lw8.dW, lw8.db, st)
+        tf_bwd("sdf", fs.wpack, self.w8, A, P, dfeat, dsdf, lw8.dW, lw8.db)
         L.mp_tr_copy_cols(dG, E, 0, self._at(self.t_dT, 4), 256, 256 - E, P, E, 1.0 / math.sqrt(2.0), 0, st)
         if want_dx:                                     # d x_c += J_PE^T (dZ_0 W_0[:, :39] + dZ_4 W_4[:, 217:] / sqrt 2)
             lw0, lw4 = self.lins[0], self.lins[4]
@@ -783,7 +891,7 @@ class ImplicitTrainFused(_FusedImplicit):
         f32 = dict(dtype=F32, device=self.x.device)
         A[self.o_dG:self.o_dG + E * P].zero_()          # the gradient sweep has no upstream here
         scratch = torch.zeros(257, **f32)               # d w8 [256], d b8 [1]
-        L.mp_tf_sdf_bwd(self.fs.wpack, self.w8, A, P, torch.zeros(P, 256, **f32), dsdf, scratch, off(scratch, 256), st)
+        tf_bwd("sdf", self.fs.wpack, self.w8, A, P, torch.zeros(P, 256, **f32), dsdf, scratch, off(scratch, 256))
         dx = torch.zeros(P, 3, **f32)
         lw0, lw4 = self.lins[0], self.lins[4]
         L.mp_tf_sdf_dx(A, P, lw0.W, lw0.in_dim, lw4.W, lw4.in_dim, self.x, dx, st)
@@ -806,7 +914,7 @@ class ImplicitTrainFusedBG(_FusedImplicit):
     def backward(self, dfeat, dsdf, dgrad=None, want_dx=False, tn_groups=None):
         assert dgrad is None and not want_dx and dfeat.shape[1] == 256
         lw8 = self.lins[8]
-        hip.lib().mp_tf_bg_bwd(self.fs.wpack, lw8.W, self.arena, self.P, dfeat, dsdf, lw8.dW, lw8.db, hip.stream())
+        tf_bwd("bg", self.fs.wpack, lw8.W, self.arena, self.P, dfeat, dsdf, lw8.dW, lw8.db)
         return self._weight_grads(dfeat, tn_groups, gradient_sweep=False)
 
 
@@ -1145,8 +1253,8 @@ class Interpenetration:
         dxc_at, held = [0] * (P * P), []
         for q, b, it, X, nnq, seed in self.items:
             dxc = it.points_adjoint(seed)                        # (exact zeros on the padding and on the inactive entries)
-            L.mp_tr_warp_bwd(X, dxc, None, None, nnq, None, X.shape[0], m.smpl_server_list[q].tables.lbs_weights, cx["per"][q]["tfs"],
-                             shares[q][0], st)
+            warp_bwd(X, dxc, None, None, nnq, None, X.shape[0], m.smpl_server_list[q].tables.lbs_weights, cx["per"][q]["tfs"],
+                     shares[q][0])
             for slot, a in enumerate(a for a in range(P) if a != b):
                 dxc_at[a * P + b] = dxc.data_ptr() + 12 * slot * n
             held.append(dxc)
@@ -1165,6 +1273,7 @@ class TrainGraph:
         (512 of them: cheaper than a second exchange in the backward), the background branch is ray-sliced."""
         self.model, self.cx, self.input, self.cond_zero, self.draws = model, cx, input, cond_zero, draws
         self.surface_flags, self.pose_grad, self.shard = surface_flags, pose_grad, shard
+        self.det = deterministic(model)       # the deterministic training mode, fixed for this graph's forward and adjoint sweep
         self.ts = ts if ts is not None else train_state(model).begin()     # shared layers: weights resolved, accumulators zeroed
         self.reg_items, self.reg_losses = [], (None, None)
         self.reg_dcond = {}             # person -> adjoint of its pose conditioning from the regularisers (pose optimisation)
@@ -1177,6 +1286,7 @@ class TrainGraph:
         self.pen, self.pen_loss = None, None
 
     # ---- forward ------------------------------------------------------------------------------------------------
+    @_in_graph_mode
     def run(self):
         m, cx = self.model, self.cx
         rs = m.ray_sampler
@@ -1492,7 +1602,7 @@ class TrainGraph:
                     pp, server = self.cx["per"][q], self.model.smpl_server_list[q]
                     dxc = it.dx.contiguous()
                     dtfs = torch.zeros(24, 16, dtype=F32, device=dev)
-                    L.mp_tr_warp_bwd(xc, dxc, None, None, nn, None, n, server.tables.lbs_weights, pp["tfs"], dtfs, st)
+                    warp_bwd(xc, dxc, None, None, nn, None, n, server.tables.lbs_weights, pp["tfs"], dtfs)
                     dverts = torch.zeros(server.verts_c.reshape(-1, 3).shape[0], 3, dtype=F32, device=dev)
                     L.mp_tr_gather_bwd(idx, n, jv, dxc, dverts.shape[0], dverts, st)
                     prev = self.reg_surf.get(q)
@@ -1538,6 +1648,7 @@ class TrainGraph:
             self.reg_surf[p] = (dtfs, dverts) if prev is None else (prev[0] + dtfs, prev[1] + dverts)
 
     # ---- backward -----------------------------------------------------------------------------------------------
+    @_in_graph_mode
     def backward(self, d_rgb_values, d_acc_map, d_acc_person, d_grad_theta, d_ssl=None, d_zpl=None, d_geometry=None, d_pen=None):
         """-> {id(parameter): gradient}.  d_geometry: the upstream gradients of GEOMETRY_KEYS[:5] (train_geometry), None = no term;
         d_pen: the upstream gradient of the interpenetration term (train_interpenetration), None = unused"""
@@ -1604,14 +1715,26 @@ class TrainGraph:
         d_bg_rgb = zp.take(R, 3)
         d_beta = zp.take(1)
         t_dsdf, t_drgb = _table(dsdf_l, dev), _table(drgb_l, dev)
-        hip.lib().mp_tr_composite_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, cx["beta"], self.bg_rgb, d_rgb_values, d_acc_map,
-                                      d_acc_person, t_dsdf, t_drgb, d_bg_rgb, d_beta, hip.stream())
+        det = _det()
+        part = torch.empty(max(R, 1), dtype=F32, device=dev) if det else None      # the rays' own d beta sums (deterministic form)
+        if det:
+            hip.lib().mp_tr_composite_bwd_det(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, cx["beta"], self.bg_rgb, d_rgb_values,
+                                              d_acc_map, d_acc_person, t_dsdf, t_drgb, d_bg_rgb, d_beta, part, hip.stream())
+        else:
+            hip.lib().mp_tr_composite_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, t_rgb, cx["beta"], self.bg_rgb, d_rgb_values, d_acc_map,
+                                          d_acc_person, t_dsdf, t_drgb, d_bg_rgb, d_beta, hip.stream())
         if d_geometry is not None and any(g is not None for g in d_geometry):
             # after the store above, on the same stream: the kernel adds (a missing upstream gradient is a NULL pointer)
             d_depth, d_depth_person, d_acc_solo, d_depth_solo, d_depth_solo_level = (
                 None if g is None else g.contiguous().float() for g in d_geometry)
-            hip.lib().mp_tr_composite_geometry_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, cx["beta"], self.level, d_depth, d_depth_person,
-                                                   d_acc_solo, d_depth_solo, d_depth_solo_level, t_dsdf, d_beta, hip.stream())
+            if det:
+                hip.lib().mp_tr_composite_geometry_bwd_det(R, P, self.NZ, t_inv, t_z, t_sdf, cx["beta"], self.level, d_depth,
+                                                           d_depth_person, d_acc_solo, d_depth_solo, d_depth_solo_level, t_dsdf,
+                                                           d_beta, part, hip.stream())
+            else:
+                hip.lib().mp_tr_composite_geometry_bwd(R, P, self.NZ, t_inv, t_z, t_sdf, cx["beta"], self.level, d_depth,
+                                                       d_depth_person, d_acc_solo, d_depth_solo, d_depth_solo_level, t_dsdf, d_beta,
+                                                       hip.stream())
         return dsdf_l, drgb_l, d_bg_rgb, d_beta
 
     def _person_backward(self, p, dsdf, drgb, dgth):
@@ -1645,8 +1768,7 @@ class TrainGraph:
         npts = f["npts"]
         dxc = (f["it"].dx[:npts] + dXA[:, :3]).contiguous()
         dtfs = torch.zeros(24, 16, **f32)
-        L.mp_tr_warp_bwd(f["X"], dxc, f["jinv"], djinv, f["nn_posed"], f["nn_cano"], npts, server.tables.lbs_weights, pp["tfs"],
-                         dtfs, st)
+        warp_bwd(f["X"], dxc, f["jinv"], djinv, f["nn_posed"], f["nn_cano"], npts, server.tables.lbs_weights, pp["tfs"], dtfs)
         surf = self.reg_surf.get(p)
         if surf is None:
             dprm = torch.empty(86, **f32)
@@ -1734,6 +1856,9 @@ def forward_train(model, input, id=-1, cond_zero_shit=False, canonical_pose=Fals
     node whose backward is the hand-written adjoint sweep.  With model.train_geometry the dict also carries GEOMETRY_KEYS
     (Multiply._composite_geometry's names and shapes, columns = acc_person_list's) off the same node."""
     epoch = int(input["current_epoch"])
+    if shard is not None and deterministic(model):
+        raise NotImplementedError("person-sharded training (shard=) is not built for the deterministic training mode: the ranks' "
+                                  "shared gradients are summed by collectives whose order this mode does not fix")
     if shard is not None and model.training and getattr(model, "train_geometry", False):
         raise NotImplementedError("train_geometry is not built for person-sharded training (shard=)")
     if shard is not None and model.training and getattr(model, "train_interpenetration", False):

@@ -77,14 +77,27 @@ def epoch_end_plan(epoch, cfg):
 # ====================================================================================================================
 # Checkpoints: Lightning's layout (followed, not verified against a file Lightning wrote)
 # ====================================================================================================================
-def checkpoint_dict(epoch, global_step, model_state, body_states, optimizer_states, lr_schedulers):
+def checkpoint_dict(epoch, global_step, model_state, body_states, optimizer_states, lr_schedulers, deterministic=None):
     """One torch.save dict: the scene model under 'model.', the body tables under 'body_model_list.<i>.<name>.weight'
-    (MultiplyModel's attribute names), optimizer_states = [joint, pose]."""
+    (MultiplyModel's attribute names), optimizer_states = [joint, pose].  deterministic (not None): recorded under 'deterministic'
+    -- whether the run that wrote the checkpoint trained in the deterministic mode (train.deterministic)."""
     sd = {"model." + k: v for k, v in model_state.items()}
     for i, bs in enumerate(body_states):
         sd.update({f"body_model_list.{i}.{k}": v for k, v in bs.items()})
-    return {"epoch": int(epoch), "global_step": int(global_step), "state_dict": sd, "optimizer_states": list(optimizer_states),
+    ckpt = {"epoch": int(epoch), "global_step": int(global_step), "state_dict": sd, "optimizer_states": list(optimizer_states),
             "lr_schedulers": list(lr_schedulers)}
+    if deterministic is not None:
+        ckpt["deterministic"] = bool(deterministic)
+    return ckpt
+
+
+def deterministic_from_config(opt, default=None):
+    """the config key `deterministic` (true / false; strings as the MP_TRAIN_DETERMINISTIC variable reads them) or `default`"""
+    v = opt.get("deterministic", None) if hasattr(opt, "get") else getattr(opt, "deterministic", None)
+    if v is None:
+        return default
+    from .train import _env_flag
+    return _env_flag(v) if isinstance(v, str) else bool(v)
 
 
 def split_checkpoint(ckpt):
@@ -394,7 +407,11 @@ class Trainer:
     shuffled order drawn from `rng`); validset / testset: Hi4DValDataset / Hi4DTestDataset or None; sam_server: a
     sam_prompts.SAMServer or None (the mask stage is then skipped and says so in the log).
     seed: every epoch re-seeds torch, the shuffle and the training set's sample draws from (seed, epoch), so that a run resumed from
-    a checkpoint draws what the uninterrupted run draws (the reference seeds once, train.py:12, and a resumed run diverges)."""
+    a checkpoint draws what the uninterrupted run draws (the reference seeds once, train.py:12, and a resumed run diverges).
+    Config key `deterministic` (default: unset = the process default, MP_TRAIN_DETERMINISTIC): sets model.train_deterministic, the
+    deterministic training mode (train.py); with it and a seed, a run resumed from a checkpoint reaches the SAME BITS
+    as the uninterrupted run -- for steps whose plan carries no mesh-space term: get_depth_order_loss adds with torch scatters
+    (index_add), which are outside the guarantee.  The mode a run trained in is recorded in its checkpoints ('deterministic')."""
 
     def __init__(self, opt, model, body_model_list, loss_fn, trainset, validset=None, testset=None, sam_server=None, out_dir=".",
                  rng=None, log=print, seed=None):
@@ -407,6 +424,9 @@ class Trainer:
         self.cfg = dict(SCHEDULE_DEFAULTS)
         self.cfg.update({k: opt.get(k) for k in SCHEDULE_DEFAULTS if opt.get(k, None) is not None})
         self.last_depth_history = None
+        det = deterministic_from_config(opt)
+        if det is not None:
+            model.train_deterministic = det
         if opt.get("using_SAM", None) is None:
             self.cfg["using_SAM"] = bool(getattr(trainset, "using_SAM", False))
         self.lr0, self.milestones, self.gamma = float(opt.learning_rate), list(opt.sched_milestones), float(opt.sched_factor)
@@ -674,8 +694,10 @@ class Trainer:
         e = self.epoch - 1
         scheds = [scheduler_state(e, [self.lr0, 0.1 * self.lr0], self.milestones, self.gamma),
                   scheduler_state(e, [0.1 * self.lr0], self.milestones, self.gamma)]
+        from .train import deterministic
         return checkpoint_dict(e, self.global_step, self.model.state_dict(), [bm.state_dict() for bm in self.body],
-                               [self.opt_joint.state_dict(), self.opt_pose.state_dict()], scheds)
+                               [self.opt_joint.state_dict(), self.opt_pose.state_dict()], scheds,
+                               deterministic=deterministic(self.model))
 
     def save_checkpoint(self, path):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

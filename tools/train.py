@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """Train a scene folder end to end (multiply_amd/trainer.py; what code/train.py does with Lightning and hydra).
     python tools/train.py --scene DIR [--conf YAML] --out DIR --epochs N [--resume] [--rays 512] [--seed 42] [--synthetic-smpl]
-                          [--sam-checkpoint FILE]
+                          [--sam-checkpoint FILE] [--deterministic]
 --scene: a folder in the layout datasets.Hi4DDataset reads (tools/build_scene.py writes one).  --conf: a model config in the layout
 of multiply_amd/confs/model.yaml (default: that file); the schedule keys of trainer.SCHEDULE_DEFAULTS go there too.  --out: the run
 folder (stage files, rendering/, checkpoints/).  --resume: continue from the newest OUT/checkpoints/epoch=*.ckpt, or from last.ckpt
 when that file is more recent.
 --synthetic-smpl: the seeded synthetic body tables instead of the licensed SMPL model (scenes of synthetic.write_sequence).
 --sam-checkpoint: build segment_anything's predictor from this file for the mask stage; without it the stage is skipped.
+--deterministic: the deterministic training mode (the config key `deterministic`): with --seed, the same run gives the same bits.
 Prints one JSON line per epoch: the epoch's mean loss terms, steps, skipped NaN steps, learning rate, seconds and ms per step."""
 import argparse
 import json
@@ -29,6 +30,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--synthetic-smpl", action="store_true")
     ap.add_argument("--sam-checkpoint", default=None)
+    ap.add_argument("--deterministic", action="store_true")
     args = ap.parse_args(argv)
     import torch
     from multiply_amd import trainer as T
@@ -42,7 +44,10 @@ def main(argv=None):
         from multiply_amd.synthetic import make_smpl_tables
         tables = make_smpl_tables(0)
     lines = []
-    tr = T.build_trainer(args.scene, args.out, opt=load_config(args.conf), dataset_opt=dict(num_sample=args.rays),
+    opt = load_config(args.conf)
+    if args.deterministic:
+        opt["deterministic"] = True
+    tr = T.build_trainer(args.scene, args.out, opt=opt, dataset_opt=dict(num_sample=args.rays),
                          sam_predictor=predictor, smpl_tables=tables, seed=args.seed, log=lines.append)
     if args.resume:
         # the newest epoch=*.ckpt as code/train.py:44 takes it, or last.ckpt when that is the more recent file (this tool writes one

@@ -2,7 +2,7 @@
 """Training iterations only (bench.py's train_iter leg): ms/iter, GPU phase times; run it under
 `rocprofv3 --kernel-trace` + tools/rocpd_summary.py for the per-kernel table of ONE iteration's work.
     python tools/train_bench.py [steps] [warmup] [--epoch E] [--mesh-index auto|index|brute] [--pose-grad] [--train-geometry]
-                                                   [--train-interpenetration]
+                                                   [--train-interpenetration] [--deterministic]
 --epoch E: every forward sees current_epoch = E instead of bench.py's 301.  Below 250 the in / off-surface flags are on; as the
 trainer has refreshed the canonical meshes by then (every 20 epochs), they are extracted once before the loop.
 --mesh-index: model.mesh_index_mode (the flags' signed distance through the face index or by brute force).
@@ -15,7 +15,9 @@ temporal term, which the loss adds with weight 1), so that the iteration holds b
 forward and mp_tr_composite_geometry_bwd in the backward.
 --train-interpenetration: model.train_interpenetration = True, and the term joins the timed loss the same way: the probe, the
 partners' SDF at the probed points and mp_pen_loss in the forward (with the term's one host read of the pair counts) and, with
---pose-grad, its adjoint (mp_tf_sdf_bwd / _dx per partner, mp_tr_warp_bwd, mp_pen_scatter_bwd) at the head of the backward."""
+--pose-grad, its adjoint (mp_tf_sdf_bwd / _dx per partner, mp_tr_warp_bwd, mp_pen_scatter_bwd) at the head of the backward.
+--deterministic: model.train_deterministic = True (the deterministic training mode); the line then also reports the
+bytes of the contractions' workspace."""
 import json
 import os
 import subprocess
@@ -44,6 +46,9 @@ opts = {}
 POSE_GRAD = "--pose-grad-child" in args
 TRAIN_GEOMETRY = "--train-geometry" in args
 TRAIN_PEN = "--train-interpenetration" in args
+DETERMINISTIC = "--deterministic" in args
+if DETERMINISTIC:
+    args.remove("--deterministic")
 if TRAIN_GEOMETRY:
     args.remove("--train-geometry")
 if TRAIN_PEN:
@@ -82,6 +87,8 @@ if TRAIN_PEN:
     model.train_interpenetration = True
     model.register_forward_hook(lambda mod, a, out: {**out, "temporal_loss": out["temporal_loss"] + out["interpenetration_loss"].sum()}
                                 if mod.training else None)
+if DETERMINISTIC:
+    model.train_deterministic = True
 if "--mesh-index" in opts:
     model.mesh_index_mode = opts["--mesh-index"]
 EPOCH = int(opts.get("--epoch", 301))
@@ -98,13 +105,13 @@ def barrier():
 
 
 dt, ph, loss, stats, host_ms = bench.train_iterations(model, gin, steps, warm, False, barrier, seed=0, rays=512)
-extra = {}
+from multiply_amd import train as T
+extra = {"deterministic": T.deterministic(model), "det_workspace_bytes": T.det_workspace_bytes()}
 if POSE_GRAD:
-    from multiply_amd import train as T
     graph = model._last_train
     assert graph.pose_grad
-    extra = {"pose_grad": True, "sdf_pose_grad_mode": T.SDF_POSE_GRAD_MODE,
-             "sdf_evaluator": "/".join(sorted({type(f["it"]).__name__ for f in graph.fg.values()}))}
+    extra.update({"pose_grad": True, "sdf_pose_grad_mode": T.SDF_POSE_GRAD_MODE,
+                  "sdf_evaluator": "/".join(sorted({type(f["it"]).__name__ for f in graph.fg.values()}))})
 print(json.dumps({**extra, "train_geometry": TRAIN_GEOMETRY, "train_interpenetration": TRAIN_PEN, "current_epoch": EPOCH, "mesh_index_mode": model.mesh_index_mode, "ms_per_iter": 1e3 * dt / steps, "host_ms_per_iter": host_ms, "gpu_ms": {"forward+loss": ph[0], "backward": ph[1], "allreduce": ph[2],
                                                                "adam": ph[3]}, "hit_rays": stats["n_hit"], "loss": loss}))
 
