@@ -351,7 +351,17 @@ int mp_sampler_resample(const MpSamplerCfg* cfg, const MpSamplerState* st, const
  * alpha = 1-exp(-sigma dt), T = exp(-exclusive cumsum), sums; bg transmittance = exclusive T of the last sample.
  *   per person p: inv_index[p] [R], z[p] [*][n_z] (n_z = S+1 depths, last = z_max), sdf[p] [*][S], rgb[p] [*][S][3],
  *   normal[p] [*][S][3]  (pointer tables live in device memory, P entries each)
- * Outputs [R]: fg_rgb[3], normal[3], acc, acc_person[P], bg_T; rgb = fg + bg_T*bg_rgb; fg_out = fg + bg_T. */
+ * Outputs [R]: fg_rgb[3], normal[3], acc, acc_person[P], bg_T; rgb = fg + bg_T*bg_rgb; fg_out = fg + bg_T.
+ * Tie rules: samples of equal t_end merge with the lower person first; hence, when several persons end at the same final
+ * depth, the HIGHER person's last sample is the last of the merged list, and bg_T is the transmittance in front of that sample
+ * (everything of the other persons and that person's first S-1 samples).  A ray without samples: rgb = bg_rgb, fg_out = 1,
+ * normal = 0, acc = 0, bg_T = 1; a person the ray misses (inv_index < 0): exactly 0 in its acc_person column.
+ * Zero-weight rule: rgb and normal of a sample are read only where its float32 weight w is not exactly 0 -- the eval path leaves
+ * the colours and normals of unshaded samples undefined (they may be NaN), and such samples have fe = 0, hence w = 0.
+ * bg_rgb may be NULL: a white background (bg = 1).  Every output pointer is required.  All outputs are stored, rows [0, n_rays)
+ * only; no atomics, fixed summation order: bit-identical from run to run.
+ * Status: -1 n_person outside [0, 8]; 0 for n_rays <= 0; -2 LDS limit: 4 waves x n_person x (3S+1) floats must fit 160 KiB (at
+ * n_person = 8 up to S = 426).  In all three nothing is launched and nothing written. */
 int mp_composite(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
                  const float* const* sdf, const float* const* rgb, const float* const* normal, const float* beta,
                  const float* bg_rgb, float* rgb_values, float* fg_rgb_values, float* normal_values, float* acc_map,
@@ -478,7 +488,24 @@ int mp_tr_hoist_fwd(const float* W, int out_dim, int in_dim, const float* b, int
                     void* stream);
 int mp_tr_hoist_bwd(const float* db2, int out_dim, int in_dim, int c0, int n, const float* vec, float* dW, void* stream);
 int mp_tr_colsum(const float* dZ, int ld, int rows, int C, float* db, void* stream);
-/* adjoint of mp_composite: d rgb_values / d acc_map / d acc_person -> d sdf[p], d rgb[p], d bg_rgb, d beta (+=) */
+/* adjoint of mp_composite: d rgb_values / d acc_map / d acc_person -> d sdf[p], d rgb[p], d bg_rgb, d beta (z is a constant).
+ * With dC / dA / dA_p the ray's upstream gradients, dw_j = dC . rgb_j + dA + dA_p(j), dT_bg = dC . bg, in merged order:
+ *   dfe_j = dw_j T_j e^-fe_j - sum_{i behind j} dw_i w_i - [j is not the very last sample] dT_bg T_bg
+ *   d rgb_j = w_j dC,  d bg_rgb = T_bg dC,  d sigma_j = dfe_j (te-ts)_j -> d sdf, d beta through the Laplace density.
+ * The merge, both tie rules and T_bg are mp_composite's: the very last sample is the last one of the person whose final depth is
+ * the largest, of the HIGHER person on a tie.
+ * Store or accumulate: d_sdf[p] and d_rgb[p] are STORED, for every sample of every row that a ray below n_rays refers to; rows of
+ * persons a ray misses, rows no such ray refers to and everything past the person's table are not touched.  d_bg_rgb rows
+ * [0, n_rays) are stored (T_bg = 1 on a ray without samples).  d_beta ACCUMULATES (+=: one float32 atomic add per ray).
+ * NULL: bg_rgb (white background), d_acc, d_acc_person (term dropped), d_bg_rgb (not written).  d_rgb_values is required.
+ * Colours: unlike mp_composite this kernel reads the rgb of EVERY sample of a hit row, whatever its weight: dw_j w_j with an
+ * undefined (NaN) colour at a zero-weight sample would poison the ray.  Its one caller is the training step, which shades every
+ * sample of every hit row (train.py: the colour evaluator runs on all Rp*S points), so every colour is defined there; tables
+ * from the eval path, whose unshaded samples carry no colour, must not be handed to it.
+ * Launch shape: 4 waves per block, halved down to 1 until n_person x (5S+2) floats per wave fit 160 KiB of LDS (at n_person = 8:
+ * 2 waves from S = 256, 1 wave from S = 512).
+ * Status: -1 n_person outside [0, 8]; 0 for n_rays <= 0; -2 LDS limit: one wave does not fit.  In all three nothing is launched
+ * and nothing written. */
 int mp_tr_composite_bwd(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
                         const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
                         const float* d_rgb_values, const float* d_acc, const float* d_acc_person, float* const* d_sdf,
@@ -502,7 +529,8 @@ int mp_tr_composite_geometry_bwd(int n_rays, int n_person, int n_z, const int* c
                                  float* const* d_sdf, float* d_beta, void* stream);
 /* DETERMINISTIC forms of the two adjoints: every ray's wave STORES its own d beta sum into d_beta_part [n_rays] (the caller's
  * scratch) and a finishing kernel adds them in a fixed order (thread t of 256: rays t, t + 256, .. ascending; then the 256 sums
- * ascending) into d_beta (+=).  Everything else as above (d sdf / d rgb never went through atomics).  -3: d_beta_part is NULL. */
+ * ascending) into d_beta (+=).  Everything else as above (d sdf / d rgb never went through atomics: they are bit-equal to the plain
+ * forms').  -3: d_beta_part is NULL (checked after the other status codes: n_rays <= 0 still gives 0). */
 int mp_tr_composite_bwd_det(int n_rays, int n_person, int n_z, const int* const* inv_index, const float* const* z,
                             const float* const* sdf, const float* const* rgb, const float* beta, const float* bg_rgb,
                             const float* d_rgb_values, const float* d_acc, const float* d_acc_person, float* const* d_sdf,
