@@ -912,6 +912,59 @@ int mp_pose_errors(const float* pred, const float* gt, const float* pred_root, c
 int mp_contact_distance(const float* verts, int F, int P, int V, const int* faces, int n_faces, const int* corr, const float* bary,
                         const int* frame_start, int m, double* work, double* out, void* stream);
 
+/* ---- registration of meshes before the mesh metrics (multiply_amd/registration.py, csrc/registration.hip; the reference has no
+ * code for it: the paper's protocol aligns the monocular reconstruction, which lives in a normalised frame, to the scans).
+ * Point-to-plane ICP for x = s R p + t, rigid (s fixed) or similarity, on closest-surface correspondences.  Everything after the
+ * loads is DOUBLE, there are no atomics, partial sums are finished in a fixed order: the same inputs give the same bits.
+ *   state [MP_REG_STATE] doubles in device memory, the whole iteration state (indices MP_REG_*):
+ *       S scale; R [9] row-major; T [3]; TAU2 the acceptance threshold on |x - q|^2 of the NEXT rows launch (+inf: accept all);
+ *       RMS sqrt(sum |x - q|^2 / accepted) of the last step's pairs; ACCEPTED / REJECTED / LEFT_OUT (non-finite) their counts;
+ *       ITERS steps taken; FLAG 0 = running, MP_REG_CONVERGED, MP_REG_DEGENERATE; STEP the last step size; C [3] the fixed origin
+ *       the rows are formed about; BOX_LO / BOX_HI [3] the target's bounding box; RMS_PLANE sqrt(sum r^2 / accepted).
+ *       The host writes S, R, T, TAU2, C, BOX_* (C = the box's centre) and zeroes the rest; the kernels do the rest.
+ *   slot [MP_REG_SLOT] doubles, one direction's sums: ATA the 28 entries of the upper triangle of A^T A (row-major, i <= j), ATR
+ *       the 7 of A^T r, R2 = sum r^2, D2 = sum |x - q|^2, ACCEPTED / REJECTED / LEFT_OUT counts.
+ *   mp_reg_apply     : out[i] = s R p[i] + t (inverse = 0) or R^T (p[i] - t) / s (inverse != 0), the transform read from state, in
+ *                      double, rounded once to fp32.  out may be p.
+ *   mp_reg_rows      : pairs (p[i] in the source frame, q[i] in the target frame) with unit normals: normals [n][3] per pair when
+ *                      face == NULL, else normals [n_faces][3] and face [n] ids into it.  normals_in_source != 0: n = R n.  x = s R p
+ *                      + t.  A pair with a non-finite value (or a face id outside [0, n_faces)) is LEFT OUT; one with |x - q|^2 >
+ *                      TAU2 is REJECTED; every other adds the row a = [(x - c) x n, n, (x - c) . n], residual r = (x - q) . n, to
+ *                      the slot's sums.  mask [n] bytes (may be NULL) receives 0 accepted / 1 rejected / 2 left out.  Workgroup b
+ *                      of G = min(ceil(n / 256), MP_REG_MAX_BLOCKS) takes the pairs b 256 + t + k G 256 (thread t, k = 0, 1, ..),
+ *                      lanes are added by the xor butterfly, waves in order, and a finishing launch adds the workgroups' partial
+ *                      sums work [MP_REG_MAX_BLOCKS][MP_REG_SLOT] in ascending order into slot.  n == 0 writes a zero slot.
+ *   mp_reg_step      : ONE workgroup adds slots [n_slots][MP_REG_SLOT] in ascending order, solves the 6 x 6 (similarity == 0) or
+ *                      7 x 7 normal equations A^T A delta = -A^T r by Cholesky, composes R <- exp([omega]x) R (Rodrigues), s <- s
+ *                      exp(sigma), t <- c + exp(sigma) exp([omega]x) (t - c) + v, and writes RMS, the counts, TAU2 = (reject rms)^2
+ *                      (+inf for reject == 0), STEP = the largest displacement of the 8 corners of the box between the old and the
+ *                      new transform, and FLAG = MP_REG_CONVERGED when STEP <= tol |BOX_HI - BOX_LO|.  Fewer than 7 accepted pairs
+ *                      or a pivot not above 2^-40 of its diagonal entry: FLAG = MP_REG_DEGENERATE, the transform stays.  (The
+ *                      routine is csrc/reg_solve.hpp, __host__ __device__.)
+ *   Once FLAG != 0 both of the above return without writing anything: a fixed sequence of launches needs no host synchronisation
+ *   to stop.
+ *   mp_reg_fit_pairs : the closed form (Umeyama 1991) for weighted pairs: means p_, q_ (pass 1), H = sum w (p - p_)(q - q_)^T and
+ *                      sum w |p - p_|^2 about them (pass 2), R by the Procrustes routine of csrc/procrustes.hpp, s = tr(S D) / sum
+ *                      w |p - p_|^2 (1 when similarity == 0), t = q_ - s R p_.  w == NULL: all 1.  A pair with a non-finite value or
+ *                      a weight that is not > 0 is left out.  out [16] doubles = s, R [9], t [3], sum w, pairs left out, status (0;
+ *                      1: sum w == 0; 2: the p coincide, s = 1).  One workgroup, the order of k_pose_errors.
+ * Status -1 without a launch: a negative size, a NULL required pointer (p / q / normals / out may be NULL only with n == 0),
+ * n_slots < 1, n_faces < 1 with a face list, reject < 0 or tol < 0 (or not a number). */
+#define MP_REG_STATE 32
+#define MP_REG_SLOT 40
+#define MP_REG_MAX_BLOCKS 256
+enum { MP_REG_S = 0, MP_REG_R = 1, MP_REG_T = 10, MP_REG_TAU2 = 13, MP_REG_RMS = 14, MP_REG_ACCEPTED = 15, MP_REG_REJECTED = 16,
+       MP_REG_LEFT_OUT = 17, MP_REG_ITERS = 18, MP_REG_FLAG = 19, MP_REG_STEP = 20, MP_REG_C = 21, MP_REG_BOX_LO = 24,
+       MP_REG_BOX_HI = 27, MP_REG_RMS_PLANE = 30 };
+enum { MP_REG_SLOT_ATA = 0, MP_REG_SLOT_ATR = 28, MP_REG_SLOT_R2 = 35, MP_REG_SLOT_D2 = 36, MP_REG_SLOT_ACCEPTED = 37,
+       MP_REG_SLOT_REJECTED = 38, MP_REG_SLOT_LEFT_OUT = 39 };
+enum { MP_REG_CONVERGED = 1, MP_REG_DEGENERATE = 2 };
+int mp_reg_apply(const float* p, int n, const double* state, int inverse, float* out, void* stream);
+int mp_reg_rows(const float* p, const float* q, const float* normals, const int* face, int n_faces, int normals_in_source, int n,
+                const double* state, double* work, double* slot, unsigned char* mask, void* stream);
+int mp_reg_step(const double* slots, int n_slots, int similarity, double reject, double tol, double* state, void* stream);
+int mp_reg_fit_pairs(const float* p, const float* q, const float* w, int n, int similarity, double* out, void* stream);
+
 /* ---- refining SMPL fits to 2D keypoints (multiply_amd/keypoint_fit.py, csrc/keypoint_fit.hip; the reference's `refine` mode,
  * preprocessing/preprocessing_multiple_trace.py:360-527 with preprocessing/loss.py).  One row = one person in one frame; its free
  * parameters are params [MP_KP_PARAMS] = transl 3, thetas 72, betas 10 (scale 1, absolute transforms).  One workgroup per row.

@@ -1147,3 +1147,94 @@ def contact_distance(verts, faces, corr, bary, frame_start):
     lib().mp_contact_distance(verts.detach().contiguous(), F, P, V, faces.contiguous(), faces.shape[0], corr.contiguous() if m else None,
                               bary.contiguous() if m else None, frame_start.contiguous(), m, work, out, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ registration (csrc/registration.hip)
+REG_STATE, REG_SLOT, REG_MAX_BLOCKS = 32, 40, 256       # = include/multiply_hip.h MP_REG_STATE, MP_REG_SLOT, MP_REG_MAX_BLOCKS
+# indices into a state block / a slot (= the header's MP_REG_* / MP_REG_SLOT_* enums)
+REG_S, REG_R, REG_T, REG_TAU2, REG_RMS, REG_ACCEPTED, REG_REJECTED, REG_LEFT_OUT = 0, 1, 10, 13, 14, 15, 16, 17
+REG_ITERS, REG_FLAG, REG_STEP, REG_C, REG_BOX_LO, REG_BOX_HI, REG_RMS_PLANE = 18, 19, 20, 21, 24, 27, 30
+REG_SLOT_ATA, REG_SLOT_ATR, REG_SLOT_R2, REG_SLOT_D2, REG_SLOT_ACCEPTED, REG_SLOT_REJECTED, REG_SLOT_LEFT_OUT = 0, 28, 35, 36, 37, 38, 39
+REG_CONVERGED, REG_DEGENERATE = 1, 2
+
+
+def reg_state(scale, R, t, box_lo, box_hi, device, tau2=math.inf):
+    """a fresh state block (REG_STATE,) float64 on the device: the transform x = scale R p + t, the acceptance threshold tau2, the
+    target's bounding box and, as the fixed origin c, its centre; everything else zero"""
+    st = np.zeros(REG_STATE, np.float64)
+    st[REG_S] = float(scale)
+    st[REG_R:REG_R + 9] = np.asarray(R, np.float64).reshape(9)
+    st[REG_T:REG_T + 3] = np.asarray(t, np.float64).reshape(3)
+    st[REG_TAU2] = float(tau2)
+    lo, hi = np.asarray(box_lo, np.float64).reshape(3), np.asarray(box_hi, np.float64).reshape(3)
+    st[REG_C:REG_C + 3] = 0.5 * (lo + hi)
+    st[REG_BOX_LO:REG_BOX_LO + 3], st[REG_BOX_HI:REG_BOX_HI + 3] = lo, hi
+    return torch.from_numpy(st).to(device)
+
+
+def _reg_check_state(state):
+    if state.dtype != torch.float64 or state.numel() != REG_STATE:
+        raise ValueError(f"a registration state is {REG_STATE} float64 values, got {tuple(state.shape)} {state.dtype}")
+
+
+def reg_apply(pts, state, inverse=False, out=None):
+    """out = s R p + t, or R^T (p - t) / s with inverse=True, for pts (n,3) float32 and the transform of the state block
+    (mp_reg_apply): computed in double, rounded once"""
+    _reg_check_state(state)
+    pts = pts.detach().float().contiguous()
+    n = pts.shape[0]
+    out = torch.empty(n, 3, dtype=torch.float32, device=pts.device) if out is None else out
+    lib().mp_reg_apply(pts if n else None, n, state, int(bool(inverse)), out if n else None, stream())
+    return out
+
+
+def reg_work(device):
+    """the scratch of reg_rows (the workgroups' partial sums)"""
+    return torch.empty(REG_MAX_BLOCKS * REG_SLOT, dtype=torch.float64, device=device)
+
+
+def reg_rows(p, q, normals, state, slot, face=None, normals_in_source=False, work=None, mask=None):
+    """One direction's pairs into `slot` ((REG_SLOT,) float64, a row of the slots tensor) (mp_reg_rows): p (n,3) in the source
+    frame, q (n,3) in the target frame; normals (n,3) per pair, or with face (n,) int32 the table (F,3) those ids point into;
+    normals_in_source: the normals are rotated by the state's R.  mask: optional (n,) uint8 that receives 0 accepted / 1 rejected /
+    2 left out."""
+    _reg_check_state(state)
+    n = p.shape[0]
+    assert slot.dtype == torch.float64 and slot.numel() == REG_SLOT and q.shape[0] == n
+    for x in (p, q, normals):
+        assert x.dtype == torch.float32
+    if face is not None:
+        assert face.dtype == torch.int32 and face.shape[0] == n and normals.shape[0] >= 1
+    else:
+        assert normals.shape[0] == n
+    assert mask is None or (mask.dtype == torch.uint8 and mask.shape[0] == n)
+    work = reg_work(state.device) if work is None else work
+    assert work.dtype == torch.float64 and work.numel() >= REG_MAX_BLOCKS * REG_SLOT
+    lib().mp_reg_rows(p if n else None, q if n else None, normals if n else None, face if n else None,
+                      normals.shape[0] if face is not None else 0, int(bool(normals_in_source)), n, state, work, slot,
+                      mask if n else None, stream())
+    return slot
+
+
+def reg_step(slots, state, similarity=False, reject=3.0, tol=1e-6):
+    """One Gauss-Newton step from the sums in slots (k, REG_SLOT) float64, in place on the state block (mp_reg_step)"""
+    _reg_check_state(state)
+    assert slots.dtype == torch.float64 and slots.dim() == 2 and slots.shape[1] == REG_SLOT and slots.shape[0] >= 1
+    lib().mp_reg_step(slots, slots.shape[0], int(bool(similarity)), float(reject), float(tol), state, stream())
+    return state
+
+
+def reg_fit_pairs(p, q, weights=None, similarity=False):
+    """The closed-form fit of x = s R p + t to the pairs p, q (n,3) float32 with optional weights (n,) (mp_reg_fit_pairs): (16,)
+    float64 on the device = s, R (9, row-major), t (3), sum of weights, pairs left out, status (0; 1: no weight; 2: the p coincide)"""
+    if p.dim() != 2 or p.shape[1] != 3 or p.shape != q.shape:
+        raise ValueError(f"pairs must be two (n, 3) tensors of one shape, got {tuple(p.shape)} and {tuple(q.shape)}")
+    n = p.shape[0]
+    p, q = p.detach().float().contiguous(), q.detach().float().contiguous()
+    if weights is not None:
+        if tuple(weights.shape) != (n,):
+            raise ValueError(f"weights must be (n,) = {(n,)}, got {tuple(weights.shape)}")
+        weights = weights.detach().float().contiguous()
+    out = torch.empty(16, dtype=torch.float64, device=p.device)
+    lib().mp_reg_fit_pairs(p if n else None, q if n else None, weights if n else None, n, int(bool(similarity)), out, stream())
+    return out

@@ -156,14 +156,40 @@ def volume_iou(pred, gt, resolution, index_mode="auto"):
     return float(int((a & b).sum()) / union) if union else 0.0
 
 
+def _align(P, G, align, options, seed, index_mode):
+    """the prediction (vertices, faces) carried into the ground truth's frame, and the `align` entry of mesh_metrics' result"""
+    from . import registration as reg
+    if isinstance(align, reg.Similarity):
+        T, kind, info = align, "given", dict(rms=None, iterations=0, converged=None)
+    elif isinstance(align, str) and align in reg.KINDS:
+        opts = dict(seed=seed, index_mode=index_mode)
+        opts.update(options or {})
+        T, info = reg.register(P, G, kind=align, **opts)
+        kind = align
+    else:
+        raise ValueError(f"align must be None, one of {reg.KINDS} or a registration.Similarity, got {align!r}")
+    aligned = dict(kind=kind, scale=T.scale, matrix=T.matrix.tolist(), rms=info["rms"], iterations=info["iterations"],
+                   converged=info["converged"])
+    return (reg.transform_vertices(P[0], T), P[1]), aligned
+
+
 def mesh_metrics(pred, gt, n_samples=100_000, thresholds=(), seed=0, unit_scale=1.0, iou_resolution=None, index_mode="auto",
-                 details=None):
+                 details=None, align=None, align_options=None):
     """The metrics of the module's docstring between the meshes pred and gt (ExtractedMesh, (vertices, faces), or a PLY path) as
     a dict of floats (precision / recall / f_score: lists, one entry per threshold).  Both meshes are sampled with the SAME
     n_samples uniforms of a device generator seeded with `seed`, so a mesh's samples do not depend on which argument it is:
     swapping pred and gt swaps accuracy and completeness exactly.  details: a dict that receives the samples and the two queries
-    (for tests and plots)."""
+    (for tests and plots).  align: None (both meshes share a frame), 'rigid' / 'similarity' (registration.register of pred onto gt,
+    with the keyword arguments in align_options) or a registration.Similarity; the prediction's vertices are transformed before
+    sampling and before volume_iou, and the result gains align = {kind, scale, matrix, rms, iterations, converged}."""
+    if align is not None:
+        from . import registration as reg
+        if not isinstance(align, reg.Similarity) and not (isinstance(align, str) and align in reg.KINDS):
+            raise ValueError(f"align must be None, one of {reg.KINDS} or a registration.Similarity, got {align!r}")
     P, G = as_mesh(pred), as_mesh(gt)
+    aligned = None
+    if align is not None:
+        P, aligned = _align(P, G, align, align_options, seed, index_mode)
     dev, s = P[0].device, float(unit_scale)
     if len(thresholds) > 8:
         raise ValueError("at most 8 thresholds")
@@ -188,4 +214,6 @@ def mesh_metrics(pred, gt, n_samples=100_000, thresholds=(), seed=0, unit_scale=
                n_samples=int(n_samples), n_left_out=int(a[6] + c[6]))
     if iou_resolution:
         out["volume_iou"] = volume_iou(P, G, iou_resolution, index_mode)
+    if aligned is not None:
+        out["align"] = aligned
     return out
