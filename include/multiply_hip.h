@@ -1068,6 +1068,65 @@ typedef struct {
 int mp_adam_multi(const MpAdamDesc* descs, int n_desc, int total_blocks, const float* lr, const unsigned char* skip, double beta1,
                   double beta2, double eps, void* stream);
 
+/* ---- shaded mesh overlays: the QC images of preprocessing and testing (multiply_amd/overlay.py, csrc/overlay.hip; the reference
+ * draws them one mesh at a time with pytorch3d and cv2.circle, preprocessing_multiple_trace.py:330-342, 496-510 and
+ * ait_viewer_vis/vis_mesh_image.py; both are third party and unpinned, so the rule below is the project's own).
+ *   mp_mesh_vertex_normals   : N meshes verts [N][V][3] that share faces [n_faces][3]: normals[n][v] = s / max(|s|, 1e-6) with s =
+ *                              sum of cross(v1 - v0, v2 - v0) over the faces adj_face[adj_ptr[v] .. adj_ptr[v + 1]) (the faces
+ *                              that contain v, ascending, once per occurrence; built on the host once per topology).  One thread
+ *                              per vertex, no atomics: a mesh's normals have the same bits alone and at any position of any
+ *                              batch; a vertex of no face gives 0.  Status -1 without a launch: N, V or n_faces < 0, with N V > 0
+ *                              a NULL verts / adj_ptr / normals (faces / adj_face with n_faces > 0), N V >= 2^31; N V == 0 returns
+ *                              0 and touches nothing.
+ *   mp_overlay_vertex_colors : colors [N][V][3] from normals [N][V][3].  MP_OVERLAY_NORMAL: (0.5 n + 0.5) with the channels
+ *                              reversed (z, y, x);  MP_OVERLAY_SHADE: d = max(n . light, 0) on all three channels;
+ *                              MP_OVERLAY_TINT: tint[n][ch] (ambient + (1 - ambient) d), tint [N][3] DEVICE floats.  light =
+ *                              (lx, ly, lz) as given (not normalised).  Status -1 without a launch: N or V < 0, with N V > 0 a
+ *                              NULL normals / colors (tint in tint mode), N V >= 2^31; -2: an unknown mode; N V == 0 returns 0
+ *                              and touches nothing.
+ *   mp_overlay_batch         : n_rec meshes into M images [H][W][3] bytes.  recs = DEVICE array of MpOverlayMesh: verts [n_verts][3]
+ *                              world space, faces [n_faces][3], colors [n_verts][3] (records may share any of them), image in
+ *                              [0, M), face_base = the exclusive prefix sum of n_faces over the table, block0 = that of
+ *                              ceil(n_faces / 256); total_faces and total_blocks are the two sums.  cams_host [n_cam][16] HOST
+ *                              floats, n_cam = 1 (all images) or M, mp_raster_zbuf's layout and pixel convention; z_clip its.
+ *                              Visibility is mp_raster_zbuf's rule with the same projection, box and coverage arithmetic: one
+ *                              64-bit atomicMin per covered pixel on keys [M][H][W] with key = depth bits << 32 | (face_base + f),
+ *                              so ties go to the earlier record, then the lower face: what mp_raster_zbuf gives on an image's
+ *                              meshes joined in record order.  The grid is the records' face blocks concatenated (a block finds
+ *                              its record by binary search); faces whose pixel box exceeds 48 centres go through the queue big
+ *                              [1 + total_faces] and a second launch; the number of launches does not depend on n_rec.
+ *                              The resolve pass (one thread per pixel) recomputes the winner's perspective-correct barycentrics,
+ *                              c = b0 c0 + b1 c1 + b2 c2 per channel, the mesh byte m = floor(255 clamp(c, 0, 1)), and with f =
+ *                              the byte of frames [M][H][W][3] (frames == NULL: of background_host, 3 HOST bytes):
+ *                              out = floor(fmaf(opacity, m - f, f) + 0.5);  an uncovered pixel keeps f.  Keypoints are painted
+ *                              last: keypoints [M][K][3] = (x, y, conf), kp_rgb [K][3] bytes: pixel (r, c) takes keypoint k's
+ *                              colour when conf > kp_conf, x and y are finite and (c - floor x)^2 + (r - floor y)^2 <=
+ *                              kp_radius^2 in integers; the highest such k wins.  owner [M][H][W] (optional) = the winner's
+ *                              record or -1.  Scratch: keys, big, cam_dev [n_cam][16] floats (the cameras' device copy).
+ *                              Status -1 without a launch: n_rec, total_blocks, total_faces, M or K < 0, H or W < 1, with M > 0
+ *                              a NULL cams_host / keys / cam_dev / out (background_host with NULL frames; recs / big with n_rec >
+ *                              0; keypoints / kp_rgb with K > 0), M H W >= 2^31;  -2: n_cam not 1 or M, total_faces >= 2^32 - 1,
+ *                              opacity outside [0, 1], kp_radius outside [0, 4096];  M == 0 returns 0 and touches nothing.
+ *                              n_rec == 0 with M > 0 gives the frames (background) plus the keypoints. */
+enum { MP_OVERLAY_NORMAL = 0, MP_OVERLAY_SHADE = 1, MP_OVERLAY_TINT = 2 };
+typedef struct {
+    const float* verts;
+    const int* faces;
+    const float* colors;
+    int n_verts, n_faces, image, block0;
+    unsigned face_base;
+    int pad_;
+} MpOverlayMesh;
+int mp_mesh_vertex_normals(const float* verts, int N, int V, const int* faces, int n_faces, const int* adj_ptr, const int* adj_face,
+                           float* normals, void* stream);
+int mp_overlay_vertex_colors(const float* normals, int N, int V, int mode, const float* tint, float lx, float ly, float lz,
+                             float ambient, float* colors, void* stream);
+int mp_overlay_batch(const MpOverlayMesh* recs, int n_rec, int total_blocks, long long total_faces, int M, int H, int W,
+                     const float* cams_host, int n_cam, float z_clip, const unsigned char* frames,
+                     const unsigned char* background_host, float opacity, const float* keypoints, int K,
+                     const unsigned char* kp_rgb, float kp_conf, int kp_radius, unsigned long long* keys, unsigned* big,
+                     float* cam_dev, unsigned char* out, int* owner, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

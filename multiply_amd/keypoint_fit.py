@@ -22,7 +22,7 @@ the whole Adam loop in one launch, one workgroup per person-frame (mp_kp_fit; mp
 
 Parameters are rows of 85 = [transl 3, thetas 72, betas 10] (pack_params / split_params); scale is 1 and the transforms absolute,
 as in the reference's fit.  Not built: the spline interpolation of missing frames (interpolate_frames copies, as the loop does),
-person matching, the distance gate between the two keypoint sets, the overlay images.  This module imports without a device."""
+person matching, the distance gate between the two keypoint sets (the overlay images: overlay.py).  This module imports without a device."""
 import warnings
 
 import numpy as np

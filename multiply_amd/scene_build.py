@@ -4,7 +4,7 @@ preprocessing/normalize_cameras_trace.py:6-61, over a whole sequence at once on 
 
 `build_scene` takes what keypoint_fit.refine_sequence returns (pose, trans, shape per person-frame in camera space) and produces
 poses.npy, normalize_trans.npy, mean_shape.npy, gender.npy, cameras.npz, max_human_sphere.npy, cameras_normalize.npz, mask/<p>/*.png
-and image/*.png.  Its definitions, in the order they are applied:
+and image/*.png; with overlays=True also the QC images overlay/<p>/*.png and overlay/all/*.png (write_overlays).  Its definitions, in the order they are applied:
 
   1 mean shape     mean_shape[p] = mean over the frames of shape[:, p] (:590-592); every body below is posed with it (:552-557).
   2 scene space    per person-frame, float64 on the host (transform_smpl_remain_extrinsic, :72-84): with the current extrinsic
@@ -206,7 +206,7 @@ def _np(x):
 
 
 def build_scene(servers, refined, intrinsics, img_size, out_dir=None, frames=None, genders=None, normalize="per_frame", dilate=20,
-                scale_factor=1, extrinsic=None, rows_per_call=None):
+                scale_factor=1, extrinsic=None, rows_per_call=None, overlays=False):
     """servers: one SMPLServer per person, or one for all (as refine_sequence); refined: dict of pose (F, P, 72), trans (F, P, 3),
     shape (F, P, 10) in camera space; intrinsics (3, 3); img_size (H, W) of the frames; frames: F PNG paths or None (no image/);
     genders: P names for gender.npy (default 'neutral', :594).  Returns a dict: poses (F, P, 72), normalize_trans (F, P, 3),
@@ -215,8 +215,11 @@ def build_scene(servers, refined, intrinsics, img_size, out_dir=None, frames=Non
     -> {count (F, P), bbox (F, P, 4), centre (F, P, 2)} and img_size.  With out_dir the folder datasets.py reads is written (the
     module docstring has every definition and the deviations from the reference).  The silhouettes are rendered at the OUTPUT size
     (H // s, W // s) with the divided intrinsics, where the reference renders at full size and resizes the mask: less than a pixel
-    at the outline, under the dilation."""
+    at the outline, under the dilation.
+    overlays (needs out_dir and frames): also writes the QC images overlay/<p>/%04d.png and overlay/all/%04d.png (write_overlays)."""
     hip.require_device()
+    if overlays and (out_dir is None or frames is None):
+        raise ValueError("overlays are drawn over the written image/ folder: they need out_dir and frames")
     if normalize not in NORMALIZE_MODES:
         raise ValueError(f"normalize must be one of {NORMALIZE_MODES}, got {normalize!r}")
     s = int(scale_factor)
@@ -277,6 +280,8 @@ def build_scene(servers, refined, intrinsics, img_size, out_dir=None, frames=Non
                mask_stats=stats, img_size=(H, W), genders=genders)
     if out_dir is not None:
         write_scene(out_dir, out, frames, s)
+        if overlays:
+            write_overlays(out_dir, verts, faces, cam16, (H, W), rows_per_call)
     return out
 
 
@@ -308,6 +313,47 @@ def write_scene(out_dir, scene, frames=None, scale_factor=1):
             if (img.size[1], img.size[0]) != tuple(scene["img_size"]):
                 raise ValueError(f"{path}: {img.size[1]} x {img.size[0]} after the reduction, the masks are {scene['img_size']}")
             img.save(os.path.join(out_dir, "image", "%04d.png" % f))
+
+
+def write_overlays(out_dir, verts, faces, cam16, img_size, frames_per_call=None):
+    """The QC images of a written scene folder (the reference's init_smpl_image/ and init_refined_smpl/ folders,
+    preprocessing_multiple_trace.py:330-342, 496-510), over the folder's own image/%04d.png: overlay/<p>/%04d.png = person p in
+    'normal' colours, overlay/all/%04d.png = all persons tinted with mesh_losses.COLOR_DICT and z-tested against each other
+    (overlay.render_overlays).  verts (F, P, V, 3): the posed bodies v'; cam16: the camera of the silhouettes -- the scene's written
+    intrinsics and [Rt | 0]: the written cam_f = K4 [Rt | -Rt shift_f] acts on v' + shift_f, the shift cancels, and with the
+    silhouettes' own arithmetic an overlay covers exactly the pixels of the undilated mask.  frames_per_call bounds the frames held
+    at once (default 16)."""
+    from PIL import Image
+    from . import overlay as OV
+    from .mesh_losses import COLOR_DICT
+    F, P = verts.shape[:2]
+    H, W = img_size
+    dev = verts.device
+    step = 16 if frames_per_call is None else max(1, int(frames_per_call))
+    adj = tuple(torch.from_numpy(a).to(dev) for a in OV.vertex_adjacency(faces, verts.shape[2]))
+    tint = torch.tensor([COLOR_DICT[p % len(COLOR_DICT)] for p in range(P)], dtype=torch.float32, device=dev) / 255.0
+    for name in ["all"] + ["%d" % p for p in range(P)]:
+        os.makedirs(os.path.join(out_dir, "overlay", name), exist_ok=True)
+    for f0 in range(0, F, step):
+        f1 = min(F, f0 + step)
+        n = f1 - f0
+        img = np.stack([np.asarray(Image.open(os.path.join(out_dir, "image", "%04d.png" % f)).convert("RGB")) for f in range(f0, f1)])
+        if img.shape[1:3] != (H, W):
+            raise ValueError(f"image/: {img.shape[1]} x {img.shape[2]}, the scene is {H} x {W}")
+        fr = torch.from_numpy(img).to(dev)
+        v = verts[f0:f1].reshape(n * P, -1, 3).contiguous()
+        nrm = OV.vertex_normals(v, faces, adj)
+        image_of = [i // P for i in range(n * P)]
+        pics = {"all": OV.render_overlays((v, faces, OV.vertex_colors(nrm, "tint", tint=tint.repeat(n, 1))), image_of, cam16, H, W,
+                                          frames=fr)}
+        col = OV.vertex_colors(nrm, "normal").reshape(n, P, -1, 3)
+        for p in range(P):
+            pics["%d" % p] = OV.render_overlays((verts[f0:f1, p].contiguous(), faces, col[:, p].contiguous()), list(range(n)), cam16,
+                                                H, W, frames=fr)
+        for name, pic in pics.items():
+            pic = pic.cpu().numpy()
+            for i in range(n):
+                Image.fromarray(pic[i]).save(os.path.join(out_dir, "overlay", name, "%04d.png" % (f0 + i)))
 
 
 # ------------------------------------------------------------------------------------------------ between detector output and refine

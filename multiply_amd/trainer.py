@@ -654,7 +654,8 @@ class Trainer:
         """multiply_model.py:1183-1323 for every test frame (or `frames`): test_mesh/<p>/%04d_{canonical,deformed}.ply and, per
         view id in (-1, 0 .. P-1), test_rendering / test_fg_rendering / test_normal / test_mask/<id>/%04d.png, plus
         test_instance_mask/<p>/%04d.png -- all of the frame's size (the reference stacks the ground truth above the rendering;
-        here the rendering alone is written, which is what tools/eval_images.py compares)."""
+        here the rendering alone is written, which is what tools/eval_images.py compares).  With the config key test_overlay
+        (default False) also test_overlay/%04d.png: the deformed meshes tinted per person over the input frame (_write_test_overlay)."""
         from .mesh import ExtractedMesh
         from .mesh_losses import skinning
         with _working_dir(self.out_dir):
@@ -663,6 +664,7 @@ class Trainer:
                 inputs, targets, ppb, total, idx = self._test_inputs(i)
                 H, W = (int(x) for x in targets["img_size"])
                 meshes = self._canonical_meshes(inputs, self.opt.get("test_res_up", 4))
+                deformed = []
                 for p, m in enumerate(meshes):
                     server, deformer = self.model.smpl_server_list[p], self.model.deformer_list[p]
                     so = server(inputs["smpl_params"][:, p, 0], inputs["smpl_trans"][:, p], inputs["smpl_pose"][:, p],
@@ -676,6 +678,9 @@ class Trainer:
                     os.makedirs(f"test_mesh/{p}", exist_ok=True)
                     m.export(f"test_mesh/{p}/{idx:04d}_canonical.ply")
                     ExtractedMesh(posed, m["faces"]).export(f"test_mesh/{p}/{idx:04d}_deformed.ply")
+                    deformed.append((posed, m["faces"]))
+                if self.opt.get("test_overlay", False):
+                    self._write_test_overlay(inputs, targets, deformed, idx)
                 views = self._render_frame(inputs, total, min(ppb, total),
                                            ("rgb_values", "fg_rgb_values", "normal_values", "acc_map", "acc_person_list"))
                 for vid, v in views.items():
@@ -687,6 +692,25 @@ class Trainer:
                         inst = v["acc_person_list"].reshape(H, W, -1)
                         for p in range(inst.shape[2]):
                             _write_png(f"test_instance_mask/{p}/{idx:04d}.png", _to_u8(inst[:, :, p]))
+
+    def _write_test_overlay(self, inputs, targets, deformed, idx):
+        """test_overlay/%04d.png (the reference's ait_viewer_vis/vis_mesh_image.py): the frame's deformed meshes -- another
+        topology per person, hence overlay.render_overlays' record table --, each tinted with its mesh_losses.COLOR_DICT colour,
+        z-tested against each other and laid over the input frame with opacity 0.6, through the frame's own camera"""
+        from . import overlay as OV
+        from .mesh_losses import COLOR_DICT
+        from .render import get_renderer
+        H, W = (int(x) for x in targets["img_size"])
+        cam = list(get_renderer(inputs)._cam16())
+        scale = float(inputs["smpl_params"][0, 0, 0])                             # the renderer's units: get_renderer
+        recs = []
+        for p, (v, f) in enumerate(deformed):
+            v = (v.detach().float() / scale).contiguous()
+            tint = [c / 255.0 for c in COLOR_DICT[p % len(COLOR_DICT)]]
+            recs.append((v, f, OV.vertex_colors(OV.vertex_normals(v, f), "tint", tint=tint)))
+        frame = (targets["rgb"].reshape(1, H, W, 3).float() * 255).round().clamp(0, 255).to(torch.uint8)
+        out = OV.render_overlays(recs, [0] * len(recs), cam, H, W, frames=frame, opacity=0.6)
+        _write_png(f"test_overlay/{idx:04d}.png", out[0].cpu().numpy())
 
     # ------------------------------------------------------------------ checkpoints
     def checkpoint(self):

@@ -8,7 +8,8 @@ RAW holds
   extrinsic.npy        optional (3, 4) / (4, 4) world-to-camera, identity without it
   frames/*.png         optional, one per frame in sorted order; without them no image/ is written and --img-size is needed
 OUT receives image/, mask/<person>/, poses.npy, mean_shape.npy, normalize_trans.npy, gender.npy, cameras.npz, max_human_sphere.npy
-and cameras_normalize.npz.  Prints one JSON line of summary."""
+and cameras_normalize.npz; with --overlays (needs frames) also the QC images overlay/<person>/ (the body in normal colours over the
+frame) and overlay/all/ (all persons tinted, z-tested against each other).  Prints one JSON line of summary."""
 import argparse
 import glob
 import json
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--gender", nargs="+", default=["neutral"], help="one for all persons, or one per person")
     ap.add_argument("--smpl-dir", default=None, help="folder of SMPL_<GENDER>.pkl (default: $MULTIPLY_SMPL_DIR)")
     ap.add_argument("--img-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="only without RAW/frames")
+    ap.add_argument("--overlays", action="store_true", help="write OUT/overlay/<person>/ and OUT/overlay/all/ (needs RAW/frames)")
     a = ap.parse_args()
     from multiply_amd import scene_build as SB
     from multiply_amd.smpl import SMPLServer, load_smpl_tables
@@ -49,6 +51,8 @@ def main():
         raise SystemExit(f"no frames/*.png under {a.raw}: give --img-size H W")
     else:
         img_size = tuple(a.img_size)
+    if a.overlays and frames is None:
+        raise SystemExit(f"--overlays draws over the frames: no frames/*.png under {a.raw}")
     ext = os.path.join(a.raw, "extrinsic.npy")
     ext = np.load(ext) if os.path.exists(ext) else None
     genders = a.gender if len(a.gender) > 1 else a.gender * P
@@ -58,7 +62,7 @@ def main():
     t0 = time.perf_counter()
     sc = SB.build_scene([servers[g] for g in genders], refined, np.load(os.path.join(a.raw, "intrinsics.npy")), img_size,
                         out_dir=a.out, frames=frames, genders=genders, normalize=a.normalize.replace("-", "_"), dilate=a.dilate,
-                        scale_factor=a.scale_factor, extrinsic=ext)
+                        scale_factor=a.scale_factor, extrinsic=ext, overlays=a.overlays)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     H, W = sc["img_size"]
@@ -68,7 +72,7 @@ def main():
                       "max_human_sphere": sc["max_human_sphere"], "scale": 1.0 / float(sc["cameras_normalize"]["scale_mat_0"][0, 0]),
                       "covered_fraction_min": [float(x) for x in frac.min(0)], "covered_fraction_mean": [float(x) for x in frac.mean(0)],
                       "empty_mask_person_frames": int((sc["mask_stats"]["raw"]["count"] == 0).sum()), "seconds": dt,
-                      "out": os.path.abspath(a.out)}))
+                      "out": os.path.abspath(a.out), **({"overlays": os.path.join(os.path.abspath(a.out), "overlay")} if a.overlays else {})}))
 
 
 if __name__ == "__main__":

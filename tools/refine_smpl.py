@@ -9,7 +9,11 @@ The scene folder holds
   intrinsics.npy           (3, 3)
   J_regressor_extra.npy    optional (9, 6890): the reference's extra joint regressor, needed by coco17's hips
   extrinsic.npy            optional (3, 4) / (4, 4) world-to-camera, identity without it
-and receives refined_smpl.npz (pose, trans, shape, terms (F, P, 3), flags (F, P)).  Prints one JSON line of summary."""
+  frames/*.png             optional, one per frame in sorted order: needed by --overlays
+and receives refined_smpl.npz (pose, trans, shape, terms (F, P, 3), flags (F, P)).  --overlays DIR writes the QC images
+DIR/init/<p>/%04d.png and DIR/refined/<p>/%04d.png: the body before / after the fit in normal colours over the frame, the detected
+keypoints above the confidence threshold in red, the model's projected keypoints in green (multiply_amd.overlay).  Prints one JSON
+line of summary."""
 import argparse
 import glob
 import json
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--interpolate-frames", type=int, nargs="*", default=[])
     ap.add_argument("--tracking", type=int, nargs="*", default=[], help="frame person frame person ...")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--overlays", default=None, metavar="DIR", help="write DIR/init/<p>/ and DIR/refined/<p>/ (needs SCENE/frames/*.png)")
     a = ap.parse_args()
     from multiply_amd import keypoint_fit as KF
     from multiply_amd.smpl import SMPLServer, load_smpl_tables
@@ -49,6 +54,9 @@ def main():
         raise SystemExit(f"{len(files)} keypoint files against {F} frames of initial values")
     if len(a.tracking) % 2:
         raise SystemExit("--tracking takes (frame, person) pairs")
+    frames = sorted(glob.glob(os.path.join(a.scene, "frames", "*.png")))
+    if a.overlays is not None and len(frames) != F:
+        raise SystemExit(f"--overlays draws over the frames: {len(frames)} frames/*.png against {F} frames of initial values")
     extra = os.path.join(a.scene, "J_regressor_extra.npy")
     extra = np.load(extra) if os.path.exists(extra) else None
     kmap = getattr(KF.KeypointMap, a.format)(extra)
@@ -67,10 +75,16 @@ def main():
     dt = time.perf_counter() - t0
     path = a.out or os.path.join(a.scene, "refined_smpl.npz")
     np.savez(path, **res)
+    if a.overlays is not None:
+        from multiply_amd import overlay as OV
+        for name, fit in (("init", init), ("refined", res)):
+            OV.write_fit_overlays(os.path.join(a.overlays, name), [servers[g] for g in genders], fit, kps, kmap, cam, frames,
+                                  conf_threshold=a.conf_threshold)
     print(json.dumps({"tool": "refine_smpl", "scene": os.path.abspath(a.scene), "frames": F, "persons": P, "format": a.format,
                       "iters": a.iters, "keypoints": kmap.K, "support_vertices": kmap.S, "notes": kmap.notes,
                       "mean_total_loss": float(np.nanmean(res["terms"][..., 2])), "mean_l2d": float(np.nanmean(res["terms"][..., 0])),
-                      "flagged_person_frames": int(res["flags"].sum()), "seconds": dt, "out": os.path.abspath(path)}))
+                      "flagged_person_frames": int(res["flags"].sum()), "seconds": dt, "out": os.path.abspath(path),
+                      **({"overlays": os.path.abspath(a.overlays)} if a.overlays is not None else {})}))
 
 
 if __name__ == "__main__":
