@@ -1127,6 +1127,47 @@ int mp_overlay_batch(const MpOverlayMesh* recs, int n_rec, int total_blocks, lon
                      const unsigned char* kp_rgb, float kp_conf, int kp_radius, unsigned long long* keys, unsigned* big,
                      float* cam_dev, unsigned char* out, int* owner, void* stream);
 
+/* ---- mesh simplification: vertex clustering with quadric-optimal representatives (Lindstrom 2000; multiply_amd/simplify.py,
+ * csrc/simplify.hip, csrc/quadric_solve.hpp).  The reference has no counterpart.  The host sorts (torch) between the
+ * launches; everything that reads a coordinate is here.  Index arrays that torch's sorts and prefix sums produce are long long.
+ *   mp_simplify_keys     : key[v] = i << 42 | j << 21 | k with (i, j, k) = floor((verts[v] - lo) * inv_h) per axis in fp32, one
+ *                          subtraction and one multiplication, each rounded to nearest and never contracted; an index is clamped
+ *                          to [0, MP_SIMPLIFY_MAX_INDEX] (the host checks the bounding box first, so nothing is).  One thread per
+ *                          vertex.
+ *   mp_simplify_count    : live[f] = 1 when the keys of face f's three corners are pairwise different, else 0 (the count pass of
+ *                          the target-face bisection; needs no cell ids).  A corner outside [0, n_verts) gives 0.
+ *   mp_simplify_faces    : cell [n_verts] = each vertex's cell id (rank of its key).  tri[f] = the ids of the corners in the face's
+ *                          own order, live[f] as above, key_lo[f] = min << 32 | mid and key_hi[f] = max of the three ids (the
+ *                          unordered triple); a face that is not live gets key_lo = 2^63 - 1, key_hi = 2^31 - 1 and sorts last.
+ *   mp_simplify_first    : order [n_faces] = the faces sorted by (key_lo, key_hi), stably, so equal triples are in ascending face
+ *                          order: keep[order[s]] = live and (s == 0 or the triple of order[s - 1] differs).
+ *   mp_simplify_quadrics : per cell c (keys [n_cells] ascending): centre = lo + (ijk + 0.5) h in double.  pair_order
+ *                          [pair_start[c] .. pair_start[c + 1]) = the pair indices 3 f + corner whose corner lies in c, ascending
+ *                          (a stable sort of tri); each adds n n^T and n (n . (p0 - centre)), n = (p1 - p0) x (p2 - p0), in
+ *                          double.  vert_order [vert_start[c] .. vert_start[c + 1]) = the cell's own vertices, ascending: their
+ *                          mean relative to the centre.  MP_SIMPLIFY_LANES lanes share a cell: lane l adds entries l, l + LANES,
+ *                          ... of each list in order, the lanes are added by the xor butterfly -- a fixed order, no atomics, the
+ *                          same bits on every run.  Then quadric_point (quadric_solve.hpp) and pos[c] = (float)(centre + x).
+ *   mp_simplify_attr_mean: out[c][k] = (float)(sum of attrs[v][k] over the cell's vertices in vert_order, in double / their number),
+ *                          one thread per (c, k).
+ *   Status -1 without a launch: a negative size, a NULL array that the sizes make necessary, inv_h / h / lam not positive and
+ *   finite, 3 n_faces >= 2^31, n_cells K >= 2^38.  A size of zero returns 0 and touches nothing (no launch with an empty grid). */
+#define MP_SIMPLIFY_BITS 21
+#define MP_SIMPLIFY_MAX_INDEX ((1 << MP_SIMPLIFY_BITS) - 1)
+#define MP_SIMPLIFY_LANES 16
+int mp_simplify_keys(const float* verts, int n_verts, float lo_x, float lo_y, float lo_z, float inv_h, long long* key, void* stream);
+int mp_simplify_count(const int* faces, int n_faces, const long long* key, int n_verts, unsigned char* live, void* stream);
+int mp_simplify_faces(const int* faces, int n_faces, const int* cell, int n_verts, int* tri, long long* key_lo, int* key_hi,
+                      unsigned char* live, void* stream);
+int mp_simplify_first(const long long* order, int n_faces, const long long* key_lo, const int* key_hi, const unsigned char* live,
+                      unsigned char* keep, void* stream);
+int mp_simplify_quadrics(const float* verts, int n_verts, const int* faces, int n_faces, const long long* keys, int n_cells,
+                         const long long* pair_order, const long long* pair_start, const long long* vert_order,
+                         const long long* vert_start, float lo_x, float lo_y, float lo_z, float h, double lam, float* pos,
+                         void* stream);
+int mp_simplify_attr_mean(const float* attrs, int n_verts, int K, const long long* vert_order, const long long* vert_start,
+                          int n_cells, float* out, void* stream);
+
 /* library / device info: returns the gfx arch string compiled in, and checks the current device */
 const char* mp_arch(void);
 int mp_device_ok(void);

@@ -1238,3 +1238,82 @@ def reg_fit_pairs(p, q, weights=None, similarity=False):
     out = torch.empty(16, dtype=torch.float64, device=p.device)
     lib().mp_reg_fit_pairs(p if n else None, q if n else None, weights if n else None, n, int(bool(similarity)), out, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh simplification
+# (csrc/simplify.hip; the header documents every array; multiply_amd/simplify.py sorts between these calls)
+SIMPLIFY_BITS, SIMPLIFY_LANES = 21, 16
+
+
+def _simplify_mesh_args(verts, faces):
+    assert verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+    return verts.shape[0], faces.shape[0]
+
+
+def simplify_keys(verts, lo, inv_h):
+    """key (V,) int64 of every vertex's cell (mp_simplify_keys): lo = three floats, inv_h = the fp32 value of 1.0f / h"""
+    assert verts.dtype == torch.float32 and verts.dim() == 2 and verts.shape[1] == 3
+    n = verts.shape[0]
+    key = torch.empty(n, dtype=torch.int64, device=verts.device)
+    lib().mp_simplify_keys(verts if n else None, n, float(lo[0]), float(lo[1]), float(lo[2]), float(inv_h), key if n else None, stream())
+    return key
+
+
+def simplify_count(faces, key):
+    """live (F,) uint8: the three corners of the face lie in three different cells (mp_simplify_count)"""
+    assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and key.dtype == torch.int64
+    F, V = faces.shape[0], key.shape[0]
+    live = torch.empty(F, dtype=torch.uint8, device=faces.device)
+    lib().mp_simplify_count(faces if F else None, F, key if V else None, V, live if F else None, stream())
+    return live
+
+
+def simplify_faces(faces, cell):
+    """(tri (F,3) int32 cell ids, key_lo (F,) int64, key_hi (F,) int32, live (F,) uint8) (mp_simplify_faces)"""
+    assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and cell.dtype == torch.int32
+    F, V, dev = faces.shape[0], cell.shape[0], faces.device
+    tri = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    key_lo = torch.empty(F, dtype=torch.int64, device=dev)
+    key_hi = torch.empty(F, dtype=torch.int32, device=dev)
+    live = torch.empty(F, dtype=torch.uint8, device=dev)
+    lib().mp_simplify_faces(faces if F else None, F, cell if V else None, V, tri if F else None, key_lo if F else None,
+                            key_hi if F else None, live if F else None, stream())
+    return tri, key_lo, key_hi, live
+
+
+def simplify_first(order, key_lo, key_hi, live):
+    """keep (F,) uint8: the face is live and the first of its unordered triple in the sorted order (mp_simplify_first)"""
+    F = order.shape[0]
+    assert order.dtype == torch.int64 and key_lo.dtype == torch.int64 and key_hi.dtype == torch.int32 and live.dtype == torch.uint8
+    assert key_lo.shape[0] == F and key_hi.shape[0] == F and live.shape[0] == F
+    keep = torch.zeros(F, dtype=torch.uint8, device=order.device)
+    lib().mp_simplify_first(order if F else None, F, key_lo if F else None, key_hi if F else None, live if F else None,
+                            keep if F else None, stream())
+    return keep
+
+
+def simplify_quadrics(verts, faces, keys, pair_order, pair_start, vert_order, vert_start, lo, h, lam):
+    """pos (C,3) float32: every cell's representative (mp_simplify_quadrics)"""
+    V, F = _simplify_mesh_args(verts, faces)
+    C = keys.shape[0]
+    for t in (keys, pair_order, pair_start, vert_order, vert_start):
+        assert t.dtype == torch.int64
+    assert pair_order.shape[0] == 3 * F and vert_order.shape[0] == V and pair_start.shape[0] == C + 1 and vert_start.shape[0] == C + 1
+    pos = torch.empty(C, 3, dtype=torch.float32, device=verts.device)
+    lib().mp_simplify_quadrics(verts if V else None, V, faces if F else None, F, keys if C else None, C, pair_order if F else None,
+                               pair_start, vert_order if V else None, vert_start, float(lo[0]), float(lo[1]), float(lo[2]), float(h),
+                               float(lam), pos if C else None, stream())
+    return pos
+
+
+def simplify_attr_mean(attrs, vert_order, vert_start):
+    """out (C,K) float32: per cell the mean of its vertices' rows of attrs (V,K) (mp_simplify_attr_mean)"""
+    assert attrs.dtype == torch.float32 and attrs.dim() == 2 and vert_order.dtype == torch.int64 and vert_start.dtype == torch.int64
+    V, K = attrs.shape
+    C = vert_start.shape[0] - 1
+    assert vert_order.shape[0] == V
+    out = torch.empty(C, K, dtype=torch.float32, device=attrs.device)
+    lib().mp_simplify_attr_mean(attrs if V * K else None, V, K, vert_order if V else None, vert_start, C, out if C * K else None,
+                                stream())
+    return out

@@ -239,6 +239,14 @@ class ExtractedMesh:
                 out.append(part)
         return out
 
+    def simplify(self, cell=None, target_faces=None):
+        """the mesh reduced by quadric vertex clustering (multiply_amd/simplify.py): an ExtractedMesh whose record is that of
+        simplify_mesh (cell, origin, n_cells, n_collapsed, n_duplicate, n_unreferenced, passes).  Exactly one of cell (the cluster
+        size, in the mesh's unit) and target_faces."""
+        from .simplify import simplify_mesh
+        verts, faces, info = simplify_mesh(self.vertices_t, self.faces_t, cell=cell, target_faces=target_faces)
+        return ExtractedMesh(verts, faces, **info)
+
     def export(self, path):
         """binary little-endian PLY (vertices float32, faces int32), the format the reference's callers write"""
         v, f = self.vertices.astype("<f4"), self.faces.astype("<i4")

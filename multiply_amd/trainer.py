@@ -655,7 +655,10 @@ class Trainer:
         view id in (-1, 0 .. P-1), test_rendering / test_fg_rendering / test_normal / test_mask/<id>/%04d.png, plus
         test_instance_mask/<p>/%04d.png -- all of the frame's size (the reference stacks the ground truth above the rendering;
         here the rendering alone is written, which is what tools/eval_images.py compares).  With the config key test_overlay
-        (default False) also test_overlay/%04d.png: the deformed meshes tinted per person over the input frame (_write_test_overlay)."""
+        (default False) also test_overlay/%04d.png: the deformed meshes tinted per person over the input frame (_write_test_overlay).
+        With test_mesh_cell (a cluster size in canonical units) or test_mesh_faces (a face count), both default None, each canonical
+        mesh is simplified (ExtractedMesh.simplify) before its skinning weights are queried: both PLY files and the overlay then
+        carry the reduced mesh."""
         from .mesh import ExtractedMesh
         from .mesh_losses import skinning
         with _working_dir(self.out_dir):
@@ -664,6 +667,9 @@ class Trainer:
                 inputs, targets, ppb, total, idx = self._test_inputs(i)
                 H, W = (int(x) for x in targets["img_size"])
                 meshes = self._canonical_meshes(inputs, self.opt.get("test_res_up", 4))
+                cell, n_faces = self.opt.get("test_mesh_cell", None), self.opt.get("test_mesh_faces", None)
+                if cell is not None or n_faces is not None:                        # both unset: the meshes as extracted
+                    meshes = [m.simplify(cell=cell, target_faces=n_faces) for m in meshes]
                 deformed = []
                 for p, m in enumerate(meshes):
                     server, deformer = self.model.smpl_server_list[p], self.model.deformer_list[p]
